@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: MLUPS of the D2Q9-BGK time-step path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1024x1024|8192x8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1024x1024|8192x8192] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -206,9 +206,28 @@ def kernel_of(lat, tb):
     return f"lbm_sweep<{int(lat.info('vector_width'))}>", 72.0
 
 
-def measure(name, world, rank, local_rank, steps, warmup):
+DUMP_BYTES = 63 * 10**6   # --dump-outputs: the arrays of all files together (under 64 MB with the .npy headers)
+DUMP_SEED = 20261015      # the fixed seed of the sample taken of an output larger than its share
+
+
+def dump_sample(a: np.ndarray, max_bytes: int) -> np.ndarray:
+    """`a` itself if it fits `max_bytes`, else a fixed sample of its elements: seeded, the same positions in every run
+    on the same shape, flattened in index order.  A per-step series (1-D) keeps its LAST entries instead, so that the
+    timed run's last step is always there."""
+    k = max_bytes // a.itemsize
+    if a.size <= k:
+        return a
+    if a.ndim == 1:
+        return a[-k:].copy()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def measure(name, world, rank, local_rank, steps, warmup, dump_bytes=0):
     """Creates the resident lattice, warms up, times exactly `steps` steps; at N > 1 every rank then
-    repeats the same steps on the UNDIVIDED lattice alone on its GPU and compares its slab bit for bit."""
+    repeats the same steps on the UNDIVIDED lattice alone on its GPU and compares its slab bit for bit.
+    dump_bytes > 0: also returns what the timed run handed its caller -- the av_vels of its steps and the lattice
+    after its last step (this rank's slab at N > 1) -- within that many bytes (dump_sample) as "outputs"."""
     p, ob, data = make_workload(name)
     exchange, halo_note = choose_exchange(p, ob, world, rank, local_rank)
     lat = make_lattice(p, ob, world, rank, local_rank, exchange)
@@ -231,6 +250,10 @@ def measure(name, world, rank, local_rank, steps, warmup):
     t_run = time.perf_counter() - t0
     fence()
     dt = time.perf_counter() - t0
+    outputs = None
+    if dump_bytes > 0:
+        av_bytes = min(av.nbytes, dump_bytes // 16)
+        outputs = {"av_vels": dump_sample(av, av_bytes), "state": dump_sample(lat.read_state(), dump_bytes - av_bytes)}
     gpu_ms, lib_ms = lat.last_run_ms()
     if MULTI:
         t = torch.tensor([dt, gpu_ms], dtype=torch.float64, device="cuda")
@@ -334,7 +357,7 @@ def measure(name, world, rank, local_rank, steps, warmup):
                      "traffic_gbs": None if traffic is None else round(traffic / launch_s / 1e9, 1),
                      "traffic_frac_of_peak": None if traffic is None else round(traffic / launch_s / 1e9 / HBM_PEAK_GBS, 4)},
         "data": data, "params": p, "blocked": int(ob.sum()), "av_last": float(av[-1]), "finite": bool(np.isfinite(av).all()),
-        "halo": halo_note, "mass_drift": mass_drift, "bitexact": bitexact,
+        "halo": halo_note, "mass_drift": mass_drift, "bitexact": bitexact, "outputs": outputs,
     }
 
 
@@ -441,6 +464,11 @@ def main():
     ap.add_argument("--rehearse-multi", action="store_true",
                     help="one GPU only: run the N>1 code path (RCCL communicator, halo self-check, peer-to-peer "
                          "halos) on a ring of one rank; not a benchmark configuration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what each timed run computed as DIR/<name>.npy (float32, at most 64 MB in all): "
+                         "av_vels (per step) and state (the lattice after the last step, (ny, nx, 9)) of the headline "
+                         "workload, also_av_vels and also_state of the second; an output over its share is a fixed, "
+                         "seeded sample (av_vels: its last steps); at N > 1 each rank writes its slab as <name>_rank<r>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -464,10 +492,18 @@ def main():
             os.environ["LBM_FORCE_EXCHANGE"] = "1"
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
 
-    head = measure(args.workload, world, rank, local_rank, args.steps, args.warmup)
+    with_also = bool(args.also and args.also != args.workload)
+    dump = DUMP_BYTES // world if args.dump_outputs else 0           # this rank's share
+    head = measure(args.workload, world, rank, local_rank, args.steps, args.warmup, dump * 3 // 4 if with_also else dump)
     also = None
-    if args.also and args.also != args.workload:
-        also = measure(args.also, world, rank, local_rank, args.also_steps, min(args.warmup, 20))
+    if with_also:
+        also = measure(args.also, world, rank, local_rank, args.also_steps, min(args.warmup, 20), dump // 4)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = f"_rank{rank}" if world > 1 else ""
+        for prefix, res in (("", head), ("also_", also)):
+            for key, a in (res["outputs"].items() if res is not None else ()):
+                np.save(os.path.join(args.dump_outputs, f"{prefix}{key}{suffix}.npy"), a)
 
     cpu = None
     if rank == 0 and world == 1 and args.cpu_sample_steps > 0:

@@ -24,10 +24,24 @@ Two kinds of fixture, both DATA (inputs + expected outputs), never source:
    CLI binary as shipped (float, -Ofast; oracle/_ref/d2q9-bgk) on the small
    decks: the expected float-vs-double deviation our own checker must report.
 
+4. `ref_strict_decks.npz` / `ref_strict_random.npz`: what the strict build of
+   the reference (oracle/_ref/libd2q9_ref_strict.so) computes on the shipped
+   decks (from rest, a few hundred steps: av_vels per step, sha256 of the final
+   lattice, av_velocity, Reynolds number) and on small random lattices (inputs
+   and outputs in full).  They pin the float oracle bit for bit where the
+   reference is absent.
+
+5. `check_py_128x128.json`: the stdout and exit status of the reference's
+   unchanged check/check.py on the cases check_py_cases() writes (identical
+   files, the reference float binary's outputs, out of tolerance, wrong step
+   count, wrong coordinates), against the 128x128 golden files.
+
 Usage: python tests/golden/make_golden.py [--pressure 256x256 1024x1024] [--kat] [--ref-float]
+                                          [--ref-strict] [--check-py <reference>/check/check.py]
 """
 import argparse
 import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -121,11 +135,117 @@ def make_ref_float(decks) -> None:
         print(f"ref_float_{deck}: Reynolds {reyn}")
 
 
+# (deck, steps) and (nx, ny, seed) of the strict-reference fixtures; tests/test_oracle_vs_reference.py runs the same
+REF_STRICT_DECKS = (("128x128", 300), ("128x256", 300), ("256x256", 100), ("1024x1024", 8))
+REF_STRICT_RANDOM = ((2, 2, 1), (3, 5, 2), (17, 9, 3), (40, 31, 4), (128, 7, 5))
+RANDOM_STEPS = 5
+
+
+def random_param(nx, ny):
+    return O.OrcParam(nx, ny, RANDOM_STEPS, 7, 0.13, 0.02, 1.7)
+
+
+def random_case(nx, ny, seed):
+    """(param, obstacles, cells0) of a random lattice: dense random obstacles, perturbed populations."""
+    rng = np.random.default_rng(seed)
+    prm = random_param(nx, ny)
+    ob = (rng.random((ny, nx)) < 0.3).astype(np.int32)
+    ob[0, 0] = 0
+    a = (0.05 + 0.1 * rng.random((ny, nx, 9))).astype(np.float32)
+    return prm, ob, a
+
+
+def make_ref_strict() -> None:
+    ref = O.ReferenceStrict()
+    out = {}
+    for deck, nsteps in REF_STRICT_DECKS:
+        prm = O.read_params(os.path.join(ROOT, f"input_{deck}.params"))
+        rp = O.to_ref_param(prm)
+        ob = O.read_obstacles(os.path.join(ROOT, f"obstacles_{deck}.dat"), prm.nx, prm.ny)
+        a = O.Oracle().init_cells(prm, np.float32)
+        b = np.empty_like(a)
+        av = []
+        for _ in range(nsteps):
+            av.append(ref.timestep_new2(rp, a, b, ob))
+            a, b = b, a
+        out[f"{deck}.av_vels"] = np.array(av, dtype=np.float32)
+        out[f"{deck}.state_sha256"] = np.array(hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest())
+        out[f"{deck}.av_velocity"] = np.float32(ref.av_velocity(rp, a, ob))
+        out[f"{deck}.reynolds"] = np.float32(ref.calc_reynolds(rp, a, ob))
+        print(f"ref_strict {deck}: {nsteps} steps, av_vels[-1] = {av[-1]:.9e}")
+    np.savez_compressed(os.path.join(HERE, "ref_strict_decks.npz"), **out)
+    out = {}
+    for nx, ny, seed in REF_STRICT_RANDOM:
+        prm, ob, a = random_case(nx, ny, seed)
+        rp = O.to_ref_param(prm)
+        key = f"{nx}x{ny}_{seed}"
+        out[f"{key}.obstacles"], out[f"{key}.cells0"] = ob, a.copy()
+        b = np.empty_like(a)
+        av = []
+        for _ in range(RANDOM_STEPS):
+            av.append(ref.timestep_new2(rp, a, b, ob))
+            a, b = b, a
+        out[f"{key}.av_vels"], out[f"{key}.cells"] = np.array(av, dtype=np.float32), a
+    np.savez_compressed(os.path.join(HERE, "ref_strict_random.npz"), **out)
+    print(f"ref_strict random lattices: {len(REF_STRICT_RANDOM)}")
+
+
+def check_py_cases(outdir):
+    """{case: (av_vels file, final_state file)} written under `outdir`, each to be checked against
+    tests/golden/128x128.{av_vels,final_state}.dat."""
+    ga = os.path.join(HERE, "128x128.av_vels.dat")
+    gf = os.path.join(HERE, "128x128.final_state.dat")
+    with np.load(os.path.join(HERE, "ref_float_128x128.npz")) as z:
+        av, pr = z["av_vels"].astype(np.float64), z["pressure"].astype(np.float64).ravel()
+    fs_lines = open(gf).readlines()
+
+    def write(name, av, pr, lines=fs_lines):
+        pa, pf = os.path.join(outdir, f"{name}.av_vels.dat"), os.path.join(outdir, f"{name}.final_state.dat")
+        with open(pa, "w") as f:
+            f.write(O.format_av_vels(av))
+        with open(pf, "w") as f:
+            for ln, p in zip(lines, pr):
+                t = ln.split(" ")
+                t[5] = "%.12E" % p
+                f.write(" ".join(t))
+        return pa, pf
+
+    off_av, off_pr = av.copy(), pr.copy()
+    off_av[30000] *= 1.015
+    off_pr[777] *= 0.97
+    swapped = list(fs_lines)
+    swapped[5], swapped[6] = swapped[6], swapped[5]
+    return {
+        "identical": (ga, gf),
+        "float_binary": write("float_binary", av, pr),
+        "out_of_tolerance": write("out_of_tolerance", off_av, off_pr),
+        "fewer_steps": write("fewer_steps", av[:-1], pr),
+        "coordinates_differ": write("coordinates_differ", av, pr, swapped),
+    }
+
+
+def make_check_py(check_py) -> None:
+    ga = os.path.join(HERE, "128x128.av_vels.dat")
+    gf = os.path.join(HERE, "128x128.final_state.dat")
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for case, (sa, sf) in check_py_cases(td).items():
+            r = subprocess.run([sys.executable, check_py, "--ref-av-vels-file", ga, "--ref-final-state-file", gf,
+                                "--av-vels-file", sa, "--final-state-file", sf], capture_output=True, text=True)
+            out[case] = {"returncode": r.returncode, "stdout": r.stdout}
+            print(f"check.py {case}: exit {r.returncode}")
+    with open(os.path.join(HERE, "check_py_128x128.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--pressure", nargs="*", default=[])
     ap.add_argument("--kat", action="store_true")
     ap.add_argument("--ref-float", nargs="*", default=[])
+    ap.add_argument("--ref-strict", action="store_true")
+    ap.add_argument("--check-py", default=None, help="the reference's check/check.py")
     args = ap.parse_args()
     O.build()
     for d in args.pressure:
@@ -134,3 +254,7 @@ if __name__ == "__main__":
         make_kat()
     if args.ref_float:
         make_ref_float(args.ref_float)
+    if args.ref_strict:
+        make_ref_strict()
+    if args.check_py:
+        make_check_py(args.check_py)

@@ -1,12 +1,13 @@
-"""bench.py prints exactly one JSON line with the fields the driver reads."""
+"""bench.py prints exactly one JSON line with the fields the driver reads; --dump-outputs writes what it computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, deck_paths
 
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"}
@@ -60,3 +61,57 @@ def test_bench_multi_rank_path_rehearsal(gpu):
     assert "peer-to-peer" in d["config"]["halo"] or "RCCL" in d["config"]["halo"]
     assert "REHEARSAL" in d["config"]["decomposition"]
     assert d["results_bitexact"] is True and d["halo_verified"] is True and d["results_valid"] is True
+
+
+def test_dump_sample_is_bounded_and_fixed():
+    """bench.dump_sample, the sampler of --dump-outputs: an array within its share is written whole, a per-step series
+    over it keeps its last steps, a lattice over it becomes the same seeded sample in every run.  (bench imports torch,
+    which must not follow the HIP library into a process: the check runs in a child.)"""
+    code = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from bench import dump_sample
+small = np.arange(10, dtype=np.float32)
+assert dump_sample(small, 40) is small
+assert np.array_equal(dump_sample(small, 16), small[-4:])
+big = np.arange(6 * 5 * 9, dtype=np.float64).reshape(6, 5, 9)
+s1, s2 = dump_sample(big, 800), dump_sample(big.copy(), 800)
+assert s1.dtype == np.float64 and s1.shape == (100,) and s1.nbytes <= 800
+assert np.array_equal(s1, s2)                                  # the same positions every time
+assert np.all(np.diff(s1) > 0) and s1[-1] < big.size           # distinct elements, in index order
+assert dump_sample(big, big.nbytes) is big
+"""
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(gpu, tmp_path):
+    """--dump-outputs DIR: float32 .npy files under 64 MB in all, holding exactly what the timed runs computed --
+    av_vels of the --steps timed steps and the lattice after the last of them, for both workloads -- as the one-step
+    kernel computes it on a fresh lattice from the same inputs (warm-up + timed steps; av_vels to summation order)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from make_deck import obstacle_map
+    L = gpu
+    out = tmp_path / "outputs"
+    d = _run(["--steps", "40", "--warmup", "5", "--also", "256x256", "--also-steps", "16", "--cpu-sample-steps", "0",
+              "--dump-outputs", str(out)])
+    assert d["steps"] == 40 and d["results_bitexact"] is True
+    files = sorted(f.name for f in out.iterdir())
+    assert files == ["also_av_vels.npy", "also_state.npy", "av_vels.npy", "state.npy"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10**6
+    pf, of = deck_paths("1024x1024")
+    p = L.read_params(pf)
+    runs = ((p, L.read_obstacles(of, p), 5, 40, ""),
+            (L.Param(256, 256, 1000, 10, 0.1, 0.01, 1.85), obstacle_map(256, 256), 5, 16, "also_"))
+    for p, ob, warmup, steps, prefix in runs:
+        av, st = np.load(out / f"{prefix}av_vels.npy"), np.load(out / f"{prefix}state.npy")
+        assert av.dtype == np.float32 and st.dtype == np.float32
+        assert av.shape == (steps,) and st.shape == (p.ny, p.nx, 9)
+        with L.Lattice(p, ob, nslabs=1, devices=[0]) as plain:
+            plain.set_option("time_block", 1)
+            av_w = plain.run(warmup + steps)
+            ref = plain.read_state()
+        assert np.array_equal(st.view(np.uint32), ref.view(np.uint32)), prefix
+        assert np.allclose(av, av_w[warmup:], rtol=2e-6, atol=0), prefix

@@ -419,7 +419,7 @@ def test_derived_quantities_match_oracle_on_resident_state(gpu, O, oracle):
 
 def test_cli_end_to_end(gpu, tmp_path):
     """./d2q9-bgk <paramfile> <obstaclefile>: output files, stdout block, and the golden check
-    by our checker and -- where the reference checkout exists -- by its unchanged check.py."""
+    by our checker, in process and as the command the reference's check.py is run as."""
     import check_results as CR
     exe = os.path.join(ROOT, "d2q9-bgk")
     if not os.path.exists(exe):
@@ -442,12 +442,12 @@ def test_cli_end_to_end(gpu, tmp_path):
     # flag column: the untransposed obstacle flag, as in the golden file
     got = np.loadtxt(str(tmp_path / "final_state.dat"), usecols=[6])
     assert np.array_equal(got, np.loadtxt(gf, usecols=[6]))
-    ref_check = "/root/reference/check/check.py"
-    if os.path.exists(ref_check):
-        rr = subprocess.run(["python", ref_check, "--ref-av-vels-file", ga, "--ref-final-state-file", gf,
-                             "--av-vels-file", "av_vels.dat", "--final-state-file", "final_state.dat"],
-                            cwd=tmp_path, capture_output=True, text=True)
-        assert rr.returncode == 0 and "Both tests passed!" in rr.stdout
+    # the checker's command line (that of the reference's check.py, which ours reproduces report for report:
+    # tests/test_host_io.py::test_reference_check_py_accepts_what_ours_accepts)
+    rr = subprocess.run([sys.executable, os.path.join(ROOT, "check", "check_results.py"), "--ref-av-vels-file", ga,
+                         "--ref-final-state-file", gf, "--av-vels-file", "av_vels.dat", "--final-state-file", "final_state.dat"],
+                        cwd=tmp_path, capture_output=True, text=True)
+    assert rr.returncode == 0 and "Both tests passed!" in rr.stdout
 
 
 def test_full_size_synthetic_translation_invariance(gpu):
@@ -1487,7 +1487,7 @@ def test_largest_lattice_16384_squared(gpu):
     tools/big_lattice_check.py -- x-translation invariance bit for bit, the default kernel (lbm_wave<8>, two columns per lane)
     against the one-step kernel over 19 steps (two passes, a pair, a single step) bit for bit, mass drift."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "big_lattice_check.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, GRAFT_REPO_ROOT=ROOT))
+                       timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     out = r.stdout
     assert "translation invariance bit-exact: True av close: True" in out

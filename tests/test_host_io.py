@@ -142,15 +142,26 @@ def test_checker_end_to_end_on_files(tmp_path):
 
 
 def test_reference_check_py_accepts_what_ours_accepts(tmp_path):
-    """Where the reference checkout is present, its unchanged check.py agrees with ours."""
-    ref_check = "/root/reference/check/check.py"
-    if not os.path.exists(ref_check):
-        pytest.skip("reference checkout absent")
+    """The reference's unchanged check.py and ours agree: on every case of make_golden.check_py_cases (identical
+    files, the reference float binary's outputs, out of tolerance, wrong step count, wrong coordinates) our checker,
+    run with check.py's command line, prints check.py's report character for character and exits with its status
+    (tests/golden/check_py_128x128.json, recorded from check.py by make_golden.py --check-py)."""
+    import json
+    import sys
+    if GOLDEN not in sys.path:
+        sys.path.insert(0, GOLDEN)
+    from make_golden import check_py_cases
+    expected = json.load(open(os.path.join(GOLDEN, "check_py_128x128.json")))
+    cases = check_py_cases(str(tmp_path))
+    assert set(cases) == set(expected)
     ga = os.path.join(GOLDEN, "128x128.av_vels.dat")
     gf = os.path.join(GOLDEN, "128x128.final_state.dat")
-    r = subprocess.run(["python", ref_check, "--ref-av-vels-file", ga, "--ref-final-state-file", gf,
-                        "--av-vels-file", ga, "--final-state-file", gf], capture_output=True, text=True)
-    assert r.returncode == 0 and "Both tests passed!" in r.stdout
+    for case, (sa, sf) in cases.items():
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "check", "check_results.py"), "--ref-av-vels-file", ga,
+                            "--ref-final-state-file", gf, "--av-vels-file", sa, "--final-state-file", sf],
+                           capture_output=True, text=True)
+        assert (r.returncode, r.stdout) == (expected[case]["returncode"], expected[case]["stdout"]), case
+    assert expected["identical"]["returncode"] == 0 and expected["float_binary"]["returncode"] == 0
 
 
 @pytest.mark.skipif(not os.path.exists(EXE), reason="d2q9-bgk not built (make)")

@@ -1,12 +1,19 @@
-"""Pins the float oracle bit for bit: (a) against known-answer vectors produced by the
-reference's own timestep_new2 (tests/golden/kat_*.npz, made by make_golden.py from a
-strict-IEEE build of /root/reference/d2q9-bgk.c) -- runs everywhere; (b) against that
-reference build directly on the shipped decks and random states -- only where
-oracle/_ref/ exists (the build container, or shipped prebuilt to the GPU box)."""
+"""Pins the float oracle bit for bit to the reference's own timestep_new2: (a) known-answer
+vectors (tests/golden/kat_*.npz); (b) the shipped decks and random states
+(tests/golden/ref_strict_*.npz).  All were made by tests/golden/make_golden.py from a
+strict-IEEE build of the reference's d2q9-bgk.c (oracle/Makefile, oracle/_ref/)."""
+import hashlib
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from conftest import KATS, deck_paths, load_kat
+from conftest import GOLDEN, KATS, deck_paths, load_kat
+
+if GOLDEN not in sys.path:
+    sys.path.insert(0, GOLDEN)
+from make_golden import RANDOM_STEPS, REF_STRICT_DECKS, REF_STRICT_RANDOM, random_param  # noqa: E402
 
 
 def _kat_param(O, k):
@@ -44,48 +51,42 @@ def test_known_answers_exercise_every_branch():
         assert refused.any()
 
 
-needs_ref = pytest.mark.skipif(
-    not __import__("lbm_oracle").ReferenceStrict.available(),
-    reason="oracle/_ref/libd2q9_ref_strict.so not present (reference checkout absent)")
+def _strict_vectors(name):
+    with np.load(os.path.join(GOLDEN, name)) as z:
+        return {k: z[k] for k in z.files}
 
 
-@needs_ref
-@pytest.mark.parametrize("deck,nsteps", [("128x128", 300), ("128x256", 300), ("256x256", 100), ("1024x1024", 8)])
+@pytest.mark.parametrize("deck,nsteps", REF_STRICT_DECKS)
 def test_oracle_equals_reference_on_shipped_decks_bitwise(O, oracle, deck, nsteps):
-    ref = O.ReferenceStrict()
+    """From rest on the shipped decks: every step's av_vels, the final lattice (sha256 of its bytes), av_velocity and
+    the Reynolds number equal what the strict build of the reference computed (tests/golden/ref_strict_decks.npz)."""
+    k = _strict_vectors("ref_strict_decks.npz")
     pf, of = deck_paths(deck)
     prm = O.read_params(pf)
-    rp = O.to_ref_param(prm)
     ob = O.read_obstacles(of, prm.nx, prm.ny)
     a = oracle.init_cells(prm, np.float32)
-    ra = a.copy()
-    b, rb = np.empty_like(a), np.empty_like(a)
+    b = np.empty_like(a)
+    av = []
     for _ in range(nsteps):
-        av = oracle.timestep(prm, a, b, ob)
-        rav = ref.timestep_new2(rp, ra, rb, ob)
-        assert np.float32(av) == np.float32(rav)
-        a, b, ra, rb = b, a, rb, ra
-    assert np.array_equal(a.view(np.uint32), ra.view(np.uint32))
-    assert np.float32(oracle.av_velocity(prm, a, ob)) == np.float32(ref.av_velocity(rp, ra, ob))
-    assert np.float32(oracle.reynolds(prm, a, ob)) == np.float32(ref.calc_reynolds(rp, ra, ob))
+        av.append(oracle.timestep(prm, a, b, ob))
+        a, b = b, a
+    assert np.array_equal(np.array(av, np.float32).view(np.uint32), k[f"{deck}.av_vels"].view(np.uint32))
+    assert hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() == str(k[f"{deck}.state_sha256"])
+    assert np.float32(oracle.av_velocity(prm, a, ob)) == k[f"{deck}.av_velocity"]
+    assert np.float32(oracle.reynolds(prm, a, ob)) == k[f"{deck}.reynolds"]
 
 
-@needs_ref
-@pytest.mark.parametrize("nx,ny,seed", [(2, 2, 1), (3, 5, 2), (17, 9, 3), (40, 31, 4), (128, 7, 5)])
+@pytest.mark.parametrize("nx,ny,seed", REF_STRICT_RANDOM)
 def test_oracle_equals_reference_on_random_lattices_bitwise(O, oracle, nx, ny, seed):
-    """Ragged and minimum sizes (the peeled reference needs nx, ny >= 2), dense random obstacles."""
-    ref = O.ReferenceStrict()
-    rng = np.random.default_rng(seed)
-    prm = O.OrcParam(nx, ny, 5, 7, 0.13, 0.02, 1.7)
-    rp = O.to_ref_param(prm)
-    ob = (rng.random((ny, nx)) < 0.3).astype(np.int32)
-    ob[0, 0] = 0
-    a = (0.05 + 0.1 * rng.random((ny, nx, 9))).astype(np.float32)
-    ra = a.copy()
-    b, rb = np.empty_like(a), np.empty_like(a)
-    for _ in range(5):
-        av = oracle.timestep(prm, a, b, ob)
-        rav = ref.timestep_new2(rp, ra, rb, ob)
-        assert np.float32(av) == np.float32(rav)
-        a, b, ra, rb = b, a, rb, ra
-    assert np.array_equal(a.view(np.uint32), ra.view(np.uint32))
+    """Ragged and minimum sizes (the peeled reference needs nx, ny >= 2), dense random obstacles: every step's
+    av_vels and the final lattice equal the strict reference's (tests/golden/ref_strict_random.npz)."""
+    k = _strict_vectors("ref_strict_random.npz")
+    key = f"{nx}x{ny}_{seed}"
+    prm, ob, a = random_param(nx, ny), k[f"{key}.obstacles"], k[f"{key}.cells0"].copy()
+    b = np.empty_like(a)
+    av = []
+    for _ in range(RANDOM_STEPS):
+        av.append(oracle.timestep(prm, a, b, ob))
+        a, b = b, a
+    assert np.array_equal(np.array(av, np.float32).view(np.uint32), k[f"{key}.av_vels"].view(np.uint32))
+    assert np.array_equal(a.view(np.uint32), k[f"{key}.cells"].view(np.uint32))

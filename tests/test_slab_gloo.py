@@ -24,6 +24,30 @@ def _free_port():
     return port
 
 
+def _spawn(fn, world, *args, timeout=600):
+    """fn(rank, *args) in `world` fresh processes; fails if any of them fails (the others are then stopped).  The
+    standard library's spawn, not torch.multiprocessing: torch must not be imported into this process once a test has
+    loaded the HIP library here (see advanced_hpc_lbm_amd.load_library); the workers import it themselves."""
+    import multiprocessing
+    import time
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(rank,) + args) for rank in range(world)]
+    for p in procs:
+        p.start()
+    deadline = time.monotonic() + timeout
+    try:
+        while any(p.is_alive() for p in procs):
+            if any(p.exitcode not in (None, 0) for p in procs) or time.monotonic() > deadline:
+                break
+            time.sleep(0.05)
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+            p.join()
+    assert all(p.exitcode == 0 for p in procs), f"worker exit codes {[p.exitcode for p in procs]}"
+
+
 def _worker(rank, world, port, deck, nsteps, outdir):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -225,10 +249,8 @@ def test_k_row_ghost_zone_of_the_marching_kernels(tmp_path, O, oracle, world, de
     """K steps on a slab need K rows of each neighbour and nothing else (accelerate row included, wherever in the ghost
     zone its periodic image falls): what lbm_march reads in place across slabs (csrc/lbm_host_march.inc: launch_march_slabs; lbm_host_run.inc: run_p2p),
     rehearsed with the oracle over gloo, NaN everywhere the algorithm does not compute."""
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.start_processes(_worker_march, args=(world, port, deck_paths(deck), ngroups, K, str(tmp_path)),
-                       nprocs=world, join=True, start_method="spawn")
+    _spawn(_worker_march, world, world, port, deck_paths(deck), ngroups, K, str(tmp_path))
     pf, of = deck_paths(deck)
     prm = O.read_params(pf)
     ob = O.read_obstacles(of, prm.nx, prm.ny)
@@ -246,10 +268,8 @@ def test_k_row_ghost_zone_of_the_marching_kernels(tmp_path, O, oracle, world, de
 def test_two_step_halo_protocol_matches_single_domain_oracle(tmp_path, O, oracle, world, deck, npairs):
     """The nine-slot halo of the two-step kernel (HALO9_*): exchanged once per pair of steps, ring rows
     recomputed on both sides -- sufficient (all else is NaN) and bit-exact against the single domain."""
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.start_processes(_worker_pairs, args=(world, port, deck_paths(deck), npairs, str(tmp_path)),
-                       nprocs=world, join=True, start_method="spawn")
+    _spawn(_worker_pairs, world, world, port, deck_paths(deck), npairs, str(tmp_path))
     pf, of = deck_paths(deck)
     prm = O.read_params(pf)
     ob = O.read_obstacles(of, prm.nx, prm.ny)
@@ -269,10 +289,8 @@ def test_slab_protocol_matches_single_domain_oracle(tmp_path, O, oracle, world, 
     (d2q9-bgk.c:971-998), everything else in the halo rows is NaN.  This is the message content of the one-step halo
     kernels AND of the register tiles across slabs (csrc/lbm_regtile.hip.h, kRegSlab: the same three populations per column
     and step, as 16-byte granules stored into the neighbour's mailboxes) -- only the transport differs."""
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.start_processes(_worker, args=(world, port, deck_paths(deck), nsteps, str(tmp_path)),
-                       nprocs=world, join=True, start_method="spawn")
+    _spawn(_worker, world, world, port, deck_paths(deck), nsteps, str(tmp_path))
     pf, of = deck_paths(deck)
     prm = O.read_params(pf)
     ob = O.read_obstacles(of, prm.nx, prm.ny)

@@ -1,5 +1,5 @@
 import os, sys, time, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import advanced_hpc_lbm_amd as L
 n = 16384
 p = L.Param(n, n, 6, 10, 0.1, 0.01, 1.85)

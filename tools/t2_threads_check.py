@@ -1,8 +1,8 @@
 import os, sys, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import advanced_hpc_lbm_amd as L
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for deck, steps in (("128x128", 20000), ("256x256", 20000), ("1024x1024", 8000)):
     p = L.read_params(f"{ROOT}/input_{deck}.params"); ob = L.read_obstacles(f"{ROOT}/obstacles_{deck}.dat", p)
     for nt in (256, 512, 1024, 256, 512, 1024):
