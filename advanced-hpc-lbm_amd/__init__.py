@@ -37,7 +37,7 @@ EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_P2P = 0, 1, 2, 3
 ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
-    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_last_run_ms", "lbm_read_state",
+    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
 )
@@ -87,6 +87,7 @@ def load_library():
     lib.lbm_slab_rows.argtypes = [vp, C.c_int, ip, ip]
     lib.lbm_num_slabs.argtypes = [vp]
     lib.lbm_run.argtypes = [vp, C.c_int, vp]
+    lib.lbm_run_sampled.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
@@ -192,6 +193,27 @@ class Lattice:
         av = np.empty(max(nsteps, 0), dtype=np.float32)
         _check(self._lib.lbm_run(self._ctx, nsteps, av.ctypes.data))
         return av
+
+    def run_sampled(self, nsteps: int, every: int, out=None):
+        """lbm_run with snapshots after steps every, 2 every, ...: returns (av_vels[nsteps], fields) where fields is
+        (m, rows, nx, 4) float32 (u_x, u_y, |u|, pressure; m = nsteps // every; as final_state), a numpy array -- or
+        `out`, a contiguous float32 torch tensor of that shape on the context's GPU, filled there."""
+        m = nsteps // every if every > 0 else 0
+        shape = (m, self._local_rows(), self.params.nx, 4)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        if out is None:
+            fields = np.empty(shape, dtype=np.float32)
+            ptr = fields.ctypes.data if m > 0 else None
+        else:
+            import torch
+            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
+                    or not out.is_contiguous() or tuple(out.shape) != shape):
+                raise LbmError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
+            fields = out
+            ptr = out.data_ptr() if m > 0 else None
+            torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        _check(self._lib.lbm_run_sampled(self._ctx, nsteps, av.ctypes.data, every, ptr))
+        return av, fields
 
     def last_run_ms(self):
         g, w = C.c_double(0), C.c_double(0)

@@ -223,6 +223,7 @@ struct lbm_ctx {
   //   3 resident in registers (lbm_regtile) or fail   (2 was the LDS-resident engine, removed in round 3)
   int engine = 0;
   int engine_last = 0;         // what the last lbm_run used: 1 streaming, 3 resident in registers
+  int samples_in_kernel = 0;   // 1: the snapshots of the last lbm_run_sampled came from the register tiles
   // register-tile engine (engine 3): 64 x ty tiles, nw waves of r rows (ty == 0: none); bpc = blocks of this tiling a CU
   // takes by the occupancy query (0 = not asked yet, -1 = the query failed or the grid does not fit)
   struct { int ty = 0, r = 0, nw = 0, ntx = 0, nty = 0, bpc = 0; } tplan;
@@ -600,9 +601,18 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 
 #include "lbm_host_run.inc"
 
-extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
+
+// Will the next run try the register tiles first?  (info "engine_next")
+static bool regtile_is_next(const lbm_ctx* c) {
+  if (c->exchange != 0) return regtile_slabs_usable(c);
+  return c->slabs.size() == 1 && !c->resident_broken && (c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && (c->variant & 8) == 0;
+}
+
+// The step loop of lbm_run.  sn != nullptr (lbm_run_sampled): ONLY the register-tile engines are tried, with the snapshots
+// in the kernel; *sampled tells whether they ran -- if not, nothing has been stepped and the caller runs the steps in pieces.
+static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn, bool* sampled) {
+  if (sampled) *sampled = false;
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   const int nx = c->p.nx;
@@ -610,22 +620,23 @@ extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) {
   const float a2 = c->p.density * c->p.accel / 36.f;
   if (c->exchange != 0 && regtile_slabs_usable(c)) {
     bool done = false;
-    int rr = run_regtile_slabs(c, nsteps, av_vels, &done);
+    int rr = run_regtile_slabs(c, nsteps, av_vels, &done, sn);
     if (rr && c->engine == 0) {          // (as below: set-up failures of the automatic engine are not the caller's problem)
       (void)hipGetLastError();
       resident_give_up(c, lbm_last_error());
       rr = LBM_OK;
     }
     if (rr) return rr;
-    if (done) { c->engine_last = 3; return LBM_OK; }
+    if (done) { c->engine_last = 3; if (sampled) *sampled = true; return LBM_OK; }
   }
   if (c->exchange != 0 && c->engine >= 2) return fail(LBM_EINVAL, "register tiles across slabs cannot run here (%s) (engine = %d)",
                                                       c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
+  if (sn && c->exchange != 0) return LBM_OK;
   if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels); }
   if (c->exchange == 0 && c->slabs.size() == 1 && (c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && !c->resident_broken &&
       (c->variant & 8) == 0) {
     bool done = false;
-    int rr = run_regtile(c, nsteps, av_vels, &done);
+    int rr = run_regtile(c, nsteps, av_vels, &done, sn);
     if (rr && c->engine == 0) {
       // automatic engine: a set-up or launch failure of the resident kernel (LDS attribute refused, tiles not all
       // resident, allocation failed) is not the caller's problem -- the source lattice is untouched, the streaming kernels run
@@ -634,10 +645,11 @@ extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) {
       rr = LBM_OK;
     }
     if (rr) return rr;
-    if (done) { c->engine_last = 3; return LBM_OK; }
+    if (done) { c->engine_last = 3; if (sampled) *sampled = true; return LBM_OK; }
   }
   if (c->engine >= 2) return fail(LBM_EINVAL, "the resident kernel cannot run here (%s), or this lattice has no resident tiling (engine = %d)",
                                   c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
+  if (sn) return LBM_OK;
   c->engine_last = 1;
   const bool ex = c->exchange != 0;
   const bool pairs = t2_eligible(c) && nsteps >= 2;
@@ -785,6 +797,85 @@ extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) {
   return collect_sums(c, nsteps, av_vels, wall0);
 }
 
+extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) { return lbm_run_sampled(c, nsteps, av_vels, 0, nullptr); }
+
+extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every, float* fields_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every < 0) return fail(LBM_EINVAL, "every < 0");
+  const int m = every > 0 ? nsteps / every : 0;
+  if (m > 0 && !fields_out) return fail(LBM_EINVAL, "fields_out is NULL but %d snapshot(s) are due", m);
+  c->samples_in_kernel = 0;
+  if (m == 0) return run_steps(c, nsteps, av_vels, nullptr, nullptr);
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  const int nx = c->p.nx;
+  const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
+  long rows = 0;
+  for (auto& s : c->slabs) rows += s.nyl;
+  const long slot = rows * nx * 4;                          // floats per snapshot
+  if ((unsigned long long)m > (unsigned long long)(PTRDIFF_MAX / 4) / (unsigned long long)slot)
+    return fail(LBM_EINVAL, "%d snapshots of %ld floats do not fit the address space", m, slot);
+  bool on_dev = false;
+  {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, fields_out) == hipSuccess && attr.type == hipMemoryTypeDevice) {
+      on_dev = true;
+      for (auto& s : c->slabs)
+        if (s.dev != attr.device)
+          return fail(LBM_EINVAL, "fields_out is memory of device %d: device output needs every slab on that device (slab on %d)", attr.device, s.dev);
+    }
+    (void)hipGetLastError();      // (host memory unknown to HIP: an error the runtime remembers)
+  }
+  int rc;
+  if (regtile_is_next(c)) {
+    // ---- in the kernel: straight into device output, or into one staging buffer per slab copied out after the run
+    SnapPlan sp;
+    sp.every = every;
+    std::vector<DeviceTemp> stage(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (on_dev) { sp.at.push_back(fields_out + 4L * (s.row0 - base_row) * nx); sp.stride.push_back(slot); continue; }
+      HIPC(hipSetDevice(s.dev));
+      const size_t bytes = sizeof(float) * 4 * (size_t)m * (size_t)s.nyl * (size_t)nx;
+      if (hipMalloc(&stage[i].p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        stage[i].p = nullptr;
+        return fail(LBM_ENOMEM, "no room on device %d for %d snapshot(s) of slab %zu (%zu bytes)", s.dev, m, i, bytes);
+      }
+      sp.at.push_back((float*)stage[i].p); sp.stride.push_back((long)s.nyl * nx * 4);
+    }
+    bool sampled = false;
+    if ((rc = run_steps(c, nsteps, av_vels, &sp, &sampled))) return rc;
+    if (sampled) {
+      if (!on_dev)
+        for (size_t i = 0; i < c->slabs.size(); ++i) {
+          Slab& s = c->slabs[i];
+          HIPC(hipSetDevice(s.dev));
+          const size_t w = sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx;
+          HIPC(hipMemcpy2D(fields_out + 4L * (s.row0 - base_row) * nx, sizeof(float) * (size_t)slot, stage[i].p, w, w, (size_t)m,
+                           hipMemcpyDeviceToHost));
+        }
+      c->samples_in_kernel = 1;
+      return LBM_OK;
+    }
+    // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run)
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then lbm_final_state's derive into its slot
+  double gpu_ms = 0.0, wall_ms = 0.0;
+  int done = 0;
+  for (int j = 0; j <= m; ++j) {
+    const int n = (j < m) ? every : nsteps - done;
+    if (n == 0) break;
+    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr, nullptr, nullptr))) return rc;
+    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
+    done += n;
+    if (j < m && (rc = derive_all(c, fields_out + (size_t)j * (size_t)slot, nullptr, nullptr, on_dev))) return rc;
+  }
+  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  return LBM_OK;
+}
+
 extern "C" int lbm_last_run_ms(const lbm_ctx* c, double* gpu_ms, double* wall_ms) {
   if (!c) return fail(LBM_EINVAL, "ctx is NULL");
   if (gpu_ms) *gpu_ms = c->gpu_ms;
@@ -811,7 +902,8 @@ extern "C" int lbm_read_state(lbm_ctx* c, float* out) {
 }
 
 // Runs lbm_derive on every local slab; returns global speed sum and mass.
-static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass) {
+// out_on_device: out4 is device memory on the slabs' device (written in place, nothing copied).
+static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device) {
   const int nx = c->p.nx;
   const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
   double tot[2] = {0.0, 0.0};
@@ -820,8 +912,8 @@ static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass) 
     const long ncell = (long)s.nyl * nx;
     const int grid = cdiv(ncell, lbm::kBlock);
     DeviceTemp t;
-    if (out4) HIPC(hipMalloc(&t.p, sizeof(float) * 4 * ncell));
-    float* d_out = (float*)t.p;
+    if (out4 && !out_on_device) HIPC(hipMalloc(&t.p, sizeof(float) * 4 * ncell));
+    float* d_out = out_on_device ? out4 + 4L * (s.row0 - base_row) * nx : (float*)t.p;
     float* part = s.partials[0];  // idle between runs; capacity >= grid
     double* mpart = s.scratch_d;
     double* res = s.scratch_d + s.scratch_cap;  // 2 doubles: speed, mass
@@ -837,7 +929,7 @@ static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass) 
     double h[2];
     HIPC(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
     tot[0] += h[0]; tot[1] += h[1];
-    if (out4) {
+    if (out4 && !out_on_device) {
       HIPC(hipMemcpy(out4 + 4L * (s.row0 - base_row) * nx, d_out, sizeof(float) * 4 * ncell, hipMemcpyDeviceToHost));
     }
   }
@@ -849,7 +941,7 @@ static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass) 
 extern "C" int lbm_av_velocity(lbm_ctx* c, float* out) {
   if (!c || !out) return fail(LBM_EINVAL, "NULL argument");
   double sp = 0.0;
-  int rc = derive_all(c, nullptr, &sp, nullptr);
+  int rc = derive_all(c, nullptr, &sp, nullptr, false);
   if (rc) return rc;
   *out = (float)(sp / (double)c->tot_fluid);  // d2q9-bgk.c:2713
   return LBM_OK;
@@ -867,12 +959,12 @@ extern "C" int lbm_reynolds(lbm_ctx* c, float* out) {
 
 extern "C" int lbm_total_density(lbm_ctx* c, double* out) {
   if (!c || !out) return fail(LBM_EINVAL, "NULL argument");
-  return derive_all(c, nullptr, nullptr, out);
+  return derive_all(c, nullptr, nullptr, out, false);
 }
 
 extern "C" int lbm_final_state(lbm_ctx* c, float* out) {
   if (!c || !out) return fail(LBM_EINVAL, "NULL argument");
-  return derive_all(c, out, nullptr, nullptr);
+  return derive_all(c, out, nullptr, nullptr, false);
 }
 
 extern "C" int lbm_destroy(lbm_ctx* c) {
@@ -1020,10 +1112,9 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "fluid_cells")) { *value = (double)c->tot_fluid; return LBM_OK; }
   if (!strcmp(key, "engine")) { *value = c->engine; return LBM_OK; }
   if (!strcmp(key, "engine_last")) { *value = c->engine_last; return LBM_OK; }
+  if (!strcmp(key, "samples_in_kernel")) { *value = c->samples_in_kernel; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first
-    if (c->exchange != 0) *value = regtile_slabs_usable(c) ? 3 : 1;
-    else *value = (c->slabs.size() == 1 && !c->resident_broken)
-                 ? (((c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && (c->variant & 8) == 0) ? 3 : 1) : 1;
+    *value = regtile_is_next(c) ? 3 : 1;
     return LBM_OK;
   }
   if (!strcmp(key, "resident_fallback")) { *value = c->resident_broken ? 1 : 0; return LBM_OK; }   // 1: the resident kernel could not run here

@@ -2,6 +2,14 @@
 // and across slabs, the step loop with peer-to-peer halos.
 namespace {
 
+// Where a register-tile run puts its snapshots (lbm_run_sampled): per local slab, the slab's region of snapshot 0 on its
+// device and the floats from one snapshot to the next; every = 0: none.
+struct SnapPlan {
+  int every = 0;
+  std::vector<float*> at;
+  std::vector<long> stride;
+};
+
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the
 // peer-to-peer error word through pinned staging with async copies queued behind the step loop,
 // then ONE wait per slab (s.sc has joined the edge and exchange streams by then).
@@ -116,8 +124,17 @@ bool plan_regtile(lbm_ctx* c) {
 
 // The instantiation of lbm_regtile for a tiling and flavour (dbg: the LBM_RESIDENT_DEBUG timing experiments, R = 4 only).
 typedef void (*regtile_fn)(const lbm::RegTileArgs);
-regtile_fn regtile_kernel(int r, bool fast, int dbg, bool trace, bool async) {
-  constexpr int NW_ = lbm::kResDebugNoWait, NS_ = lbm::kResDebugNoSend, AS_ = lbm::kRegAsync;
+regtile_fn regtile_kernel(int r, bool fast, int dbg, bool trace, bool async, bool snap) {
+  constexpr int NW_ = lbm::kResDebugNoWait, NS_ = lbm::kResDebugNoSend, AS_ = lbm::kRegAsync, SN_ = lbm::kRegSnap;
+  if (snap) {                  // (lbm_run_sampled: the production flavours only)
+    if (async && r == 4) return fast ? lbm::lbm_regtile<4, SN_ | AS_ | 1> : lbm::lbm_regtile<4, SN_ | AS_>;
+    if (async && r == 2) return fast ? lbm::lbm_regtile<2, SN_ | AS_ | 1> : lbm::lbm_regtile<2, SN_ | AS_>;
+    switch (r) {
+      case 4: return fast ? lbm::lbm_regtile<4, SN_ | 1> : lbm::lbm_regtile<4, SN_>;
+      case 2: return fast ? lbm::lbm_regtile<2, SN_ | 1> : lbm::lbm_regtile<2, SN_>;
+      default: return fast ? lbm::lbm_regtile<1, SN_ | 1> : lbm::lbm_regtile<1, SN_>;
+    }
+  }
   if (async && dbg == 0 && !trace && r == 4) return fast ? lbm::lbm_regtile<4, AS_ | 1> : lbm::lbm_regtile<4, AS_>;
   if (async && dbg == 0 && !trace && r == 2) return fast ? lbm::lbm_regtile<2, AS_ | 1> : lbm::lbm_regtile<2, AS_>;
   if (async && trace && r == 4) return lbm::lbm_regtile<4, AS_ | 2048 | 1>;
@@ -161,7 +178,7 @@ int regtile_prepare(const lbm_ctx* c, const void* fn, int dev, int threads, unsi
   return n;
 }
 
-int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
+int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPlan* sn) {
   *done = false;
   Slab& s = c->slabs[0];
   HIPC(hipSetDevice(s.dev));
@@ -173,9 +190,10 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
   const char* dbg = getenv("LBM_RESIDENT_DEBUG");   // timing experiments (wrong results): see lbm_regtile.hip.h
   static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run, and a trace
-  const regtile_fn fn = regtile_kernel(t.r, fast, dbg ? atoi(dbg) : 0, want_stats && getenv("LBM_REGTILE_TRACE"), c->regtile_async != 0);
+  const regtile_fn fn0 = regtile_kernel(t.r, fast, dbg ? atoi(dbg) : 0, want_stats && getenv("LBM_REGTILE_TRACE"), c->regtile_async != 0, false);
+  const regtile_fn fn = sn ? regtile_kernel(t.r, fast, 0, false, c->regtile_async != 0, true) : fn0;
   if (c->tplan.bpc == 0) {                             // first run of this tiling: is every tile resident at once?
-    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), s.dev, (int)block.x, shm);
+    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn0), s.dev, (int)block.x, shm);
     c->tplan.bpc = (n < 0) ? -1 : n;
     if (n < 0) snprintf(c->resident_why, sizeof(c->resident_why), "%s", lbm_last_error());
     else if ((long)n * std::max(c->ncu, 1) < (long)ntiles) {
@@ -184,6 +202,10 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
     }
   }
   if (c->tplan.bpc < 0) return fail(LBM_EINVAL, "register tiling not usable: %s", c->resident_why);
+  if (sn) {                                             // the snapshot flavour must be resident at once too (else: the split run)
+    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), s.dev, (int)block.x, shm);
+    if (n < 0 || (long)n * std::max(c->ncu, 1) < (long)ntiles) { (void)hipGetLastError(); return LBM_OK; }
+  }
   if (!c->tmail) {
     // Uncached device memory where the device offers it: the granules are written once and read once, by another CU, and
     // every access is sc1 anyway -- without the L2 allocation a hand-off is shorter (1024x1024: 4.14 -> 3.48 us per step, found
@@ -230,6 +252,8 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
   a.mail = c->tmail; a.mail_bytes = (unsigned)mail_bytes; a.partials = c->rpartials; a.abort_word = c->rabort;
   a.fault = getenv("LBM_REGTILE_FAULT") ? 1 : 0;   // (tests: a tile that never starts)
   a.stats = nullptr;
+  a.snap = sn ? sn->at[0] : nullptr; a.snap_stride = sn ? sn->stride[0] : 0; a.every = sn ? sn->every : 0;
+  a.density = c->p.density;
   static unsigned long long* stats_buf = nullptr;
   constexpr size_t kStatsWords = 4 + 16 * 4 * 16 + 72;    // (+ the first wave that gave up: lbm_regtile.hip.h, await)
   if (want_stats) {
@@ -336,8 +360,17 @@ bool plan_regtile_slabs(lbm_ctx* c) {
 }
 
 typedef void (*regtile_slabs_fn)(const lbm::RegTileArgs*);
-regtile_slabs_fn regtile_slabs_kernel(int r, bool fast, bool async) {
-  constexpr int AS_ = lbm::kRegAsync, SL_ = lbm::kRegSlab;
+regtile_slabs_fn regtile_slabs_kernel(int r, bool fast, bool async, bool snap) {
+  constexpr int AS_ = lbm::kRegAsync, SN_ = lbm::kRegSnap, SL_ = lbm::kRegSlab;
+  if (snap) {
+    if (async && r == 4) return fast ? lbm::lbm_regtile_slabs<4, SL_ | SN_ | AS_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | SN_ | AS_>;
+    if (async && r == 2) return fast ? lbm::lbm_regtile_slabs<2, SL_ | SN_ | AS_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | SN_ | AS_>;
+    switch (r) {
+      case 4: return fast ? lbm::lbm_regtile_slabs<4, SL_ | SN_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | SN_>;
+      case 2: return fast ? lbm::lbm_regtile_slabs<2, SL_ | SN_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | SN_>;
+      default: return fast ? lbm::lbm_regtile_slabs<1, SL_ | SN_ | 1> : lbm::lbm_regtile_slabs<1, SL_ | SN_>;
+    }
+  }
   if (async && r == 4) return fast ? lbm::lbm_regtile_slabs<4, SL_ | AS_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | AS_>;
   if (async && r == 2) return fast ? lbm::lbm_regtile_slabs<2, SL_ | AS_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | AS_>;
   switch (r) {
@@ -393,14 +426,15 @@ bool regtile_slabs_usable(const lbm_ctx* c) {
   return true;
 }
 
-int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
+int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPlan* sn) {
   *done = false;
   const auto& t = c->splan;
   const int ns = (int)c->slabs.size(), ntiles = t.ntx * t.nty;
   const bool fast = (c->variant & lbm::kFastMath) != 0;
   const dim3 block(64 * t.nw);
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const regtile_slabs_fn fn = regtile_slabs_kernel(t.r, fast, c->regtile_async != 0);
+  const regtile_slabs_fn fn0 = regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, false);
+  const regtile_slabs_fn fn = sn ? regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, true) : fn0;
   int rc;
   // device groups: the local slabs in the order of their devices' first appearance
   std::vector<int> order, gstart;          // order[k] = slab index; gstart[g] = first k of group g (+ end)
@@ -419,7 +453,7 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
     for (int g = 0; g < ngroups; ++g) {
       Slab& l = c->slabs[order[gstart[g]]];
       HIPC(hipSetDevice(l.dev));
-      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), l.dev, (int)block.x, shm);
+      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn0), l.dev, (int)block.x, shm);
       if (n < 0) { c->splan.bpc = -1; snprintf(c->resident_why, sizeof(c->resident_why), "%s", lbm_last_error()); break; }
       worst = std::min(worst, n); most = std::max(most, gstart[g + 1] - gstart[g]);
     }
@@ -432,6 +466,13 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
     }
   }
   if (c->splan.bpc < 0) return fail(LBM_EINVAL, "register tiling across slabs not usable: %s", c->resident_why);
+  if (sn)                                              // the snapshot flavour must be resident at once too (else: the split run)
+    for (int g = 0; g < ngroups; ++g) {
+      Slab& l = c->slabs[order[gstart[g]]];
+      HIPC(hipSetDevice(l.dev));
+      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), l.dev, (int)block.x, shm);
+      if (n < 0 || (long)n * std::max(c->ncu, 1) < (long)ntiles * (gstart[g + 1] - gstart[g])) { (void)hipGetLastError(); return LBM_OK; }
+    }
   // peer access between the devices of neighbouring slabs (one process; asked once)
   if (!c->rank_mode && !c->splan_peers)
     for (int i = 0; i < ns; ++i)
@@ -496,6 +537,8 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done) {
       a.partials = s.rpartials; a.abort_word = c->slabs[order[gstart[g]]].rabort;
       a.fault = (getenv("LBM_REGTILE_FAULT") && i == 0) ? 1 : 0;
       a.stats = nullptr;
+      a.snap = sn ? sn->at[i] : nullptr; a.snap_stride = sn ? sn->stride[i] : 0; a.every = sn ? sn->every : 0;
+      a.density = c->p.density;
       if (c->rank_mode && c->nranks > 1) {
         a.mail_s = s.tmail_nb[0]; a.mail_n = s.tmail_nb[1];
         a.mail_bytes_s = (unsigned)s.tmail_nb_bytes[0]; a.mail_bytes_n = (unsigned)s.tmail_nb_bytes[1];

@@ -1066,6 +1066,26 @@ __global__ void lbm_pack_blocked(const int* obst, uint8_t* blocked, int pitch, i
   blocked[y * pitch + x] = obst[c] ? 1 : 0;
 }
 
+// Derived fields of one cell (write_values(), d2q9-bgk.c:2935-2976): {u_x, u_y, |u|, pressure}; rho = the cell's density.
+// Shared by lbm_derive and the register tiles' snapshots (lbm_regtile.hip.h), which must agree bit for bit: contraction is
+// off and the one product-sum the compiler used to fuse is written as the fma it was, IEEE division and sqrtf whatever
+// kernel_variant says.
+__device__ __forceinline__ f4a derive_cell(const float (&f)[9], bool blocked, float density, float& rho) {
+#pragma clang fp contract(off)
+  rho = 0.f;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) rho += f[k];
+  f4a v; v.x = 0.f; v.y = 0.f; v.z = 0.f; v.w = density * (1.f / 3.f);
+  if (!blocked) {
+    const float ux = (f[1] + f[5] + f[8] - (f[3] + f[6] + f[7])) / rho;
+    const float uy = (f[2] + f[5] + f[6] - (f[4] + f[7] + f[8])) / rho;
+    v.x = ux; v.y = uy;
+    v.z = sqrtf(__builtin_fmaf(ux, ux, uy * uy));
+    v.w = rho * (1.f / 3.f);
+  }
+  return v;
+}
+
 // Derived fields of write_values() (d2q9-bgk.c:2935-2976) and the speed sum of
 // av_velocity() (d2q9-bgk.c:2665-2714) in one pass.  out4 may be nullptr.
 __global__ __launch_bounds__(kBlock) void lbm_derive(const float* lat, long plane, int pitch, int nx,
@@ -1082,22 +1102,11 @@ __global__ __launch_bounds__(kBlock) void lbm_derive(const float* lat, long plan
     float f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
-    float rho = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) rho += f[k];
+    float rho;
+    const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
     mass = (double)rho;
-    float ux = 0.f, uy = 0.f, u = 0.f, pr = density * (1.f / 3.f);
-    if (!blocked[o]) {
-      ux = (f[1] + f[5] + f[8] - (f[3] + f[6] + f[7])) / rho;
-      uy = (f[2] + f[5] + f[6] - (f[4] + f[7] + f[8])) / rho;
-      u = sqrtf(ux * ux + uy * uy);
-      pr = rho * (1.f / 3.f);
-      sp = u;
-    }
-    if (out4 != nullptr) {
-      f4a v; v.x = ux; v.y = uy; v.z = u; v.w = pr;
-      *reinterpret_cast<f4a*>(out4 + 4 * c) = v;
-    }
+    sp = v.z;      // (0 for a blocked cell)
+    if (out4 != nullptr) *reinterpret_cast<f4a*>(out4 + 4 * c) = v;
   }
   const float bs = block_sum<float>(sp, red_f);
   const double bm = block_sum<double>(mass, red_d);

@@ -53,6 +53,8 @@ constexpr int kResDebugNoWait = 64, kResDebugNoSend = 128;
 constexpr int kRegAsync = 4096;   // lbm_regtile: mail loads / stores of the loop as inline asm with counted s_waitcnt vmcnt(N)
 constexpr int kRegSlab = 8192;    // lbm_regtile: the lattice is a slab with neighbours -- the tile rows below its first and above its
                                   // last belong to OTHER slabs (same tiling), whose mailboxes live in their own mail areas
+constexpr int kRegSnap = 16384;   // lbm_regtile: snapshots during the run (lbm_run_sampled).  A flavour of its own, not a runtime flag:
+                                  // the count-down and the store cost the unsampled loop ~2 % (1024^2, 3.09 against 3.02 us per step)
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
 // Per-step sums of a whole-run launch: partials[step][tile] -> sums[step] (double, fixed order), one wave per step; also
@@ -97,10 +99,15 @@ struct RegTileArgs {
   void* mail_s; void* mail_n;
   unsigned mail_bytes_s, mail_bytes_n;
   int nty_s, nty_n;
+  // ---- snapshots (lbm_run_sampled): after steps every, 2 every, ... the derived fields of every cell (derive_cell, from the
+  // post-collision populations, before the next step's accelerate) go to snap + j snap_stride + 4 (row nx + column), rows
+  // counted in this lattice / slab (flavour kRegSnap only; every = 0: none)
+  float* snap; long snap_stride;
+  int every; float density;
 };
 
 // LDS bytes of a block of nw waves with r rows per wave (see the kernel)
-__host__ __device__ constexpr int regtile_lds_bytes(int nw, int r) { return 4 * (nw * (2 * 6 * 64 + (r == 4 ? r * 3 * 64 : 0)) + 2 * 16 + 16); }
+__host__ __device__ constexpr int regtile_lds_bytes(int nw, int r) { return 4 * (nw * (2 * 6 * 64 + (r == 4 ? r * 3 * 64 : 0)) + 2 * 16 + 16 + 2 * 16); }
 
 // bytes of one mailbox (one tile, one parity): Sin[64], Nin[64], Win[ty+2], Ein[ty+2] granules of 16 bytes
 __host__ __device__ constexpr int regtile_box(int ty) { return 16 * (2 * 64 + 2 * (ty + 2)); }
@@ -127,6 +134,7 @@ template <int R, int MODE>
 __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool FAST = (MODE & kFastMath) != 0;
   constexpr bool SLAB = (MODE & kRegSlab) != 0;
+  constexpr bool SNAP = (MODE & kRegSnap) != 0;
   // timing experiments only (wrong results), LBM_RESIDENT_DEBUG: 1 = one pass over the inbox, no waiting; 2 = also no
   // stores to other tiles; 3 = also no inbox loads at all; 4 = like 1, the stores issued but dropped by an empty buffer
   // descriptor (what the instructions cost without their memory traffic); 5 = like 1, stores without sc1
@@ -139,11 +147,15 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   // LDS (dynamic, regtile_lds_bytes(nw, R)): edge rows between the waves of the tile [parity][wave][6][64]; the
   // populations no other row ever pulls from -- planes 0, 1, 3 of every row, [wave][R][3][64]: a row's own update is
   // the only reader and writer, so they wait in LDS instead of twelve registers the loop does not have; per-wave
-  // speed sums [parity][16]; abort word
+  // speed sums [parity][16]; abort word; the snapshot arguments (snap, snap_stride, every, density: read on sample steps
+  // only -- held in scalar registers across the loop they pushed the loop's scalar spills in front of the asm mail
+  // operations, inside their five-instruction hazard window)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int nw_ = (int)(blockDim.x >> 6);
   float* red = lds + nw_ * (2 * 6 * 64 + (R == 4 ? R * 3 * 64 : 0));
   uint32_t* lds_abort = reinterpret_cast<uint32_t*>(red + 32);
+  long long* lds_snap = reinterpret_cast<long long*>(red + 34);     // [1] snap_stride, [2] every | density << 32 (red + 36 .. 39)
+  long long* lds_snap_at = reinterpret_cast<long long*>(red + 48);  // [wave]: where its next snapshot goes (red + 48 .. 79)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
@@ -192,9 +204,25 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   const int rho0 = w * R;                                   // tile row of this wave's first row
   const int gx = bx * 64 + lane, gy0 = by * TY + rho0;
   if (tid == 0) *lds_abort = 0u;
+  if constexpr (SNAP) {
+    if (tid == 0) { lds_snap[1] = a.snap_stride; lds_snap[2] = (long long)(unsigned)a.every | ((long long)__float_as_uint(a.density) << 32); }
+    if (lane == 0) lds_snap_at[w] = (long long)a.snap;
+  }
   // planes 0, 1, 3 of row r: in LDS where the registers are short (four rows per wave), in f otherwise
   constexpr bool OWN_LDS = (R == 4);
   float* own = lds + nw * (2 * 6 * 64) + w * (R * 3 * 64) + lane;   // own[(r * 3 + j) * 64]: plane {0,1,3}[j] of row r
+  // snapshot of a row: one 16-byte nontemporal store per lane, 1 KB contiguous per wave-row (p = the row after collide_cell)
+  auto snap_row = [&](int r, const float (&p)[9], bool b) {
+    float rho;
+    const f4a v = derive_cell(p, b, __uint_as_float((unsigned)(lds_snap[2] >> 32)), rho);
+    float* at = reinterpret_cast<float*>(lds_snap_at[w]);
+    __builtin_nontemporal_store(v, reinterpret_cast<f4a*>(at + 4 * ((long)(gy0 + r) * a.nx + gx)));
+  };
+  // after a sample step: the wave's next snapshot, and the steps to it
+  auto snap_next = [&]() {
+    if (lane == 0) lds_snap_at[w] += lds_snap[1] * (long long)sizeof(float);
+    return __builtin_amdgcn_readfirstlane((int)(unsigned)lds_snap[2]);
+  };
 
   // east / west mail: lane 63 stores its row into the west inbox of the tile to the east, lane 0 into the east inbox of
   // the tile to the west (inbox row index = tile row + 1); lanes 0,1,2 fetch rows rho, rho-1, rho+1 of this tile's west
@@ -471,9 +499,11 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         afetch(std::integral_constant<int, UP ? 0 : R - 1>{}, pb0, slot[0]);
         if constexpr (D > 1) afetch(std::integral_constant<int, UP ? 1 : R - 2>{}, pb0, slot[1]);
       }
+      int snap_left = a.every;                       // (SNAP) steps to the next snapshot (never 0 again when every = 0)
       for (int s = 1; s <= a.nsteps; ++s) {
         int par = (s - 1) & 1;
         asm volatile("" : "+s"(par));
+        const bool sample = SNAP && --snap_left == 0;
         const unsigned pb = (unsigned)par * BOX, pbn = BOX - pb;
         const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
@@ -555,6 +585,12 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           p[7] = rt_east(m2e, hi[1]);
           p[8] = rt_west(m2w, hi[2]);
           sp += collide_cell<FAST, true>(p, blk[r], a.omega);
+          // snapshot (wave-uniform step): before the next step's accelerate, so that it is what lbm_derive sees after s steps.
+          // The store is issued after this row's fetch(i + D) and before the stores of its granules.  Stores count in vmcnt
+          // with the loads, in issue order (MI355X_MICROARCH.md, vmcnt): one more operation younger than a pending fetch makes
+          // the counted vmcnt(N) that retires it wait for MORE, never less -- the fixed counts stay safe, a sample step may
+          // wait a little longer.  Nothing the asm loads write is read here.
+          if (sample) snap_row(r, p, blk[r]);
           if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
           f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
           if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = p[0]; own[(r * 3 + 1) * 64] = p[1]; own[(r * 3 + 2) * 64] = p[3]; }
@@ -584,6 +620,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         stamp(s, 13);
         sp = wave_sum_dpp(sp);
         if (lane == 0) red[(s & 1) * 16 + w] = sp;
+        if (sample) snap_left = snap_next();
       }
       // nothing of the loop's mail is in flight beyond this point (the slots' last fetches are never used: retire them)
 #pragma unroll
@@ -623,9 +660,11 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   }
 
   bool aborted = false;
+  int snap_left = a.every;                         // (SNAP) steps to the next snapshot (never 0 again when every = 0)
   for (int s = 1; s <= a.nsteps; ++s) {
     int par = (s - 1) & 1;                         // parity of the state being pulled
     asm volatile("" : "+s"(par));                  // (keeps both parities' addresses from being hoisted into registers)
+    const bool sample = SNAP && --snap_left == 0;
     const unsigned pb = (unsigned)par * BOX, pbn = BOX - pb;
     const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
@@ -692,6 +731,9 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       p[7] = rt_east(m2e, hi[1]);
       p[8] = rt_west(m2w, hi[2]);
       sp += collide_cell<FAST, true>(p, blk[r], a.omega);
+      // snapshot (wave-uniform step), before the next step's accelerate.  Behind the fetch of the next row's mail: on a sample
+      // step the compiler's wait for that mail also waits for this store (no counted waits here to keep exact)
+      if (sample) snap_row(r, p, blk[r]);
       if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
       f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
       if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = p[0]; own[(r * 3 + 1) * 64] = p[1]; own[(r * 3 + 2) * 64] = p[3]; }
@@ -742,6 +784,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     stamp(s, 13);
     sp = wave_sum_dpp(sp);
     if (lane == 0) red[(s & 1) * 16 + w] = sp;
+    if (sample) snap_left = snap_next();
   }
   __syncthreads();
   if (a.stats != nullptr && lane == 0) { atomicAdd(a.stats, (unsigned long long)nmiss); atomicAdd(a.stats + 1, (unsigned long long)nspin); }

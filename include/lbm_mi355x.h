@@ -138,6 +138,18 @@ int lbm_num_slabs(const lbm_ctx* ctx);
  */
 int lbm_run(lbm_ctx* ctx, int nsteps, float* av_vels);
 
+/*
+ * lbm_run with snapshots of the derived fields taken during the run, after steps every, 2 every, ..., m every
+ * (m = nsteps / every; every = 0: none, exactly lbm_run; every < 0: LBM_EINVAL).  fields_out: float[m][rows][nx][4],
+ * snapshot j = what lbm_final_state would return after (j+1) every steps (same rows and rank-local convention), bit for
+ * bit; NULL only when m = 0.  av_vels, the lattice and everything after are bit-identical to lbm_run(ctx, nsteps, av_vels).
+ * fields_out may be host memory, or device memory of the device that holds every slab of the context (then nothing is
+ * copied to the host).  The register-tile engines write the snapshots from inside their kernels (info
+ * "samples_in_kernel" = 1); the other engines run the steps in pieces with a derive after each.  LBM_ENOMEM /
+ * LBM_EINVAL before anything runs when the device staging or the snapshots do not fit: the lattice is untouched.
+ */
+int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* fields_out);
+
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
 int lbm_last_run_ms(const lbm_ctx* ctx, double* gpu_ms, double* wall_ms);
@@ -192,7 +204,8 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * (1, 2, 4, 6, 8 steps per pass), "march_kernel", "march_rows", "wave_rows", "wave_cols" (1, 2), "regtile" (tiling),
  * "regtile_async" (0, 1), "regtile_tag" (test hook: the next mailbox tag), "kernel_variant" (bits: 1 fast rcp / sqrt, 2 / 4 nontemporal stores / loads, 8 the reference's
  * form of the speed sum, d2q9-bgk.c:1783-1811, 256 one-step kernel only), "vector_width", "t2_threads".
- * Info: "engine_last", "engine_next", "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
+ * tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */
