@@ -24,12 +24,13 @@ Two kinds of fixture, both DATA (inputs + expected outputs), never source:
    CLI binary as shipped (float, -Ofast; oracle/_ref/d2q9-bgk) on the small
    decks: the expected float-vs-double deviation our own checker must report.
 
-4. `ref_strict_decks.npz` / `ref_strict_random.npz`: what the strict build of
+4. `ref_strict_decks.npz` / `ref_strict_random.npz` / `ref_strict_params.npz`: what the strict build of
    the reference (oracle/_ref/libd2q9_ref_strict.so) computes on the shipped
    decks (from rest, a few hundred steps: av_vels per step, sha256 of the final
    lattice, av_velocity, Reynolds number) and on small random lattices (inputs
-   and outputs in full).  They pin the float oracle bit for bit where the
-   reference is absent.
+   and outputs in full; ref_strict_params: the same at every point of
+   PARAM_GRID, accelerate refusals included).  They pin the float oracle bit
+   for bit where the reference is absent.
 
 5. `check_py_128x128.json`: the stdout and exit status of the reference's
    unchanged check/check.py on the cases check_py_cases() writes (identical
@@ -37,7 +38,7 @@ Two kinds of fixture, both DATA (inputs + expected outputs), never source:
    count, wrong coordinates), against the 128x128 golden files.
 
 Usage: python tests/golden/make_golden.py [--pressure 256x256 1024x1024] [--kat] [--ref-float]
-                                          [--ref-strict] [--check-py <reference>/check/check.py]
+                                          [--ref-strict] [--ref-strict-params] [--check-py <reference>/check/check.py]
 """
 import argparse
 import hashlib
@@ -190,6 +191,95 @@ def make_ref_strict() -> None:
     print(f"ref_strict random lattices: {len(REF_STRICT_RANDOM)}")
 
 
+# Points of the parameter space that the suite visits, (density, accel, omega); tests/test_param_space.py runs them all.
+# "refusal": the accelerate guard (f3 - a1 > 0 && f6 - a2 > 0 && f7 - a2 > 0) refuses part of row ny-2 from step 3 on
+# when started from rest (calibrated on the float oracle: tests/test_param_space.py checks that it still does).
+PARAM_GRID = {
+    "control": (0.1, 0.01, 1.85),          # the shipped decks
+    "under_relaxed": (0.1, 0.005, 0.6),    # omega < 1
+    "omega_one": (0.1, 0.02, 1.0),         # 1 - omega is exactly 0
+    "stability_edge": (0.37, 0.03, 1.99),  # density well away from 0.1
+    "light_fluid": (0.02, 0.5, 1.5),       # small density, strong accel
+    "refusal": (0.1, 0.3, 1.85),           # guard refuses during the run
+}
+# (nx, ny, seed, state kind, steps) of ref_strict_params.npz, run at every point of PARAM_GRID
+REF_STRICT_PARAMS = ((17, 9, 11, "guard", 6), (33, 20, 12, "rest", 12), (21, 14, 13, "perturbed", 6))
+EQ_WEIGHTS = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
+
+
+def grid_param(point, nx, ny, steps=100):
+    density, accel, omega = PARAM_GRID[point]
+    return O.OrcParam(nx, ny, steps, 10, density, accel, omega)
+
+
+def accel_weights(density, accel):
+    """(a1, a2) of the accelerate phase in float, as the reference forms them (d2q9-bgk.c:230-231)."""
+    d, a = np.float32(density), np.float32(accel)
+    return d * a / np.float32(9), d * a / np.float32(36)
+
+
+def refused(density, accel, ob, cells):
+    """Mask over row ny-2: the fluid cells whose accelerate the guard refuses on the float lattice `cells`."""
+    a1, a2 = accel_weights(density, accel)
+    row = np.asarray(cells[-2], dtype=np.float32)
+    ok = (row[:, 3] - a1 > 0) & (row[:, 6] - a2 > 0) & (row[:, 7] - a2 > 0)
+    return (np.asarray(ob[-2]) == 0) & ~ok
+
+
+def param_state(point, nx, ny, seed, kind, blocked=0.1):
+    """(obstacles, cells0) at a point of PARAM_GRID.  kind:
+      "rest"      -- the equilibrium at rest (as the reference initialises), random obstacles;
+      "perturbed" -- every population within +-10 % of that equilibrium;
+      "guard"     -- perturbed, and row ny-2 holds every kind of cell the accelerate guard tells apart: refused by
+                     f3 - a1, by f6 - a2 and by f7 - a2 alone, f3 == a1 exactly (refused: 0 > 0 is false), f6 == a2
+                     exactly, blocked cells with populations thinner than a1 / a2, and cells that pass."""
+    density, accel, _ = PARAM_GRID[point]
+    rng = np.random.default_rng(seed)
+    ob = (rng.random((ny, nx)) < blocked).astype(np.int32)
+    eq = np.float32(density) * EQ_WEIGHTS
+    if kind == "rest":
+        return ob, np.broadcast_to(eq.astype(np.float32), (ny, nx, 9)).copy()
+    cells = (eq * (1.0 + 0.2 * (rng.random((ny, nx, 9)) - 0.5))).astype(np.float32)
+    if kind == "guard":
+        assert nx >= 10
+        a1, a2 = accel_weights(density, accel)
+        row = cells[ny - 2]
+        ob[ny - 2, :8] = 0
+        ob[ny - 2, 8:10] = 1
+        row[0, 3] = a1 * np.float32(0.5)      # f3 alone
+        row[1, 6] = a2 * np.float32(0.25)     # f6 alone
+        row[2, 7] = a2 * np.float32(0.9)      # f7 alone
+        row[3, 3] = a1                        # f3 == a1 exactly
+        row[4, 6] = a2                        # f6 == a2 exactly
+        row[5, 3] = np.nextafter(a1, np.float32(1))   # the smallest f3 that passes
+        row[8, 3], row[8, 6], row[8, 7] = a1 * np.float32(0.5), a2 * np.float32(0.5), np.float32(0)   # blocked, thin
+        row[9, 3], row[9, 6], row[9, 7] = np.float32(1e-9), np.float32(0), a2                        # blocked, thin
+        # cells 6 and 7 (and the random rest of the row) pass
+    return ob, cells
+
+
+def make_ref_strict_params() -> None:
+    """ref_strict_params.npz: the strict reference's per-step av_vels and final lattice at every PARAM_GRID point."""
+    ref = O.ReferenceStrict()
+    out = {}
+    for point in PARAM_GRID:
+        for nx, ny, seed, kind, nsteps in REF_STRICT_PARAMS:
+            prm = grid_param(point, nx, ny, nsteps)
+            rp = O.to_ref_param(prm)
+            ob, a = param_state(point, nx, ny, seed, kind)
+            b = np.empty_like(a)
+            av, nref = [], 0
+            for _ in range(nsteps):
+                nref += int(refused(prm.density, prm.accel, ob, a).sum())
+                av.append(ref.timestep_new2(rp, a, b, ob))
+                a, b = b, a
+            key = f"{point}.{nx}x{ny}_{seed}"
+            out[f"{key}.obstacles"], out[f"{key}.cells0"] = ob, param_state(point, nx, ny, seed, kind)[1]
+            out[f"{key}.av_vels"], out[f"{key}.cells"] = np.array(av, dtype=np.float32), a
+            print(f"ref_strict_params {key} ({kind}): {nsteps} steps, {nref} refusals, av_vels[-1] = {av[-1]:.9e}")
+    np.savez_compressed(os.path.join(HERE, "ref_strict_params.npz"), **out)
+
+
 def check_py_cases(outdir):
     """{case: (av_vels file, final_state file)} written under `outdir`, each to be checked against
     tests/golden/128x128.{av_vels,final_state}.dat."""
@@ -246,6 +336,7 @@ if __name__ == "__main__":
     ap.add_argument("--ref-float", nargs="*", default=[])
     ap.add_argument("--ref-strict", action="store_true")
     ap.add_argument("--check-py", default=None, help="the reference's check/check.py")
+    ap.add_argument("--ref-strict-params", action="store_true")
     args = ap.parse_args()
     O.build()
     for d in args.pressure:
@@ -258,3 +349,5 @@ if __name__ == "__main__":
         make_ref_strict()
     if args.check_py:
         make_check_py(args.check_py)
+    if args.ref_strict_params:
+        make_ref_strict_params()
