@@ -37,7 +37,8 @@ EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_P2P = 0, 1, 2, 3
 ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
-    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_last_run_ms", "lbm_read_state",
+    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_set_bodies", "lbm_run_forces",
+    "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
 )
@@ -88,6 +89,8 @@ def load_library():
     lib.lbm_num_slabs.argtypes = [vp]
     lib.lbm_run.argtypes = [vp, C.c_int, vp]
     lib.lbm_run_sampled.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    lib.lbm_set_bodies.argtypes = [vp, vp, C.c_int]
+    lib.lbm_run_forces.argtypes = [vp, C.c_int, vp, vp]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
@@ -214,6 +217,28 @@ class Lattice:
             torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
         _check(self._lib.lbm_run_sampled(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, fields
+
+    def set_bodies(self, body, nbodies: int):
+        """Labels blocked cells 1..nbodies (0: not counted) for run_forces: body is int[ny, nx] over the global lattice
+        (labels on fluid cells are ignored); nbodies = 0 clears the labelling."""
+        if nbodies == 0 and body is None:
+            _check(self._lib.lbm_set_bodies(self._ctx, None, 0))
+            self._nbodies = 0
+            return
+        b = np.ascontiguousarray(body, dtype=np.int32)
+        if b.size != self.params.nx * self.params.ny:
+            raise LbmError(f"body must hold {self.params.ny} x {self.params.nx} labels")
+        _check(self._lib.lbm_set_bodies(self._ctx, b.ctypes.data, nbodies))
+        self._nbodies = nbodies
+
+    def run_forces(self, nsteps: int):
+        """lbm_run that also returns the force of the fluid on every body at every step: (av_vels[nsteps],
+        forces[nsteps, nbodies, 2]) with (F_x, F_y) per body (definition: include/lbm_mi355x.h)."""
+        nb = getattr(self, "_nbodies", 0)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        forces = np.empty((max(nsteps, 0), nb, 2), dtype=np.float32)
+        _check(self._lib.lbm_run_forces(self._ctx, nsteps, av.ctypes.data, forces.ctypes.data if forces.size else None))
+        return av, forces
 
     def last_run_ms(self):
         g, w = C.c_double(0), C.c_double(0)

@@ -186,9 +186,25 @@ struct Slab {
   bool tmail_nb_ipc[2] = {false, false};
   uint32_t* rabort = nullptr;      // abort word of this slab's device group (owned by the group's first slab)
   hipEvent_t ev_rt = nullptr;      // "the group's launch is over" (recorded on the first slab's stream)
+  // bodies (lbm_set_bodies): the slab's blocked labelled cells with a fluid source, {column, local row, mask | label << 8};
+  // on the device as {offset in a plane, word} for lbm_body_forces; the register tiles' tables (lbm_regtile.hip.h, kRegForce)
+  // for tiles of fty rows (0: not built) and their per-step partials
+  std::vector<int4> fcells_host;
+  int2* fcells = nullptr;
+  int fcells_n = 0;
+  int* fslot = nullptr;
+  uint32_t* fwords = nullptr;
+  int fnslots = 0, fty = 0;
+  float* fpart = nullptr;
+  long fpart_cap = 0;              // floats
 };
 
 }  // namespace
+
+// An lbm_run_forces in progress (lbm_ctx::fplan): nb bodies; the run's forces are nval = 2 nb nsteps doubles at
+// sums + nsteps + 1 of every slab (behind the per-step sums and the spare word of run_regtile_slabs' "somebody gave up"),
+// reduced and fetched with them; in_kernel: the register tiles run their kRegForce flavour.
+struct ForcePlan { int nb; long nval; bool in_kernel; };
 
 struct lbm_ctx {
   lbm_param p;
@@ -224,6 +240,13 @@ struct lbm_ctx {
   int engine = 0;
   int engine_last = 0;         // what the last lbm_run used: 1 streaming, 3 resident in registers
   int samples_in_kernel = 0;   // 1: the snapshots of the last lbm_run_sampled came from the register tiles
+  int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
+  int nbodies = 0;             // lbm_set_bodies (0: none)
+  const ForcePlan* fplan = nullptr;   // the lbm_run_forces in progress (nullptr: a plain run)
+  // obstacle map of the local rows and one row either side (global rows keep_row0 .. keep_row0 + keep_rows - 1, taken
+  // modulo ny), for the bodies' direction masks
+  std::vector<uint8_t> obst_keep;
+  int keep_row0 = 0, keep_rows = 0;
   // register-tile engine (engine 3): 64 x ty tiles, nw waves of r rows (ty == 0: none); bpc = blocks of this tiling a CU
   // takes by the occupancy query (0 = not asked yet, -1 = the query failed or the grid does not fit)
   struct { int ty = 0, r = 0, nw = 0, ntx = 0, nty = 0, bpc = 0; } tplan;
@@ -618,7 +641,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
   const int nx = c->p.nx;
   const float a1 = c->p.density * c->p.accel / 9.f;   // d2q9-bgk.c:230-231
   const float a2 = c->p.density * c->p.accel / 36.f;
-  if (c->exchange != 0 && regtile_slabs_usable(c)) {
+  const bool tiles_ok = !c->fplan || c->fplan->in_kernel;   // (lbm_run_forces: the register tiles only in their force flavour)
+  if (c->exchange != 0 && tiles_ok && regtile_slabs_usable(c)) {
     bool done = false;
     int rr = run_regtile_slabs(c, nsteps, av_vels, &done, sn);
     if (rr && c->engine == 0) {          // (as below: set-up failures of the automatic engine are not the caller's problem)
@@ -629,11 +653,11 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
     if (rr) return rr;
     if (done) { c->engine_last = 3; if (sampled) *sampled = true; return LBM_OK; }
   }
-  if (c->exchange != 0 && c->engine >= 2) return fail(LBM_EINVAL, "register tiles across slabs cannot run here (%s) (engine = %d)",
+  if (c->exchange != 0 && c->engine >= 2 && !c->fplan) return fail(LBM_EINVAL, "register tiles across slabs cannot run here (%s) (engine = %d)",
                                                       c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
   if (sn && c->exchange != 0) return LBM_OK;
   if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels); }
-  if (c->exchange == 0 && c->slabs.size() == 1 && (c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && !c->resident_broken &&
+  if (tiles_ok && c->exchange == 0 && c->slabs.size() == 1 && (c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && !c->resident_broken &&
       (c->variant & 8) == 0) {
     bool done = false;
     int rr = run_regtile(c, nsteps, av_vels, &done, sn);
@@ -647,20 +671,21 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
     if (rr) return rr;
     if (done) { c->engine_last = 3; if (sampled) *sampled = true; return LBM_OK; }
   }
-  if (c->engine >= 2) return fail(LBM_EINVAL, "the resident kernel cannot run here (%s), or this lattice has no resident tiling (engine = %d)",
+  if (c->engine >= 2 && !c->fplan) return fail(LBM_EINVAL, "the resident kernel cannot run here (%s), or this lattice has no resident tiling (engine = %d)",
                                   c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
   if (sn) return LBM_OK;
   c->engine_last = 1;
   const bool ex = c->exchange != 0;
-  const bool pairs = t2_eligible(c) && nsteps >= 2;
+  const bool fo = c->fplan != nullptr;   // lbm_run_forces off the register tiles: the one-step kernel, lbm_body_forces behind each step
+  const bool pairs = !fo && t2_eligible(c) && nsteps >= 2;
   int rc;
 
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
 
-  const bool slabs_march = ex && march_slabs_on(c) && nsteps >= slab_K(c);
-  const bool bands = ex && !slabs_march && march_bands_on(c) && nsteps >= slab_K(c);   // RCCL transport: ghost bands
-  if ((slabs_march || nsteps >= c->time_block) && (rc = check_march_partials(c, slabs_march))) return rc;   // (before anything is queued)
+  const bool slabs_march = !fo && ex && march_slabs_on(c) && nsteps >= slab_K(c);
+  const bool bands = !fo && ex && !slabs_march && march_bands_on(c) && nsteps >= slab_K(c);   // RCCL transport: ghost bands
+  if (!fo && (slabs_march || nsteps >= c->time_block) && (rc = check_march_partials(c, slabs_march))) return rc;   // (before anything is queued)
   if (bands) {
     if ((rc = bands_setup(c, slab_K(c)))) return rc;
     for (auto& s : c->slabs) {
@@ -753,7 +778,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
       if ((rc = prime_halos((li & 1) ^ 1))) return rc;
     }
   } else
-  if (march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
+  if (!fo && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
     const int K = c->time_block, ngroups = nsteps / K;
     const bool wave = use_wave_kernel(c);
     for (int g = 0; g < ngroups; ++g, ++li, tt += K)
@@ -778,8 +803,10 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
     }
   }
   const int first_single = tt;
-  for (; tt < nsteps; ++tt, ++li)
+  for (; tt < nsteps; ++tt, ++li) {
     if ((rc = launch_single(c, li, tt, tt == nsteps - 1, tt > first_single, a1, a2))) return rc;
+    if (fo && (rc = launch_forces(c, tt, li & 1, nsteps))) return rc;
+  }
 
   // ---- epilogue: fold the last single step's partials, collect the per-step sums
   const int ql = (li - 1) & 1;
@@ -873,6 +900,106 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
     if (j < m && (rc = derive_all(c, fields_out + (size_t)j * (size_t)slot, nullptr, nullptr, on_dev))) return rc;
   }
   c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  return LBM_OK;
+}
+
+extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nbodies < 0 || nbodies > LBM_MAX_BODIES) return fail(LBM_EINVAL, "nbodies must be in [0, %d] (got %d)", LBM_MAX_BODIES, nbodies);
+  if (nbodies > 0 && !body) return fail(LBM_EINVAL, "body is NULL");
+  const int nx = c->p.nx, ny = c->p.ny;
+  // c_i of directions 1..8 (E N W S NE NW SW SE)
+  static const int cx[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1}, cy[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
+  std::vector<std::vector<int4>> lists(c->slabs.size());
+  for (size_t k = 0; k < c->slabs.size() && nbodies > 0; ++k) {
+    const Slab& s = c->slabs[k];
+    for (int y = 0; y < s.nyl; ++y) {
+      const int gy = s.row0 + y, ky = gy - c->keep_row0;       // (row of obst_keep)
+      for (int x = 0; x < nx; ++x) {
+        if (!c->obst_keep[(size_t)ky * nx + x]) continue;       // (labels on fluid cells are ignored)
+        const int lab = body[(long)gy * nx + x];
+        if (lab < 0 || lab > nbodies) return fail(LBM_EINVAL, "label %d of blocked cell (%d, %d) is outside [0, %d]", lab, x, gy, nbodies);
+        if (lab == 0) continue;
+        unsigned m = 0u;
+        for (int i = 1; i <= 8; ++i) {
+          const int sx = ((x - cx[i]) % nx + nx) % nx, sy = ky - cy[i];   // the source cell B - c_i (wraps in x; rows: kept)
+          if (!c->obst_keep[(size_t)sy * nx + sx]) m |= 1u << (i - 1);
+        }
+        if (m) lists[k].push_back(int4{x, y, (int)(m | ((unsigned)lab << 8)), 0});
+      }
+    }
+  }
+  (void)ny;
+  for (size_t k = 0; k < c->slabs.size(); ++k) {
+    Slab& s = c->slabs[k];
+    HIPC(hipSetDevice(s.dev));
+    if (s.fcells) HIPC(hipFree(s.fcells));
+    s.fcells = nullptr; s.fcells_n = 0; s.fty = 0;
+    s.fcells_host.swap(lists[k]);
+    if (s.fcells_host.empty()) continue;
+    std::vector<int2> dev(s.fcells_host.size());
+    for (size_t j = 0; j < dev.size(); ++j)
+      dev[j] = int2{s.fcells_host[j].y * s.pitch + s.fcells_host[j].x, s.fcells_host[j].z};
+    if (hipMalloc((void**)&s.fcells, sizeof(int2) * dev.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      s.fcells = nullptr; s.fcells_host.clear(); c->nbodies = 0;
+      return fail(LBM_ENOMEM, "no room on device %d for %zu body cells", s.dev, dev.size());
+    }
+    HIPC(hipMemcpy(s.fcells, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
+    s.fcells_n = (int)dev.size();
+  }
+  c->nbodies = nbodies;
+  return LBM_OK;
+}
+
+extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* forces) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (c->nbodies == 0) return fail(LBM_EINVAL, "no bodies are set (lbm_set_bodies)");
+  if (nsteps > 0 && !forces) return fail(LBM_EINVAL, "forces is NULL");
+  c->forces_in_kernel = 0;
+  if (nsteps == 0) return run_steps(c, 0, av_vels, nullptr, nullptr);
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  const int nb = c->nbodies;
+  const long nval = 2L * nb * nsteps;
+  if (nval + nsteps + 1 > (1L << 30)) return fail(LBM_EINVAL, "a forces run of %d steps is too long (split it)", nsteps);
+  // ---- everything that can fail for want of room is decided here, before anything is queued
+  int rc = LBM_OK;
+  for (auto& s : c->slabs)
+    if (ensure_sums(s, (int)(nsteps + 1 + nval))) { (void)hipGetLastError(); return fail(LBM_ENOMEM, "no room for the sums of %d steps and their forces", nsteps); }
+  bool in_kernel = regtile_is_next(c);
+  if (in_kernel) {
+    const int ty = c->exchange != 0 ? c->splan.ty : c->tplan.ty, ntx = c->exchange != 0 ? c->splan.ntx : c->tplan.ntx;
+    for (auto& s : c->slabs)
+      if ((rc = force_tables(c, s, ty, ntx, nsteps))) break;
+  }
+  if (c->rank_mode && c->slabs[0].comm != nullptr) {
+    // every rank takes the same path and fails together: [0] ranks short of room, [1] ranks that would not use the tiles
+    Slab& s = c->slabs[0];
+    double v[2] = {rc ? 1.0 : 0.0, in_kernel ? 0.0 : 1.0};
+    HIPC(hipSetDevice(s.dev));
+    HIPC(hipMemcpy(s.scratch_d, v, sizeof(v), hipMemcpyHostToDevice));
+    NCCLC(rccl::AllReduce(s.scratch_d, s.scratch_d, 2, rccl::kFloat64, rccl::kSum, s.comm, s.sc));
+    HIPC(hipStreamSynchronize(s.sc));
+    HIPC(hipMemcpy(v, s.scratch_d, sizeof(v), hipMemcpyDeviceToHost));
+    if (v[0] > 0.0) return rc ? rc : fail(LBM_ENOMEM, "another rank has no room for the force partials");
+    in_kernel = in_kernel && v[1] == 0.0;
+  } else if (rc) {
+    return rc;
+  }
+  const ForcePlan fp{nb, nval, in_kernel};
+  c->fplan = &fp;
+  bool tiles = false;
+  rc = run_steps(c, nsteps, av_vels, nullptr, &tiles);
+  c->fplan = nullptr;
+  if (rc) return rc;
+  c->forces_in_kernel = tiles ? 1 : 0;
+  // the local slabs' sums (a rank: everybody's, through the all-reduce that ended the run)
+  for (long k = 0; k < nval; ++k) {
+    double acc = 0.0;
+    for (auto& s : c->slabs) acc += s.sums_host[nsteps + 1 + k];
+    forces[k] = (float)acc;
+  }
   return LBM_OK;
 }
 
@@ -1113,6 +1240,7 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "engine")) { *value = c->engine; return LBM_OK; }
   if (!strcmp(key, "engine_last")) { *value = c->engine_last; return LBM_OK; }
   if (!strcmp(key, "samples_in_kernel")) { *value = c->samples_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first
     *value = regtile_is_next(c) ? 3 : 1;
     return LBM_OK;

@@ -14,7 +14,9 @@ struct SnapPlan {
 // peer-to-peer error word through pinned staging with async copies queued behind the step loop,
 // then ONE wait per slab (s.sc has joined the edge and exchange streams by then).
 int collect_sums(lbm_ctx* c, int nsteps, float* av_vels, std::chrono::steady_clock::time_point wall0, int extra = 0) {
-  // (extra: doubles behind the per-step sums that are reduced and fetched with them -- run_regtile_slabs' "somebody gave up")
+  // (extra: doubles behind the per-step sums that are reduced and fetched with them -- run_regtile_slabs' "somebody gave up";
+  // during lbm_run_forces that word and the forces behind it, on every path: every rank issues the same count)
+  if (c->fplan) extra = 1 + (int)c->fplan->nval;
   if (c->rank_mode && c->slabs[0].comm != nullptr) {   // (a ring of one rank has a communicator too: identity)
     Slab& s = c->slabs[0];
     NCCLC(rccl::AllReduce(s.sums, s.sums, (size_t)(nsteps + extra), rccl::kFloat64, rccl::kSum, s.comm, s.sc));
@@ -51,6 +53,59 @@ int collect_sums(lbm_ctx* c, int nsteps, float* av_vels, std::chrono::steady_clo
       for (size_t k = 0; k < ns; ++k) acc += c->slabs[k].sums_host[i];
       av_vels[i] = (float)(acc / nf);  // d2q9-bgk.c:1811
     }
+  }
+  return LBM_OK;
+}
+
+// ----------------------------------------------------------------- forces (lbm_run_forces)
+// The register tiles' tables of a slab for tiles of ty rows and ntx columns of tiles, and room for the partials of nsteps
+// steps: slots in the order of the tiles (only tiles that hold a counted cell have one).  LBM_ENOMEM: nothing queued.
+int force_tables(lbm_ctx* c, Slab& s, int ty, int ntx, int nsteps) {
+  HIPC(hipSetDevice(s.dev));
+  if (s.fty != ty) {
+    const int nty = s.nyl / ty, ntiles = ntx * nty;
+    std::vector<int> slot(ntiles, -1);
+    for (const int4& q : s.fcells_host) slot[(q.y / ty) * ntx + q.x / 64] = 0;
+    int n = 0;
+    for (int& v : slot) if (v == 0) v = n++;
+    std::vector<uint32_t> words((size_t)n * ty * 64, 0u);
+    for (const int4& q : s.fcells_host) words[((size_t)slot[(q.y / ty) * ntx + q.x / 64] * ty + q.y % ty) * 64 + q.x % 64] = (uint32_t)q.z;
+    if (s.fslot) HIPC(hipFree(s.fslot));
+    if (s.fwords) HIPC(hipFree(s.fwords));
+    s.fslot = nullptr; s.fwords = nullptr; s.fty = 0; s.fnslots = 0;
+    if (hipMalloc((void**)&s.fslot, sizeof(int) * ntiles) != hipSuccess ||
+        (n > 0 && hipMalloc((void**)&s.fwords, sizeof(uint32_t) * words.size()) != hipSuccess)) {
+      (void)hipGetLastError();
+      return fail(LBM_ENOMEM, "no room on device %d for the force tables (%d tiles)", s.dev, n);
+    }
+    HIPC(hipMemcpy(s.fslot, slot.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
+    if (n > 0) HIPC(hipMemcpy(s.fwords, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
+    s.fty = ty; s.fnslots = n;
+  }
+  const long need = (long)nsteps * s.fnslots * 8;
+  if (need > s.fpart_cap) {
+    if (s.fpart) HIPC(hipFree(s.fpart));
+    s.fpart = nullptr; s.fpart_cap = 0;
+    if (hipMalloc((void**)&s.fpart, sizeof(float) * (size_t)need) != hipSuccess) {
+      (void)hipGetLastError();
+      s.fpart = nullptr;
+      return fail(LBM_ENOMEM, "no room on device %d for the force partials (%d steps x %d tiles)", s.dev, nsteps, s.fnslots);
+    }
+    s.fpart_cap = need;
+  }
+  return LBM_OK;
+}
+
+// Every engine but the register tiles: the forces of step tt (0-based) from the lattice just stored, on the compute stream
+// behind the step (and behind its edge rows, where they run on a stream of their own); launch parity q.
+int launch_forces(lbm_ctx* c, int tt, int q, int nsteps) {
+  const ForcePlan& fp = *c->fplan;
+  for (auto& s : c->slabs) {
+    HIPC(hipSetDevice(s.dev));
+    if (c->exchange != 0 && c->exchange != LBM_EXCHANGE_P2P && split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[q], 0));
+    hipLaunchKernelGGL(lbm::lbm_body_forces, dim3(1), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.fcells, s.fcells_n,
+                       fp.nb, s.sums + nsteps + 1 + (long)tt * 2 * fp.nb);
+    HIPC(hipGetLastError());
   }
   return LBM_OK;
 }
@@ -124,6 +179,17 @@ bool plan_regtile(lbm_ctx* c) {
 
 // The instantiation of lbm_regtile for a tiling and flavour (dbg: the LBM_RESIDENT_DEBUG timing experiments, R = 4 only).
 typedef void (*regtile_fn)(const lbm::RegTileArgs);
+// The kRegForce instantiations of lbm_regtile (lbm_run_forces)
+regtile_fn regtile_force_kernel(int r, bool fast, bool async) {
+  constexpr int AS_ = lbm::kRegAsync, FO_ = lbm::kRegForce;
+  if (async && r == 4) return fast ? lbm::lbm_regtile<4, FO_ | AS_ | 1> : lbm::lbm_regtile<4, FO_ | AS_>;
+  if (async && r == 2) return fast ? lbm::lbm_regtile<2, FO_ | AS_ | 1> : lbm::lbm_regtile<2, FO_ | AS_>;
+  switch (r) {
+    case 4: return fast ? lbm::lbm_regtile<4, FO_ | 1> : lbm::lbm_regtile<4, FO_>;
+    case 2: return fast ? lbm::lbm_regtile<2, FO_ | 1> : lbm::lbm_regtile<2, FO_>;
+    default: return fast ? lbm::lbm_regtile<1, FO_ | 1> : lbm::lbm_regtile<1, FO_>;
+  }
+}
 regtile_fn regtile_kernel(int r, bool fast, int dbg, bool trace, bool async, bool snap) {
   constexpr int NW_ = lbm::kResDebugNoWait, NS_ = lbm::kResDebugNoSend, AS_ = lbm::kRegAsync, SN_ = lbm::kRegSnap;
   if (snap) {                  // (lbm_run_sampled: the production flavours only)
@@ -191,7 +257,10 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPl
   const char* dbg = getenv("LBM_RESIDENT_DEBUG");   // timing experiments (wrong results): see lbm_regtile.hip.h
   static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run, and a trace
   const regtile_fn fn0 = regtile_kernel(t.r, fast, dbg ? atoi(dbg) : 0, want_stats && getenv("LBM_REGTILE_TRACE"), c->regtile_async != 0, false);
-  const regtile_fn fn = sn ? regtile_kernel(t.r, fast, 0, false, c->regtile_async != 0, true) : fn0;
+  const bool fk = c->fplan && c->fplan->in_kernel;    // lbm_run_forces: the kRegForce flavour, with its larger LDS
+  const regtile_fn fn = fk ? regtile_force_kernel(t.r, fast, c->regtile_async != 0)
+                           : sn ? regtile_kernel(t.r, fast, 0, false, c->regtile_async != 0, true) : fn0;
+  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : shm;
   if (c->tplan.bpc == 0) {                             // first run of this tiling: is every tile resident at once?
     const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn0), s.dev, (int)block.x, shm);
     c->tplan.bpc = (n < 0) ? -1 : n;
@@ -202,8 +271,8 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPl
     }
   }
   if (c->tplan.bpc < 0) return fail(LBM_EINVAL, "register tiling not usable: %s", c->resident_why);
-  if (sn) {                                             // the snapshot flavour must be resident at once too (else: the split run)
-    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), s.dev, (int)block.x, shm);
+  if (sn || fk) {                                       // the snapshot / force flavour must be resident at once too (else: the split
+    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), s.dev, (int)block.x, shm_run);   // run / the force kernel)
     if (n < 0 || (long)n * std::max(c->ncu, 1) < (long)ntiles) { (void)hipGetLastError(); return LBM_OK; }
   }
   if (!c->tmail) {
@@ -254,6 +323,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPl
   a.stats = nullptr;
   a.snap = sn ? sn->at[0] : nullptr; a.snap_stride = sn ? sn->stride[0] : 0; a.every = sn ? sn->every : 0;
   a.density = c->p.density;
+  a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
   static unsigned long long* stats_buf = nullptr;
   constexpr size_t kStatsWords = 4 + 16 * 4 * 16 + 72;    // (+ the first wave that gave up: lbm_regtile.hip.h, await)
   if (want_stats) {
@@ -269,11 +339,16 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPl
   s.err_host[1] = 0;   // lbm_fold_steps stores the abort word here
   const auto wall0 = std::chrono::steady_clock::now();
   HIPC(hipEventRecord(s.ev_t0, s.sc));
-  hipLaunchKernelGGL(fn, grid, block, shm, s.sc, a);
+  hipLaunchKernelGGL(fn, grid, block, shm_run, s.sc, a);
   HIPC(hipGetLastError());
   hipLaunchKernelGGL(lbm::lbm_fold_steps, dim3(cdiv(nsteps, lbm::kBlock / 64)), dim3(lbm::kBlock), 0, s.sc,
                      c->rpartials, ntiles, nsteps, s.sums, c->rabort, s.err_host + 1);
   HIPC(hipGetLastError());
+  if (fk) {
+    hipLaunchKernelGGL(lbm::lbm_fold_forces, dim3(cdiv(c->fplan->nval, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
+                       s.fpart, s.fnslots, nsteps, c->fplan->nb, s.sums + nsteps + 1);
+    HIPC(hipGetLastError());
+  }
   HIPC(hipEventRecord(s.ev_t1, s.sc));
   rc = collect_sums(c, nsteps, av_vels, wall0);
   if (rc) return rc;
@@ -360,6 +435,16 @@ bool plan_regtile_slabs(lbm_ctx* c) {
 }
 
 typedef void (*regtile_slabs_fn)(const lbm::RegTileArgs*);
+regtile_slabs_fn regtile_slabs_force_kernel(int r, bool fast, bool async) {
+  constexpr int AS_ = lbm::kRegAsync, FO_ = lbm::kRegForce, SL_ = lbm::kRegSlab;
+  if (async && r == 4) return fast ? lbm::lbm_regtile_slabs<4, SL_ | FO_ | AS_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | FO_ | AS_>;
+  if (async && r == 2) return fast ? lbm::lbm_regtile_slabs<2, SL_ | FO_ | AS_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | FO_ | AS_>;
+  switch (r) {
+    case 4: return fast ? lbm::lbm_regtile_slabs<4, SL_ | FO_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | FO_>;
+    case 2: return fast ? lbm::lbm_regtile_slabs<2, SL_ | FO_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | FO_>;
+    default: return fast ? lbm::lbm_regtile_slabs<1, SL_ | FO_ | 1> : lbm::lbm_regtile_slabs<1, SL_ | FO_>;
+  }
+}
 regtile_slabs_fn regtile_slabs_kernel(int r, bool fast, bool async, bool snap) {
   constexpr int AS_ = lbm::kRegAsync, SN_ = lbm::kRegSnap, SL_ = lbm::kRegSlab;
   if (snap) {
@@ -434,7 +519,10 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
   const dim3 block(64 * t.nw);
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
   const regtile_slabs_fn fn0 = regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, false);
-  const regtile_slabs_fn fn = sn ? regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, true) : fn0;
+  const bool fk = c->fplan && c->fplan->in_kernel;
+  const regtile_slabs_fn fn = fk ? regtile_slabs_force_kernel(t.r, fast, c->regtile_async != 0)
+                                 : sn ? regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, true) : fn0;
+  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : shm;
   int rc;
   // device groups: the local slabs in the order of their devices' first appearance
   std::vector<int> order, gstart;          // order[k] = slab index; gstart[g] = first k of group g (+ end)
@@ -466,11 +554,11 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
     }
   }
   if (c->splan.bpc < 0) return fail(LBM_EINVAL, "register tiling across slabs not usable: %s", c->resident_why);
-  if (sn)                                              // the snapshot flavour must be resident at once too (else: the split run)
-    for (int g = 0; g < ngroups; ++g) {
+  if (sn || fk)                                        // the snapshot / force flavour must be resident at once too (else: the split
+    for (int g = 0; g < ngroups; ++g) {                 // run / the force kernel; lbm_run_forces has asked every rank already)
       Slab& l = c->slabs[order[gstart[g]]];
       HIPC(hipSetDevice(l.dev));
-      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), l.dev, (int)block.x, shm);
+      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), l.dev, (int)block.x, shm_run);
       if (n < 0 || (long)n * std::max(c->ncu, 1) < (long)ntiles * (gstart[g + 1] - gstart[g])) { (void)hipGetLastError(); return LBM_OK; }
     }
   // peer access between the devices of neighbouring slabs (one process; asked once)
@@ -539,6 +627,7 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
       a.stats = nullptr;
       a.snap = sn ? sn->at[i] : nullptr; a.snap_stride = sn ? sn->stride[i] : 0; a.every = sn ? sn->every : 0;
       a.density = c->p.density;
+      a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
       if (c->rank_mode && c->nranks > 1) {
         a.mail_s = s.tmail_nb[0]; a.mail_n = s.tmail_nb[1];
         a.mail_bytes_s = (unsigned)s.tmail_nb_bytes[0]; a.mail_bytes_n = (unsigned)s.tmail_nb_bytes[1];
@@ -561,7 +650,7 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
     Slab& l = c->slabs[order[gstart[g]]];
     HIPC(hipSetDevice(l.dev));
     for (int k = gstart[g] + 1; k < gstart[g + 1]; ++k) HIPC(hipStreamWaitEvent(l.sc, c->slabs[order[k]].ev_t0, 0));
-    hipLaunchKernelGGL(fn, dim3(ntiles, gstart[g + 1] - gstart[g]), block, shm, l.sc, c->rtable_dev + gstart[g]);
+    hipLaunchKernelGGL(fn, dim3(ntiles, gstart[g + 1] - gstart[g]), block, shm_run, l.sc, c->rtable_dev + gstart[g]);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(l.ev_rt, l.sc));
     for (int k = gstart[g]; k < gstart[g + 1]; ++k) {
@@ -570,6 +659,11 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
       hipLaunchKernelGGL(lbm::lbm_fold_steps, dim3(cdiv(nsteps, lbm::kBlock / 64)), dim3(lbm::kBlock), 0, s.sc,
                          s.rpartials, ntiles, nsteps, s.sums, l.rabort, s.err_host + 1);
       HIPC(hipGetLastError());
+      if (fk) {
+        hipLaunchKernelGGL(lbm::lbm_fold_forces, dim3(cdiv(c->fplan->nval, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
+                           s.fpart, s.fnslots, nsteps, c->fplan->nb, s.sums + nsteps + 1);
+        HIPC(hipGetLastError());
+      }
       HIPC(hipEventRecord(s.ev_t1, s.sc));
     }
   }
@@ -659,13 +753,14 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels) {
   if (!c->p2p_connected) return fail(LBM_EINVAL, "peer-to-peer halos are not connected (lbm_p2p_connect)");
   const int nx = c->p.nx;
   const float a1 = c->p.density * c->p.accel / 9.f, a2 = c->p.density * c->p.accel / 36.f;
-  const bool pairs = t2_eligible(c) && nsteps >= 2;
+  const bool pairs = !c->fplan && t2_eligible(c) && nsteps >= 2;   // (lbm_run_forces: one step per launch, forces behind each)
   const int ntx = nx / kT2X;
   const int push_grid = cdiv(nx, lbm::kBlock);
   int rc;
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
-  if (p2p_march_on(c) && nsteps >= slab_K(c) && (rc = check_march_partials(c, true))) return rc;   // (before anything is queued)
+  const bool march = !c->fplan && p2p_march_on(c) && nsteps >= slab_K(c);
+  if (march && (rc = check_march_partials(c, true))) return rc;   // (before anything is queued)
 
   auto push = [&](Slab& s, const float* lat, uint32_t seq, bool do_push) -> int {
     const int grid = do_push ? push_grid : 1;
@@ -696,7 +791,7 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels) {
   // ---- groups of K steps with lbm_march: the K ghost rows either side are read straight out of the neighbours'
   // lattices.  Launch group seq of a slab starts once both neighbours have raised seq-1 ("my launch seq-1 is over":
   // their rows are final, and they no longer read the lattice this launch overwrites) and raises seq when it is over.
-  if (p2p_march_on(c) && nsteps >= slab_K(c)) {
+  if (march) {
     const int K = slab_K(c);
     auto raise = [&](Slab& s, uint32_t q) -> int {
       const size_t f = 4 * s.halo_bytes;
@@ -806,6 +901,7 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels) {
       if ((rc = push(s, s.lat[c->cur ^ 1], seq, true))) return rc;   // the new edge rows, packed and pushed
     }
     c->cur ^= 1;
+    if (c->fplan && (rc = launch_forces(c, tt, q, nsteps))) return rc;
   }
   const int ql = (li - 1) & 1;
   for (auto& s : c->slabs) {

@@ -359,6 +359,10 @@ void slab_free(Slab& s) {
     if (s.ev_int[i]) (void)hipEventDestroy(s.ev_int[i]);
   }
   if (s.blocked) (void)hipFree(s.blocked);
+  if (s.fcells) (void)hipFree(s.fcells);
+  if (s.fslot) (void)hipFree(s.fslot);
+  if (s.fwords) (void)hipFree(s.fwords);
+  if (s.fpart) (void)hipFree(s.fpart);
   if (s.sums && !s.sums_direct) (void)hipFree(s.sums);
   if (s.sums_host) (void)hipHostFree(s.sums_host);
   if (s.err_host) (void)hipHostFree(s.err_host);
@@ -549,6 +553,16 @@ double wave_pick_cols(lbm_ctx* c, int rows, int* rows_per_chunk) {
 int finish_create(lbm_ctx* c, const int* obstacles, const float* cells) {
   const bool exchanging = c->exchange != 0;
   const int ay = c->p.ny - 2;  // the accelerate row of the global lattice (d2q9-bgk.c:240)
+  {
+    const int nx = c->p.nx, ny = c->p.ny;
+    c->keep_row0 = c->slabs.front().row0 - 1;
+    c->keep_rows = c->slabs.back().row0 + c->slabs.back().nyl + 1 - c->keep_row0;
+    c->obst_keep.resize((size_t)c->keep_rows * nx);
+    for (int i = 0; i < c->keep_rows; ++i) {
+      const long gy = ((long)(c->keep_row0 + i) % ny + ny) % ny;
+      for (int x = 0; x < nx; ++x) c->obst_keep[(size_t)i * nx + x] = obstacles[gy * nx + x] ? 1 : 0;
+    }
+  }
   for (auto& s : c->slabs) {
     s.accel_row = (ay >= s.row0 && ay < s.row0 + s.nyl) ? ay - s.row0 : -1;
     int rc = slab_alloc(c, s, exchanging);

@@ -1086,6 +1086,47 @@ __device__ __forceinline__ f4a derive_cell(const float (&f)[9], bool blocked, fl
   return v;
 }
 
+// Momentum a blocked cell takes from the fluid in one step (lbm_run_forces), halved: sum over the directions i of the mask
+// (bit i-1: the source cell B - c_i is fluid) of c_i f~_i, where f~_i, the population B pulled along i, sits in p[opp(i)]
+// once collide_cell has mirrored it -- and in plane opp(i) of the stored lattice.  Shared by the register tiles and
+// lbm_body_forces: both paths add the same eight terms in the same order.
+__device__ __forceinline__ void body_force_cell(const float (&p)[9], uint32_t m, float& fx, float& fy) {
+#pragma clang fp contract(off)
+  const float t1 = (m & 1u) ? p[3] : 0.f, t2 = (m & 2u) ? p[4] : 0.f, t3 = (m & 4u) ? p[1] : 0.f, t4 = (m & 8u) ? p[2] : 0.f;
+  const float t5 = (m & 16u) ? p[7] : 0.f, t6 = (m & 32u) ? p[8] : 0.f, t7 = (m & 64u) ? p[5] : 0.f, t8 = (m & 128u) ? p[6] : 0.f;
+  fx = ((t1 - t3) + (t5 - t7)) + (t8 - t6);
+  fy = ((t2 - t4) + (t5 - t7)) + (t6 - t8);
+}
+
+// One step's forces from the stored lattice (lbm_run_forces on every engine but the register tiles; one block):
+// cells[j] = {offset of a blocked labelled cell in the slab's planes, its word: mask | label << 8}.  out[2 b + k] = 2 x the
+// sum of component k over the cells of label b + 1, b < nb (in double, fixed order).
+__global__ __launch_bounds__(kBlock) void lbm_body_forces(const float* lat, long plane, const int2* cells, int n, int nb,
+                                                          double* out) {
+  __shared__ double red_d[kBlock / 64];
+  float fx[4] = {0.f, 0.f, 0.f, 0.f}, fy[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = threadIdx.x; j < n; j += kBlock) {
+    const int2 cw = cells[j];
+    float p[9];
+    p[0] = 0.f;
+#pragma unroll
+    for (int k = 1; k < 9; ++k) p[k] = lat[k * plane + cw.x];
+    float gx, gy;
+    body_force_cell(p, (uint32_t)cw.y, gx, gy);
+    const int b = ((uint32_t)cw.y >> 8) - 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (b == i) { fx[i] += gx; fy[i] += gy; }
+  }
+  for (int i = 0; i < nb; ++i) {
+    const double sx = block_sum<double>((double)fx[i], red_d);
+    __syncthreads();
+    const double sy = block_sum<double>((double)fy[i], red_d);
+    __syncthreads();
+    if (threadIdx.x == 0) { out[2 * i] = 2.0 * sx; out[2 * i + 1] = 2.0 * sy; }
+  }
+}
+
 // Derived fields of write_values() (d2q9-bgk.c:2935-2976) and the speed sum of
 // av_velocity() (d2q9-bgk.c:2665-2714) in one pass.  out4 may be nullptr.
 __global__ __launch_bounds__(kBlock) void lbm_derive(const float* lat, long plane, int pitch, int nx,

@@ -55,7 +55,21 @@ constexpr int kRegSlab = 8192;    // lbm_regtile: the lattice is a slab with nei
                                   // last belong to OTHER slabs (same tiling), whose mailboxes live in their own mail areas
 constexpr int kRegSnap = 16384;   // lbm_regtile: snapshots during the run (lbm_run_sampled).  A flavour of its own, not a runtime flag:
                                   // the count-down and the store cost the unsampled loop ~2 % (1024^2, 3.09 against 3.02 us per step)
+constexpr int kRegForce = 32768;  // lbm_regtile: drag and lift on labelled bodies during the run (lbm_run_forces).  A flavour of
+                                  // its own, like kRegSnap: lbm_run's kernels keep their registers and their loop
 typedef __attribute__((address_space(1))) unsigned int gu32;
+
+// Per-step forces of a whole-run launch with kRegForce: partials[step][slot][8] (8 = four labels x two components, the
+// halved sums of body_force_cell) -> out[step][2 nb] = 2 x the double sum over the slots, fixed order; one thread per value.
+__global__ __launch_bounds__(kBlock) void lbm_fold_forces(const float* partials, int nslots, int nsteps, int nb, double* out) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= (long)nsteps * 2 * nb) return;
+  const int step = (int)(i / (2 * nb)), k = (int)(i - (long)step * 2 * nb);
+  const float* p = partials + (long)step * nslots * 8 + k;
+  double s = 0.0;
+  for (int j = 0; j < nslots; ++j) s += (double)p[8 * j];
+  out[i] = 2.0 * s;
+}
 
 // Per-step sums of a whole-run launch: partials[step][tile] -> sums[step] (double, fixed order), one wave per step; also
 // hands the kernel's abort word to the host.
@@ -104,10 +118,16 @@ struct RegTileArgs {
   // counted in this lattice / slab (flavour kRegSnap only; every = 0: none)
   float* snap; long snap_stride;
   int every; float density;
+  // ---- forces (lbm_run_forces, flavour kRegForce only): fslot[tile] = the tile's slot, or -1 for a tile without a blocked
+  // labelled cell next to fluid; fwords[slot][ty][64] = per cell mask | label << 8 (0: not counted); the tile's halved sums
+  // of step s go to fpart[s - 1][slot][2 (label - 1) + component]
+  const int* fslot; const uint32_t* fwords; float* fpart; int nslots;
 };
 
 // LDS bytes of a block of nw waves with r rows per wave (see the kernel)
 __host__ __device__ constexpr int regtile_lds_bytes(int nw, int r) { return 4 * (nw * (2 * 6 * 64 + (r == 4 ? r * 3 * 64 : 0)) + 2 * 16 + 16 + 2 * 16); }
+// ... of the kRegForce flavour: behind those, the cells' force words [wave][R][64] and the waves' sums [parity][wave][8]
+__host__ __device__ constexpr int regtile_lds_bytes_force(int nw, int r) { return regtile_lds_bytes(nw, r) + 4 * nw * (r * 64 + 2 * 8); }
 
 // bytes of one mailbox (one tile, one parity): Sin[64], Nin[64], Win[ty+2], Ein[ty+2] granules of 16 bytes
 __host__ __device__ constexpr int regtile_box(int ty) { return 16 * (2 * 64 + 2 * (ty + 2)); }
@@ -135,6 +155,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool FAST = (MODE & kFastMath) != 0;
   constexpr bool SLAB = (MODE & kRegSlab) != 0;
   constexpr bool SNAP = (MODE & kRegSnap) != 0;
+  constexpr bool FORCE = (MODE & kRegForce) != 0;
   // timing experiments only (wrong results), LBM_RESIDENT_DEBUG: 1 = one pass over the inbox, no waiting; 2 = also no
   // stores to other tiles; 3 = also no inbox loads at all; 4 = like 1, the stores issued but dropped by an empty buffer
   // descriptor (what the instructions cost without their memory traffic); 5 = like 1, stores without sc1
@@ -208,6 +229,63 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     if (tid == 0) { lds_snap[1] = a.snap_stride; lds_snap[2] = (long long)(unsigned)a.every | ((long long)__float_as_uint(a.density) << 32); }
     if (lane == 0) lds_snap_at[w] = (long long)a.snap;
   }
+  // forces (FORCE): the tile's slot (-1: nothing to count here); frow = bit 4 r + b: row r of this wave holds a cell of
+  // label b + 1 -- wave-uniform, so that a row without one skips the work behind one scalar branch; the rows' words in
+  // LDS (fw), the wave's sums of a step in frc[parity][wave][8] (zeroed by the waves that have a labelled row)
+  uint32_t* fw = reinterpret_cast<uint32_t*>(lds + regtile_lds_bytes(nw_, R) / 4);
+  float* frc = reinterpret_cast<float*>(fw + nw_ * R * 64);
+  int fs = -1;
+  uint32_t frow = 0u;
+  if constexpr (FORCE) {
+    fs = __builtin_amdgcn_readfirstlane(a.fslot[tile]);
+    if (lane < 8) { frc[w * 8 + lane] = 0.f; frc[(nw_ + w) * 8 + lane] = 0.f; }
+    if (fs >= 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint32_t wd = a.fwords[((long)fs * TY + rho0 + r) * 64 + lane];
+        fw[(w * R + r) * 64 + lane] = wd;
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (__any((wd >> 8) == (uint32_t)(b + 1))) frow |= 1u << (4 * r + b);
+      }
+    }
+    frow = __builtin_amdgcn_readfirstlane(frow);
+  }
+  // a row's forces, after collide_cell (p: the pulled populations mirrored) -- lb = its labels (scalar): per label two DPP
+  // wave sums, added by lane 0 into the wave's slot of the step's parity
+  auto force_row = [&](int r, const float (&p)[9], uint32_t lb, int s) {
+    const uint32_t wd = fw[(w * R + r) * 64 + lane];
+    float gx, gy;
+    body_force_cell(p, wd & 255u, gx, gy);
+    const uint32_t lab = wd >> 8;
+    float* slot = frc + ((s & 1) * nw_ + w) * 8;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (lb & (1u << b)) {
+        const float vx = wave_sum_dpp(lab == (uint32_t)(b + 1) ? gx : 0.f);
+        const float vy = wave_sum_dpp(lab == (uint32_t)(b + 1) ? gy : 0.f);
+        if (lane == 0) { slot[2 * b] += vx; slot[2 * b + 1] += vy; }
+      }
+  };
+  // the tile's forces of a finished step (wave 0; parity q): lane = 16 k + wave, k = 0..3 -- components k and k + 4 summed
+  // over the waves by DPP row sums, lane 15 of row k stores them (two stores behind a lane mask, issued like the speed sum's)
+  auto force_out = [&](long step, int q) {
+    float u0 = 0.f, u1 = 0.f;
+    if ((lane & 15) < nw_) {
+      const float* src = frc + (q * nw_ + (lane & 15)) * 8;
+      u0 = src[lane >> 4]; u1 = src[4 + (lane >> 4)];
+    }
+#define LBM_ROW_ADD(v, ctrl) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, true))
+    LBM_ROW_ADD(u0, 0x111); LBM_ROW_ADD(u1, 0x111);
+    LBM_ROW_ADD(u0, 0x112); LBM_ROW_ADD(u1, 0x112);
+    LBM_ROW_ADD(u0, 0x114); LBM_ROW_ADD(u1, 0x114);
+    LBM_ROW_ADD(u0, 0x118); LBM_ROW_ADD(u1, 0x118);
+#undef LBM_ROW_ADD
+    if ((lane & 15) == 15) {
+      float* dst = a.fpart + (step * a.nslots + fs) * 8;
+      dst[lane >> 4] = u0; dst[4 + (lane >> 4)] = u1;
+    }
+  };
   // planes 0, 1, 3 of row r: in LDS where the registers are short (four rows per wave), in f otherwise
   constexpr bool OWN_LDS = (R == 4);
   float* own = lds + nw * (2 * 6 * 64) + w * (R * 3 * 64) + lane;   // own[(r * 3 + j) * 64]: plane {0,1,3}[j] of row r
@@ -513,7 +591,9 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           float v = (lane < nw) ? red[par * 16 + lane] : 0.f;    // the head of EVERY step, and the tile's barrier waits for its slowest wave)
           v = wave_sum_dpp(v);
           if (tid == 0) a.partials[(long)(s - 2) * nt + tile] = v;
+          if (FORCE && fs >= 0) force_out(s - 2, par);
         }
+        if (FORCE && frow != 0u && lane < 8) frc[((s & 1) * nw + w) * 8 + lane] = 0.f;
         const bool laststep = (s == a.nsteps), firststep = (s == 1);
         float sp = 0.f;
         float sv[3] = {0.f, 0.f, 0.f};               // going up: old planes 2,5,6 of the row just overwritten; going down: 4,7,8
@@ -591,6 +671,9 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           // the counted vmcnt(N) that retires it wait for MORE, never less -- the fixed counts stay safe, a sample step may
           // wait a little longer.  Nothing the asm loads write is read here.
           if (sample) snap_row(r, p, blk[r]);
+          // forces (a row with a labelled cell only): LDS and DPP work and lane 0's LDS add, no vector-memory operation --
+          // the counted vmcnt waits see exactly the operations they see without it
+          if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
           if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
           f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
           if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = p[0]; own[(r * 3 + 1) * 64] = p[1]; own[(r * 3 + 2) * 64] = p[3]; }
@@ -647,6 +730,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       float v = (lane < nw) ? red[(a.nsteps & 1) * 16 + lane] : 0.f;
       v = wave_sum(v);
       if (tid == 0) a.partials[(long)(a.nsteps - 1) * nt + tile] = v;
+      if (FORCE && fs >= 0) force_out(a.nsteps - 1, a.nsteps & 1);
     }
     return;
   }
@@ -674,7 +758,9 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       float v = (lane < nw) ? red[par * 16 + lane] : 0.f;   // (written with parity (s-1)&1 at the end of step s-1)
       v = wave_sum_dpp(v);
       if (tid == 0) a.partials[(long)(s - 2) * nt + tile] = v;
+      if (FORCE && fs >= 0) force_out(s - 2, par);
     }
+    if (FORCE && frow != 0u && lane < 8) frc[((s & 1) * nw + w) * 8 + lane] = 0.f;
     const bool laststep = (s == a.nsteps);
     float sp = 0.f;
 
@@ -734,6 +820,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       // snapshot (wave-uniform step), before the next step's accelerate.  Behind the fetch of the next row's mail: on a sample
       // step the compiler's wait for that mail also waits for this store (no counted waits here to keep exact)
       if (sample) snap_row(r, p, blk[r]);
+      if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
       if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
       f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
       if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = p[0]; own[(r * 3 + 1) * 64] = p[1]; own[(r * 3 + 2) * 64] = p[3]; }
@@ -806,6 +893,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     float v = (lane < nw) ? red[(a.nsteps & 1) * 16 + lane] : 0.f;
     v = wave_sum(v);
     if (tid == 0) a.partials[(long)(a.nsteps - 1) * nt + tile] = v;
+    if (FORCE && fs >= 0) force_out(a.nsteps - 1, a.nsteps & 1);
   }
 }
 

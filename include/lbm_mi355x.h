@@ -150,6 +150,35 @@ int lbm_run(lbm_ctx* ctx, int nsteps, float* av_vels);
  */
 int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* fields_out);
 
+/*
+ * Drag and lift on labelled bodies, step by step.
+ *
+ * Directions are the reference's: 1 E, 2 N, 3 W, 4 S, 5 NE, 6 NW, 7 SW, 8 SE. c_i is the lattice vector and opp(i)
+ * is the reverse direction. The lattice wraps in x and y. For body b and step t (t = 1..nsteps of the call):
+ *
+ *     F_b(t) = 2 * Σ_{B blocked, label(B) = b}  Σ_{i = 1..8 : cell B - c_i is fluid}  c_i * f~_i(B, t)
+ *
+ * f~_i(B, t) is the population that B pulled along direction i in step t, after that step's accelerate. It is also the
+ * value in plane opp(i) of B in the lattice stored after step t, so F can be computed from `lbm_read_state` alone.
+ * This is the force *on* the body: with the shipped decks' +x acceleration, the steady drag is positive.
+ */
+#define LBM_MAX_BODIES 4
+/* body: int[ny*nx] over the GLOBAL lattice (in both modes); 0 = not counted, 1..nbodies = the body a blocked cell
+   belongs to; labels on fluid cells are ignored.  Replaces any earlier labelling; nbodies = 0 clears it.
+   LBM_EINVAL (the earlier labelling kept) when nbodies is outside [0, LBM_MAX_BODIES], body is NULL with nbodies > 0, or
+   a blocked cell of this context's rows carries a label outside [0, nbodies]. */
+int lbm_set_bodies(lbm_ctx* ctx, const int* body, int nbodies);
+/* lbm_run that also writes forces[nsteps][nbodies][2] = (F_x, F_y) of each body at each step (definition above).
+   The lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels), and so is av_vels wherever
+   the same kernel runs (the register tiles; the one-step kernel).  Where lbm_run would take several steps per launch
+   (time_block > 1, two-step launches on slabs), the forces run takes one at a time and av_vels is the one-step kernel's:
+   equal to lbm_run's within float rounding of the per-step sum.  Rank
+   contexts: every rank gets the global forces (without RCCL: its own contribution), as with av_vels.  The register
+   tiles take the sums inside their kernels (info "forces_in_kernel" = 1); every other engine runs the one-step kernel
+   with a small force kernel behind each step (correct, not fast).  LBM_EINVAL with nothing queued and the lattice
+   untouched when no bodies are set or forces is NULL with nsteps > 0; LBM_ENOMEM likewise when the partials do not fit. */
+int lbm_run_forces(lbm_ctx* ctx, int nsteps, float* av_vels, float* forces);
+
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
 int lbm_last_run_ms(const lbm_ctx* ctx, double* gpu_ms, double* wall_ms);
@@ -205,7 +234,7 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "regtile_async" (0, 1), "regtile_tag" (test hook: the next mailbox tag), "kernel_variant" (bits: 1 fast rcp / sqrt, 2 / 4 nontemporal stores / loads, 8 the reference's
  * form of the speed sum, d2q9-bgk.c:1783-1811, 256 one-step kernel only), "vector_width", "t2_threads".
  * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
- * tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */

@@ -7,7 +7,8 @@ that retires them (marked `; retire v[a:b] ...` in the asm text) sees -- or dest
 (cdna_hip_programming.md 5.7, item 1).  This walks the ISA of every lbm_regtile<R, MODE | kRegAsync> instantiation from each
 asm `buffer_load_dwordx4` along every path (branches followed both ways, loops once round) until the retiring statement, and
 reports every instruction outside asm statements that touches the destination registers on the way; also scratch use and
-AGPR traffic.  Exit status 1 on any finding.
+AGPR traffic, and any asynchronous flavour the library selects (plain, kRegSnap, kRegForce; alone and across slabs) that is
+missing from the ISA.  Exit status 1 on any finding.
 
     python tools/audit_regtile_isa.py [file.s]      (default: compiles advanced-hpc-lbm_amd/csrc/lbm_api.hip -S for gfx950)
 """
@@ -112,7 +113,7 @@ def audit_kernel(name, body):
 def main():
     path = sys.argv[1] if len(sys.argv) > 1 else device_asm()
     lines = open(path).read().split("\n")
-    total, allf, kernels = 0, [], 0
+    total, allf, kernels, seen = 0, [], 0, set()
     i = 0
     while i < len(lines):
         m = re.match(r"^(_ZN3lbm(?:11lbm_regtile|17lbm_regtile_slabs)ILi(\d+)ELi(\d+)EEEv(?:NS_11RegTileArgsE|PKNS_11RegTileArgsE)):", lines[i])
@@ -127,11 +128,20 @@ def main():
             if scratch and not scratch[0].strip().endswith(" 0"):
                 f.append(f"{kname}: scratch in use: {scratch[0].strip()}")
             print(f"{kname}: {n} asm loads audited, {len(f)} finding(s)")
+            seen.add((int(m.group(2)), int(m.group(3))))
             total += n
             allf += f
             kernels += 1
             i = j
         i += 1
+    # the flavours the library selects must all be here: lbm_run's, the snapshots' (kRegSnap) and the forces' (kRegForce),
+    # alone and across slabs (kRegSlab), R = 2 and 4, with and without fast math
+    for flav, label in ((0, "plain"), (16384, "snapshot"), (32768, "force")):
+        for slab in (0, 8192):
+            for r in (2, 4):
+                for fast in (0, 1):
+                    if (r, 4096 | flav | slab | fast) not in seen:
+                        allf.append(f"{label} instantiation <{r}, {4096 | flav | slab | fast}> missing from the ISA")
     for f in allf[:40]:
         print("  ", f)
     if kernels == 0 or total == 0:
