@@ -201,11 +201,6 @@ struct Slab {
 
 }  // namespace
 
-// An lbm_run_forces in progress (lbm_ctx::fplan): nb bodies; the run's forces are nval = 2 nb nsteps doubles at
-// sums + nsteps + 1 of every slab (behind the per-step sums and the spare word of run_regtile_slabs' "somebody gave up"),
-// reduced and fetched with them; in_kernel: the register tiles run their kRegForce flavour.
-struct ForcePlan { int nb; long nval; bool in_kernel; };
-
 struct lbm_ctx {
   lbm_param p;
   std::vector<Slab> slabs;     // slabs owned by THIS process
@@ -242,28 +237,22 @@ struct lbm_ctx {
   int samples_in_kernel = 0;   // 1: the snapshots of the last lbm_run_sampled came from the register tiles
   int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
   int nbodies = 0;             // lbm_set_bodies (0: none)
-  const ForcePlan* fplan = nullptr;   // the lbm_run_forces in progress (nullptr: a plain run)
   // obstacle map of the local rows and one row either side (global rows keep_row0 .. keep_row0 + keep_rows - 1, taken
   // modulo ny), for the bodies' direction masks
   std::vector<uint8_t> obst_keep;
   int keep_row0 = 0, keep_rows = 0;
-  // register-tile engine (engine 3): 64 x ty tiles, nw waves of r rows (ty == 0: none); bpc = blocks of this tiling a CU
-  // takes by the occupancy query (0 = not asked yet, -1 = the query failed or the grid does not fit)
-  struct { int ty = 0, r = 0, nw = 0, ntx = 0, nty = 0, bpc = 0; } tplan;
-  unsigned long long* tmail = nullptr;   // its mailboxes
-  float* rpartials = nullptr;  // [steps][tiles]
-  long rpartials_cap = 0;      // in steps
-  int rpartials_tiles = 0;     // tiles per step it was sized for
-  uint32_t* rabort = nullptr;  // device abort word of the resident kernel
+  // register-tile engine (engine 3), a lattice alone or the same tiling on every slab: 64 x ty tiles, nw waves of r rows
+  // (ty == 0: none), nty tile rows per slab; bpc = blocks of this tiling a CU takes by the occupancy query (0 = not asked yet,
+  // -1 = the query failed or the grid does not fit); the local slabs grouped by device (order[gstart[g]] .. : the slabs of
+  // device group g, found at the first run).  The buffers are the slabs'.
+  struct { int ty = 0, r = 0, nw = 0, ntx = 0, nty = 0, bpc = 0; std::vector<int> order, gstart; } tplan;
   int regtile_async = 1;       // lbm_regtile, R > 1: the loop's mail issued and waited for by hand (counted vmcnt), granules sent at once
                                // (0: the round-2 loop, compiler-scheduled loads and stores; R = 1 always runs that one)
   uint32_t rtag = 1;           // next unused mailbox tag (0 = never written); never goes back except when the mailboxes are cleared
   bool resident_broken = false;   // the resident kernel cannot run here (not every tile resident, set-up failed, or a run
                                   // gave up): stay with the streaming kernels
   char resident_why[160] = "";    // ... and why (lbm_last_error does not carry it: the run itself succeeds)
-  // register tiles across slabs: the same 64 x ty tiling on every slab (ty == 0: none); nty = tile rows per slab
-  struct { int ty = 0, r = 0, nw = 0, ntx = 0, nty = 0, bpc = 0; } splan;
-  bool splan_peers = false;             // peer access between the neighbouring slabs' devices has been switched on
+  bool regtile_peers = false;           // peer access between the neighbouring slabs' devices has been switched on
   lbm::RegTileArgs* rtable = nullptr;   // pinned, device-mapped: one entry per local slab, grouped by device
   lbm::RegTileArgs* rtable_dev = nullptr;
   int ncu = 0;                 // CUs of slab 0's device
@@ -386,7 +375,7 @@ int p2p_connect_ipc(lbm_ctx* c, const char* handles, int nranks) {
       s.nb_blocked[side] = (const uint8_t*)s.nb_ipc[side][2];
     }
     // the neighbour's mail area (register tiles across slabs): a fourth handle behind the three, zero if it has none
-    if (c->splan.ty > 0 && r != c->rank) {
+    if (c->tplan.ty > 0 && r != c->rank) {
       if (side == 1 && north == south) { s.tmail_nb[1] = s.tmail_nb[0]; s.tmail_nb_bytes[1] = s.tmail_nb_bytes[0]; s.tmail_nb_ipc[1] = false; }
       else {
         hipIpcMemHandle_t h, zero;
@@ -394,8 +383,8 @@ int p2p_connect_ipc(lbm_ctx* c, const char* handles, int nranks) {
         HIPC(hipMemcpy(&h, blocks[side] + 4 * s.halo_bytes + 512 + 192, sizeof(h), hipMemcpyDeviceToHost));
         void* ptr = nullptr;
         if (memcmp(&h, &zero, sizeof(h)) != 0 && hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess) == hipSuccess) {
-          s.tmail_nb[side] = (char*)ptr; s.tmail_nb_bytes[side] = regtile_slab_mail_bytes(c); s.tmail_nb_ipc[side] = true;
-        } else { (void)hipGetLastError(); c->splan.ty = 0; }      // (no mail area over there, or not mappable: the streaming kernels)
+          s.tmail_nb[side] = (char*)ptr; s.tmail_nb_bytes[side] = regtile_mail_bytes(c); s.tmail_nb_ipc[side] = true;
+        } else { (void)hipGetLastError(); c->tplan.ty = 0; }      // (no mail area over there, or not mappable: the streaming kernels)
       }
     }
   }
@@ -563,7 +552,7 @@ extern "C" int lbm_create_rank_ex(const lbm_param* params, const int* obstacles,
     if (!rc) {  // agreement: sum of failures over all ranks -- [0] the halo blocks, [1] the mail areas of the register tiles
       // (a rank whose mail area could not be allocated or mapped must not be the only one to know: the others would launch
       // tiles that wait for its mail)
-      bool tiles_ok = c->splan.ty > 0;
+      bool tiles_ok = c->tplan.ty > 0;
       if (tiles_ok && nranks > 1) for (int side = 0; side < 2; ++side) tiles_ok = tiles_ok && s.tmail_nb[side] != nullptr;
       double both[2] = {p2p_rc ? 1.0 : 0.0, tiles_ok ? 0.0 : 1.0}, *d_f = (double*)d_buf;
       (void)hipMemcpy(d_f, both, sizeof(both), hipMemcpyHostToDevice);
@@ -571,7 +560,7 @@ extern "C" int lbm_create_rank_ex(const lbm_param* params, const int* obstacles,
       if (r != 0 || hipStreamSynchronize(s.sc) != hipSuccess) rc = fail(LBM_ERCCL, "peer-to-peer agreement failed");
       else (void)hipMemcpy(both, d_f, sizeof(both), hipMemcpyDeviceToHost);
       const double fails = both[0];
-      if (!rc && both[1] > 0.0) c->splan.ty = 0;       // somebody has no register tiling: nobody uses it
+      if (!rc && both[1] > 0.0) c->tplan.ty = 0;       // somebody has no register tiling: nobody uses it
       if (!rc && fails > 0.0) {
         // somebody could not map a neighbour: everyone trades halos by RCCL instead
         if (getenv("LBM_VERBOSE")) fprintf(stderr, "lbm: peer-to-peer halos unavailable (%s); using RCCL\n", p2p_rc ? g_err : "another rank failed");
@@ -626,57 +615,39 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 
 static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
 
-// Will the next run try the register tiles first?  (info "engine_next")
-static bool regtile_is_next(const lbm_ctx* c) {
-  if (c->exchange != 0) return regtile_slabs_usable(c);
-  return c->slabs.size() == 1 && !c->resident_broken && (c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && (c->variant & 8) == 0;
-}
-
-// The step loop of lbm_run.  sn != nullptr (lbm_run_sampled): ONLY the register-tile engines are tried, with the snapshots
-// in the kernel; *sampled tells whether they ran -- if not, nothing has been stepped and the caller runs the steps in pieces.
-static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn, bool* sampled) {
-  if (sampled) *sampled = false;
+// The step loop of lbm_run.  k.snap (lbm_run_sampled): ONLY the register tiles are tried, with the snapshots in the kernel;
+// if they did not run (samples_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
+static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind()) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   const int nx = c->p.nx;
   const float a1 = c->p.density * c->p.accel / 9.f;   // d2q9-bgk.c:230-231
   const float a2 = c->p.density * c->p.accel / 36.f;
-  const bool tiles_ok = !c->fplan || c->fplan->in_kernel;   // (lbm_run_forces: the register tiles only in their force flavour)
-  if (c->exchange != 0 && tiles_ok && regtile_slabs_usable(c)) {
+  const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour, else the one-step kernel, lbm_body_forces behind each step
+  if ((!fo || k.force_tiles) && regtile_is_next(c)) {
     bool done = false;
-    int rr = run_regtile_slabs(c, nsteps, av_vels, &done, sn);
-    if (rr && c->engine == 0) {          // (as below: set-up failures of the automatic engine are not the caller's problem)
-      (void)hipGetLastError();
-      resident_give_up(c, lbm_last_error());
-      rr = LBM_OK;
-    }
-    if (rr) return rr;
-    if (done) { c->engine_last = 3; if (sampled) *sampled = true; return LBM_OK; }
-  }
-  if (c->exchange != 0 && c->engine >= 2 && !c->fplan) return fail(LBM_EINVAL, "register tiles across slabs cannot run here (%s) (engine = %d)",
-                                                      c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
-  if (sn && c->exchange != 0) return LBM_OK;
-  if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels); }
-  if (tiles_ok && c->exchange == 0 && c->slabs.size() == 1 && (c->engine == 3 || c->engine == 0) && c->tplan.ty > 0 && !c->resident_broken &&
-      (c->variant & 8) == 0) {
-    bool done = false;
-    int rr = run_regtile(c, nsteps, av_vels, &done, sn);
+    int rr = run_regtile(c, nsteps, av_vels, &done, k);
     if (rr && c->engine == 0) {
-      // automatic engine: a set-up or launch failure of the resident kernel (LDS attribute refused, tiles not all
-      // resident, allocation failed) is not the caller's problem -- the source lattice is untouched, the streaming kernels run
+      // automatic engine: a set-up or launch failure of the register tiles (LDS attribute refused, tiles not all resident,
+      // allocation failed) is not the caller's problem -- the source lattice is untouched, the streaming kernels run
       (void)hipGetLastError();
       resident_give_up(c, lbm_last_error());
       rr = LBM_OK;
     }
     if (rr) return rr;
-    if (done) { c->engine_last = 3; if (sampled) *sampled = true; return LBM_OK; }
+    if (done) {
+      c->engine_last = 3;
+      if (k.snap) c->samples_in_kernel = 1;
+      if (fo) c->forces_in_kernel = 1;
+      return LBM_OK;
+    }
   }
-  if (c->engine >= 2 && !c->fplan) return fail(LBM_EINVAL, "the resident kernel cannot run here (%s), or this lattice has no resident tiling (engine = %d)",
-                                  c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
-  if (sn) return LBM_OK;
+  if (c->engine >= 2 && !fo) return fail(LBM_EINVAL, "the register tiles cannot run here (%s), or this lattice has no register tiling (engine = %d)",
+                                         c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
+  if (k.snap) return LBM_OK;
+  if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels, k); }
   c->engine_last = 1;
   const bool ex = c->exchange != 0;
-  const bool fo = c->fplan != nullptr;   // lbm_run_forces off the register tiles: the one-step kernel, lbm_body_forces behind each step
   const bool pairs = !fo && t2_eligible(c) && nsteps >= 2;
   int rc;
 
@@ -805,7 +776,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
   const int first_single = tt;
   for (; tt < nsteps; ++tt, ++li) {
     if ((rc = launch_single(c, li, tt, tt == nsteps - 1, tt > first_single, a1, a2))) return rc;
-    if (fo && (rc = launch_forces(c, tt, li & 1, nsteps))) return rc;
+    if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
   }
 
   // ---- epilogue: fold the last single step's partials, collect the per-step sums
@@ -821,7 +792,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, const SnapPlan* sn,
     HIPC(hipEventRecord(s.ev_t1, s.sc));
     if (ex) HIPC(hipStreamWaitEvent(s.sc, s.ev_recv[ql], 0));  // drain the last exchange
   }
-  return collect_sums(c, nsteps, av_vels, wall0);
+  return collect_sums(c, nsteps, av_vels, wall0, k);
 }
 
 extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) { return lbm_run_sampled(c, nsteps, av_vels, 0, nullptr); }
@@ -833,7 +804,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
   const int m = every > 0 ? nsteps / every : 0;
   if (m > 0 && !fields_out) return fail(LBM_EINVAL, "fields_out is NULL but %d snapshot(s) are due", m);
   c->samples_in_kernel = 0;
-  if (m == 0) return run_steps(c, nsteps, av_vels, nullptr, nullptr);
+  if (m == 0) return run_steps(c, nsteps, av_vels);
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   const int nx = c->p.nx;
@@ -872,9 +843,10 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
       }
       sp.at.push_back((float*)stage[i].p); sp.stride.push_back((long)s.nyl * nx * 4);
     }
-    bool sampled = false;
-    if ((rc = run_steps(c, nsteps, av_vels, &sp, &sampled))) return rc;
-    if (sampled) {
+    RunKind k;
+    k.snap = &sp;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->samples_in_kernel) {
       if (!on_dev)
         for (size_t i = 0; i < c->slabs.size(); ++i) {
           Slab& s = c->slabs[i];
@@ -883,7 +855,6 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
           HIPC(hipMemcpy2D(fields_out + 4L * (s.row0 - base_row) * nx, sizeof(float) * (size_t)slot, stage[i].p, w, w, (size_t)m,
                            hipMemcpyDeviceToHost));
         }
-      c->samples_in_kernel = 1;
       return LBM_OK;
     }
     // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run)
@@ -894,7 +865,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
   for (int j = 0; j <= m; ++j) {
     const int n = (j < m) ? every : nsteps - done;
     if (n == 0) break;
-    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr, nullptr, nullptr))) return rc;
+    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
     gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
     done += n;
     if (j < m && (rc = derive_all(c, fields_out + (size_t)j * (size_t)slot, nullptr, nullptr, on_dev))) return rc;
@@ -958,7 +929,7 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
   if (c->nbodies == 0) return fail(LBM_EINVAL, "no bodies are set (lbm_set_bodies)");
   if (nsteps > 0 && !forces) return fail(LBM_EINVAL, "forces is NULL");
   c->forces_in_kernel = 0;
-  if (nsteps == 0) return run_steps(c, 0, av_vels, nullptr, nullptr);
+  if (nsteps == 0) return run_steps(c, 0, av_vels);
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   const int nb = c->nbodies;
   const long nval = 2L * nb * nsteps;
@@ -969,9 +940,8 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
     if (ensure_sums(s, (int)(nsteps + 1 + nval))) { (void)hipGetLastError(); return fail(LBM_ENOMEM, "no room for the sums of %d steps and their forces", nsteps); }
   bool in_kernel = regtile_is_next(c);
   if (in_kernel) {
-    const int ty = c->exchange != 0 ? c->splan.ty : c->tplan.ty, ntx = c->exchange != 0 ? c->splan.ntx : c->tplan.ntx;
     for (auto& s : c->slabs)
-      if ((rc = force_tables(c, s, ty, ntx, nsteps))) break;
+      if ((rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps))) break;
   }
   if (c->rank_mode && c->slabs[0].comm != nullptr) {
     // every rank takes the same path and fails together: [0] ranks short of room, [1] ranks that would not use the tiles
@@ -987,13 +957,9 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
   } else if (rc) {
     return rc;
   }
-  const ForcePlan fp{nb, nval, in_kernel};
-  c->fplan = &fp;
-  bool tiles = false;
-  rc = run_steps(c, nsteps, av_vels, nullptr, &tiles);
-  c->fplan = nullptr;
-  if (rc) return rc;
-  c->forces_in_kernel = tiles ? 1 : 0;
+  RunKind k;
+  k.nb = nb; k.nval = nval; k.force_tiles = in_kernel;
+  if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
   // the local slabs' sums (a rank: everybody's, through the all-reduce that ended the run)
   for (long k = 0; k < nval; ++k) {
     double acc = 0.0;
@@ -1096,8 +1062,7 @@ extern "C" int lbm_final_state(lbm_ctx* c, float* out) {
 
 extern "C" int lbm_destroy(lbm_ctx* c) {
   if (!c) return LBM_OK;
-  resident_free(c);
-  regtile_slabs_free(c);
+  regtile_free(c);
   for (auto& s : c->slabs) slab_free(s);
   delete c;
   return LBM_OK;
@@ -1178,7 +1143,7 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
   if (!strcmp(key, "engine")) {
     if (value != 0 && value != 1 && value != 3)
       return fail(LBM_EINVAL, "engine must be 0 (auto), 1 (streaming kernels) or 3 (resident in registers); 2, the LDS-resident engine, was removed");
-    if (value == 3 && c->exchange != 0 && c->splan.ty == 0)
+    if (value == 3 && c->exchange != 0 && c->tplan.ty == 0)
       return fail(LBM_EINVAL, "register tiles across slabs need equal slabs that tile onto the CUs and neighbours that can store into each other's memory");
     if (value == 3 && c->exchange == 0 && (c->slabs.size() != 1 || c->tplan.ty == 0))
       return fail(LBM_EINVAL, "the resident kernel needs a lattice alone on its GPU that tiles onto the CUs");
@@ -1186,7 +1151,6 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
     if (value == 3) {
       c->resident_broken = false; c->resident_why[0] = 0;
       if (c->tplan.bpc < 0) c->tplan.bpc = 0;
-      if (c->splan.bpc < 0) c->splan.bpc = 0;
     }
     return LBM_OK;
   }
@@ -1199,15 +1163,14 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
     if (value != 0 && value != 1) return fail(LBM_EINVAL, "regtile_async must be 0 or 1");
     c->regtile_async = (int)value;
     c->tplan.bpc = c->tplan.bpc < 0 ? c->tplan.bpc : 0;     // (another instantiation: ask about its residency again)
-    c->splan.bpc = c->splan.bpc < 0 ? c->splan.bpc : 0;
     return LBM_OK;
   }
   if (!strcmp(key, "regtile")) {   // rows per tile * 10 + rows per wave
     const int ty = (int)(value / 10), r = (int)(value % 10);
     if (c->exchange != 0 || c->slabs.size() != 1 || !regtile_ok(c, ty, r))
       return fail(LBM_EINVAL, "register tile of %d rows, %d per wave, does not fit this lattice / device", ty, r);
-    if (c->tmail) { (void)hipFree(c->tmail); c->tmail = nullptr; }
-    regtile_set(c, ty, r);
+    regtile_free(c);
+    regtile_set(c, ty, r, c->p.ny / ty);
     return LBM_OK;
   }
   if (!strcmp(key, "kernel_variant")) {
@@ -1246,9 +1209,9 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
     return LBM_OK;
   }
   if (!strcmp(key, "resident_fallback")) { *value = c->resident_broken ? 1 : 0; return LBM_OK; }   // 1: the resident kernel could not run here
-  if (!strcmp(key, "regtile_blocks_per_cu")) { *value = c->exchange != 0 ? c->splan.bpc : c->tplan.bpc; return LBM_OK; }   // occupancy answer (0: not asked yet)
+  if (!strcmp(key, "regtile_blocks_per_cu")) { *value = c->tplan.bpc; return LBM_OK; }   // occupancy answer (0: not asked yet)
   if (!strcmp(key, "compute_units")) { *value = c->ncu; return LBM_OK; }
-  if (!strcmp(key, "regtile")) { *value = c->exchange != 0 ? c->splan.ty * 10.0 + c->splan.r : c->tplan.ty * 10.0 + c->tplan.r; return LBM_OK; }
+  if (!strcmp(key, "regtile")) { *value = c->tplan.ty * 10.0 + c->tplan.r; return LBM_OK; }
   if (!strcmp(key, "regtile_async")) { *value = c->regtile_async; return LBM_OK; }
   if (!strcmp(key, "regtile_tag")) { *value = c->rtag; return LBM_OK; }
   if (!strcmp(key, "exchange")) { *value = c->exchange; return LBM_OK; }

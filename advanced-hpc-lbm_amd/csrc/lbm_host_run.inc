@@ -1,5 +1,5 @@
-// lbm_host_run.inc -- part of lbm_api.hip (included there): the end of a run (sums, agreement), the register-tile engine alone
-// and across slabs, the step loop with peer-to-peer halos.
+// lbm_host_run.inc -- part of lbm_api.hip (included there): the end of a run (sums, agreement), the register-tile engine (one
+// driver for a lattice alone and for slabs), the step loop with peer-to-peer halos.
 namespace {
 
 // Where a register-tile run puts its snapshots (lbm_run_sampled): per local slab, the slab's region of snapshot 0 on its
@@ -10,13 +10,25 @@ struct SnapPlan {
   std::vector<long> stride;
 };
 
+// The kind of a run, handed from lbm_run / lbm_run_sampled / lbm_run_forces through run_steps to the engine that runs it
+// (a plain lbm_run: the defaults).  snap (lbm_run_sampled): ONLY the register tiles are tried, with the snapshots in the
+// kernel.  nb > 0 (lbm_run_forces): nb bodies; the run's forces are nval = 2 nb nsteps doubles at sums + nsteps + 1 of every
+// slab (behind the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with
+// them; force_tiles: the register tiles may run, in their kRegForce flavour (else the run keeps off them).
+struct RunKind {
+  const SnapPlan* snap = nullptr;
+  int nb = 0;
+  long nval = 0;
+  bool force_tiles = false;
+};
+
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the
 // peer-to-peer error word through pinned staging with async copies queued behind the step loop,
 // then ONE wait per slab (s.sc has joined the edge and exchange streams by then).
-int collect_sums(lbm_ctx* c, int nsteps, float* av_vels, std::chrono::steady_clock::time_point wall0, int extra = 0) {
-  // (extra: doubles behind the per-step sums that are reduced and fetched with them -- run_regtile_slabs' "somebody gave up";
+int collect_sums(lbm_ctx* c, int nsteps, float* av_vels, std::chrono::steady_clock::time_point wall0, RunKind k, int extra = 0) {
+  // (extra: doubles behind the per-step sums that are reduced and fetched with them -- the register tiles' "somebody gave up";
   // during lbm_run_forces that word and the forces behind it, on every path: every rank issues the same count)
-  if (c->fplan) extra = 1 + (int)c->fplan->nval;
+  if (k.nb > 0) extra = 1 + (int)k.nval;
   if (c->rank_mode && c->slabs[0].comm != nullptr) {   // (a ring of one rank has a communicator too: identity)
     Slab& s = c->slabs[0];
     NCCLC(rccl::AllReduce(s.sums, s.sums, (size_t)(nsteps + extra), rccl::kFloat64, rccl::kSum, s.comm, s.sc));
@@ -98,29 +110,18 @@ int force_tables(lbm_ctx* c, Slab& s, int ty, int ntx, int nsteps) {
 
 // Every engine but the register tiles: the forces of step tt (0-based) from the lattice just stored, on the compute stream
 // behind the step (and behind its edge rows, where they run on a stream of their own); launch parity q.
-int launch_forces(lbm_ctx* c, int tt, int q, int nsteps) {
-  const ForcePlan& fp = *c->fplan;
+int launch_forces(lbm_ctx* c, int tt, int q, int nsteps, RunKind k) {
   for (auto& s : c->slabs) {
     HIPC(hipSetDevice(s.dev));
     if (c->exchange != 0 && c->exchange != LBM_EXCHANGE_P2P && split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[q], 0));
     hipLaunchKernelGGL(lbm::lbm_body_forces, dim3(1), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.fcells, s.fcells_n,
-                       fp.nb, s.sums + nsteps + 1 + (long)tt * 2 * fp.nb);
+                       k.nb, s.sums + nsteps + 1 + (long)tt * 2 * k.nb);
     HIPC(hipGetLastError());
   }
   return LBM_OK;
 }
 
-// ----------------------------------------------------------------- resident engine
-void resident_free(lbm_ctx* c) {
-  if (c->slabs.empty()) return;
-  (void)hipSetDevice(c->slabs[0].dev);
-  if (c->tmail) (void)hipFree(c->tmail);
-  c->tmail = nullptr; c->rpartials_tiles = 0;
-  if (c->rpartials) (void)hipFree(c->rpartials);
-  if (c->rabort) (void)hipFree(c->rabort);
-  c->rpartials = nullptr; c->rabort = nullptr; c->rpartials_cap = 0;
-}
-
+// ----------------------------------------------------------------- register tiles (lbm_regtile.hip.h)
 // The resident engine cannot be used on this context (any more): remember why, say so ONCE on stderr (a run that quietly
 // takes twice as long is worse than a line of text), carry on with the streaming kernels.
 void resident_give_up(lbm_ctx* c, const char* why) {
@@ -131,7 +132,7 @@ void resident_give_up(lbm_ctx* c, const char* why) {
   said = true;
 }
 
-// ---- register-tile engine (lbm_regtile.hip.h): 64-column tiles of nw x r rows, one per CU
+// ---- a lattice alone on its GPU: 64-column tiles of nw x r rows, one per CU
 bool regtile_ok(const lbm_ctx* c, int ty, int r) {
   if (c->p.nx % 64 != 0 || ty < 1 || ty > c->p.ny || c->p.ny % ty != 0) return false;
   if (!(r == 1 || r == 2 || r == 4) || ty % r != 0 || ty / r > 16) return false;
@@ -140,9 +141,10 @@ bool regtile_ok(const lbm_ctx* c, int ty, int r) {
   const int per_cu = std::min({3, 16 / nw, (160 * 1024) / lbm::regtile_lds_bytes(nw, r)});
   return (long)(c->p.nx / 64) * (c->p.ny / ty) <= (long)c->ncu * per_cu;
 }
-void regtile_set(lbm_ctx* c, int ty, int r) {
-  c->tplan.ty = ty; c->tplan.r = r; c->tplan.nw = ty / r; c->tplan.ntx = c->p.nx / 64; c->tplan.nty = c->p.ny / ty;
-  c->tplan.bpc = 0;          // (the residency of this tiling has not been asked yet)
+// The tiling of every slab (of the lattice alone): tiles of ty rows, nty tile rows per slab; its residency not asked yet
+void regtile_set(lbm_ctx* c, int ty, int r, int nty) {
+  c->tplan.ty = ty; c->tplan.r = r; c->tplan.nw = ty / r; c->tplan.ntx = c->p.nx / 64; c->tplan.nty = nty;
+  c->tplan.bpc = 0;
 }
 // Default tiling (of a lattice alone and of equal slabs alike; `per_dev` = slabs sharing a device, `rows` = rows per slab).
 // Measured with the mailboxes in uncached memory (profiles/r03_regtile_tilings.log), us per step: the SHORTEST tiles that
@@ -173,48 +175,90 @@ bool plan_regtile(lbm_ctx* c) {
   c->tplan.ty = 0;
   int ty = 0, r = 0;
   if (!regtile_default_tiling(c, c->p.ny, 1, &ty, &r) || !regtile_ok(c, ty, r)) return false;
-  regtile_set(c, ty, r);
+  regtile_set(c, ty, r, c->p.ny / ty);
   return true;
 }
 
-// The instantiation of lbm_regtile for a tiling and flavour (dbg: the LBM_RESIDENT_DEBUG timing experiments, R = 4 only).
-typedef void (*regtile_fn)(const lbm::RegTileArgs);
-// The kRegForce instantiations of lbm_regtile (lbm_run_forces)
-regtile_fn regtile_force_kernel(int r, bool fast, bool async) {
-  constexpr int AS_ = lbm::kRegAsync, FO_ = lbm::kRegForce;
-  if (async && r == 4) return fast ? lbm::lbm_regtile<4, FO_ | AS_ | 1> : lbm::lbm_regtile<4, FO_ | AS_>;
-  if (async && r == 2) return fast ? lbm::lbm_regtile<2, FO_ | AS_ | 1> : lbm::lbm_regtile<2, FO_ | AS_>;
+// ---- register tiles ACROSS SLABS (SURVEY 8 f1, the multi-GPU half): every slab keeps its rows in the registers of its
+// own GPU for the whole run, and the granules that leave a slab through its bottom / top edge go straight into the
+// neighbouring slab's mailboxes (lbm_regtile.hip.h, kRegSlab) -- over xGMI when that slab lives on another GPU.  Same
+// tiling on every slab (equal slabs, 64-column tiles of ty rows); the slabs of one device go in ONE launch (their tiles
+// wait for each other, so they must be resident together).  Contexts whose neighbours can store into each other's
+// memory: slabs of one process (copy and peer-to-peer contexts: pointers, peer access across devices), and one process
+// per GPU with peer-to-peer halos (hipIpc mappings, handles in the halo block; needs the communicator, through which the
+// ranks agree after every run whether anybody gave up).
+int regtile_slab_count(const lbm_ctx* c) { return c->rank_mode ? c->nranks : (int)c->slabs.size(); }
+
+bool regtile_slabs_possible(const lbm_ctx* c) {
+  if (c->exchange != LBM_EXCHANGE_P2P && c->exchange != LBM_EXCHANGE_COPY) return false;
+  // (ranks without a communicator cannot agree on whether anybody gave up: the streaming kernels, unless a test that adds up
+  // the ranks' results itself says otherwise)
+  static const bool trust = getenv("LBM_REGTILE_SLABS_NO_AGREEMENT") && atoi(getenv("LBM_REGTILE_SLABS_NO_AGREEMENT"));
+  if (c->rank_mode && c->nranks > 1 && ((c->no_comm && !trust) || c->exchange != LBM_EXCHANGE_P2P)) return false;
+  const int n = regtile_slab_count(c);
+  return c->p.nx % 64 == 0 && n >= 1 && c->p.ny % n == 0;
+}
+
+// Tiling: as for a lattice alone (as few rows per wave as fit, on at most half the CUs where possible), counted per device.
+bool plan_regtile_slabs(lbm_ctx* c) {
+  c->tplan.ty = 0;
+  if (!regtile_slabs_possible(c)) return false;
+  const char* off = getenv("LBM_REGTILE_SLABS");
+  if (off && atoi(off) == 0) return false;
+  const int nyl = c->p.ny / regtile_slab_count(c);
+  int per_dev = 1;
+  for (auto& a : c->slabs) {
+    int n = 0;
+    for (auto& b : c->slabs) n += (b.dev == a.dev) ? 1 : 0;
+    per_dev = std::max(per_dev, n);
+  }
+  // (development: LBM_REGTILE_SLAB_TILING = rows per tile x 10 + rows per wave, as the `regtile` option of a lone lattice)
+  const int forced = getenv("LBM_REGTILE_SLAB_TILING") ? atoi(getenv("LBM_REGTILE_SLAB_TILING")) : 0;
+  int ty = 0, r = 0;
+  if (forced > 0) {
+    ty = forced / 10; r = forced % 10;
+    if (!(r == 1 || r == 2 || r == 4) || ty < r || ty % r != 0 || ty / r > 16 || nyl % ty != 0 ||
+        (long)per_dev * (c->p.nx / 64) * (nyl / ty) > (long)c->ncu) return false;
+  } else if (!regtile_default_tiling(c, nyl, per_dev, &ty, &r)) return false;
+  regtile_set(c, ty, r, nyl / ty);
+  return true;
+}
+
+// Will the next run try the register tiles first?  (info "engine_next")
+bool regtile_is_next(const lbm_ctx* c) {
+  if (c->tplan.ty <= 0 || c->resident_broken || (c->variant & 8) != 0 || !(c->engine == 0 || c->engine == 3)) return false;
+  if (c->exchange == 0) return c->slabs.size() == 1;
+  if (!regtile_slabs_possible(c)) return false;
+  if (c->rank_mode && c->nranks > 1) {
+    if (!c->p2p_connected) return false;
+    for (int side = 0; side < 2; ++side) if (!c->slabs[0].tmail_nb[side]) return false;
+  }
+  return true;
+}
+
+// The instantiation of the register tiles for a tiling and a flavour (0, kRegSnap, kRegForce): lbm_regtile, its arguments
+// by value (a lattice alone), or lbm_regtile_slabs, a table of them (SLAB)
+template <bool SLAB, int R, int MODE>
+constexpr auto regtile_instance() {
+  if constexpr (SLAB) return lbm::lbm_regtile_slabs<R, MODE | lbm::kRegSlab>;
+  else return lbm::lbm_regtile<R, MODE>;
+}
+template <bool SLAB, int FLAVOUR>
+auto regtile_flavour(int r, bool fast, bool async) {
+  constexpr int AS = lbm::kRegAsync | FLAVOUR;     // (R = 1 has no asynchronous loop)
+  if (async && r == 4) return fast ? regtile_instance<SLAB, 4, AS | 1>() : regtile_instance<SLAB, 4, AS>();
+  if (async && r == 2) return fast ? regtile_instance<SLAB, 2, AS | 1>() : regtile_instance<SLAB, 2, AS>();
   switch (r) {
-    case 4: return fast ? lbm::lbm_regtile<4, FO_ | 1> : lbm::lbm_regtile<4, FO_>;
-    case 2: return fast ? lbm::lbm_regtile<2, FO_ | 1> : lbm::lbm_regtile<2, FO_>;
-    default: return fast ? lbm::lbm_regtile<1, FO_ | 1> : lbm::lbm_regtile<1, FO_>;
+    case 4: return fast ? regtile_instance<SLAB, 4, FLAVOUR | 1>() : regtile_instance<SLAB, 4, FLAVOUR>();
+    case 2: return fast ? regtile_instance<SLAB, 2, FLAVOUR | 1>() : regtile_instance<SLAB, 2, FLAVOUR>();
+    default: return fast ? regtile_instance<SLAB, 1, FLAVOUR | 1>() : regtile_instance<SLAB, 1, FLAVOUR>();
   }
 }
-regtile_fn regtile_kernel(int r, bool fast, int dbg, bool trace, bool async, bool snap) {
-  constexpr int NW_ = lbm::kResDebugNoWait, NS_ = lbm::kResDebugNoSend, AS_ = lbm::kRegAsync, SN_ = lbm::kRegSnap;
-  if (snap) {                  // (lbm_run_sampled: the production flavours only)
-    if (async && r == 4) return fast ? lbm::lbm_regtile<4, SN_ | AS_ | 1> : lbm::lbm_regtile<4, SN_ | AS_>;
-    if (async && r == 2) return fast ? lbm::lbm_regtile<2, SN_ | AS_ | 1> : lbm::lbm_regtile<2, SN_ | AS_>;
-    switch (r) {
-      case 4: return fast ? lbm::lbm_regtile<4, SN_ | 1> : lbm::lbm_regtile<4, SN_>;
-      case 2: return fast ? lbm::lbm_regtile<2, SN_ | 1> : lbm::lbm_regtile<2, SN_>;
-      default: return fast ? lbm::lbm_regtile<1, SN_ | 1> : lbm::lbm_regtile<1, SN_>;
-    }
-  }
-  if (async && dbg == 0 && !trace && r == 4) return fast ? lbm::lbm_regtile<4, AS_ | 1> : lbm::lbm_regtile<4, AS_>;
-  if (async && dbg == 0 && !trace && r == 2) return fast ? lbm::lbm_regtile<2, AS_ | 1> : lbm::lbm_regtile<2, AS_>;
-  if (async && trace && r == 4) return lbm::lbm_regtile<4, AS_ | 2048 | 1>;
-  if (r == 4 && dbg == 1) return lbm::lbm_regtile<4, NW_>;
-  if (r == 4 && dbg == 2) return lbm::lbm_regtile<4, NW_ | NS_>;
-  if (r == 4 && dbg == 3) return lbm::lbm_regtile<4, NW_ | NS_ | 256>;
-  if (r == 4 && dbg == 4) return lbm::lbm_regtile<4, NW_ | 512>;
-  if (r == 4 && dbg == 5) return lbm::lbm_regtile<4, NW_ | 1024>;
-  if (r == 4 && trace) return lbm::lbm_regtile<4, 2048>;
-  switch (r) {
-    case 4: return fast ? lbm::lbm_regtile<4, 1> : lbm::lbm_regtile<4, 0>;
-    case 2: return fast ? lbm::lbm_regtile<2, 1> : lbm::lbm_regtile<2, 0>;
-    default: return fast ? lbm::lbm_regtile<1, 1> : lbm::lbm_regtile<1, 0>;
-  }
+template <bool SLAB>
+auto regtile_kernel(int r, bool fast, bool async, int flavour) {
+  if (flavour == lbm::kRegSnap) return regtile_flavour<SLAB, lbm::kRegSnap>(r, fast, async);
+  if (flavour == lbm::kRegForce) return regtile_flavour<SLAB, lbm::kRegForce>(r, fast, async);
+  return regtile_flavour<SLAB, 0>(r, fast, async);
 }
 
 // Before the first launch of a tiling on a device: let the kernel have its dynamic LDS (beyond the 64 KB a kernel gets
@@ -244,239 +288,25 @@ int regtile_prepare(const lbm_ctx* c, const void* fn, int dev, int threads, unsi
   return n;
 }
 
-int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPlan* sn) {
-  *done = false;
-  Slab& s = c->slabs[0];
-  HIPC(hipSetDevice(s.dev));
-  const auto& t = c->tplan;
-  const int ntiles = t.ntx * t.nty;
-  const size_t mail_bytes = (size_t)ntiles * 2 * (size_t)lbm::regtile_box(t.ty);
-  const bool fast = (c->variant & lbm::kFastMath) != 0;
-  const dim3 grid(ntiles), block(64 * t.nw);
-  const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const char* dbg = getenv("LBM_RESIDENT_DEBUG");   // timing experiments (wrong results): see lbm_regtile.hip.h
-  static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run, and a trace
-  const regtile_fn fn0 = regtile_kernel(t.r, fast, dbg ? atoi(dbg) : 0, want_stats && getenv("LBM_REGTILE_TRACE"), c->regtile_async != 0, false);
-  const bool fk = c->fplan && c->fplan->in_kernel;    // lbm_run_forces: the kRegForce flavour, with its larger LDS
-  const regtile_fn fn = fk ? regtile_force_kernel(t.r, fast, c->regtile_async != 0)
-                           : sn ? regtile_kernel(t.r, fast, 0, false, c->regtile_async != 0, true) : fn0;
-  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : shm;
-  if (c->tplan.bpc == 0) {                             // first run of this tiling: is every tile resident at once?
-    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn0), s.dev, (int)block.x, shm);
-    c->tplan.bpc = (n < 0) ? -1 : n;
-    if (n < 0) snprintf(c->resident_why, sizeof(c->resident_why), "%s", lbm_last_error());
-    else if ((long)n * std::max(c->ncu, 1) < (long)ntiles) {
-      c->tplan.bpc = -1;
-      snprintf(c->resident_why, sizeof(c->resident_why), "%d tiles of %d waves, but the device takes %d block(s) per CU on %d CUs at once", ntiles, t.nw, n, c->ncu);
-    }
-  }
-  if (c->tplan.bpc < 0) return fail(LBM_EINVAL, "register tiling not usable: %s", c->resident_why);
-  if (sn || fk) {                                       // the snapshot / force flavour must be resident at once too (else: the split
-    const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), s.dev, (int)block.x, shm_run);   // run / the force kernel)
-    if (n < 0 || (long)n * std::max(c->ncu, 1) < (long)ntiles) { (void)hipGetLastError(); return LBM_OK; }
-  }
-  if (!c->tmail) {
-    // Uncached device memory where the device offers it: the granules are written once and read once, by another CU, and
-    // every access is sc1 anyway -- without the L2 allocation a hand-off is shorter (1024x1024: 4.14 -> 3.48 us per step, found
-    // when the slabs' mail areas, uncached for the sake of stores from other GPUs, ran faster than this one;
-    // LBM_REGTILE_MAIL_CACHED=1: ordinary device memory)
-    static const bool cached = getenv("LBM_REGTILE_MAIL_CACHED") && atoi(getenv("LBM_REGTILE_MAIL_CACHED"));
-    if (cached || hipExtMallocWithFlags((void**)&c->tmail, mail_bytes, hipDeviceMallocUncached) != hipSuccess) {
-      (void)hipGetLastError();
-      c->tmail = nullptr;
-      HIPC(hipMalloc((void**)&c->tmail, mail_bytes));
-    }
-    HIPC(hipMemsetAsync(c->tmail, 0, mail_bytes, s.sc));
-    if (!c->rabort) {
-      HIPC(hipMalloc((void**)&c->rabort, 64));
-      HIPC(hipMemsetAsync(c->rabort, 0, 64, s.sc));
-    }
-  }
-  // Tags only ever grow (a freshly zeroed mailbox is valid for any tag >= 1), except here: before they would wrap, the
-  // mailboxes are cleared and the count starts over.
-  if ((unsigned long long)c->rtag + (unsigned long long)nsteps >= 0x7fffff00ull) {
-    HIPC(hipMemsetAsync(c->tmail, 0, mail_bytes, s.sc));
-    c->rtag = 1;
-  }
-  // per-step tile sums
-  const int rtiles = ntiles;
-  if (c->rpartials_cap < nsteps || c->rpartials_tiles < rtiles) {
-    long cap = std::max(1024L, c->rpartials_cap);
-    while (cap < nsteps) cap *= 2;
-    if (c->rpartials) HIPC(hipFree(c->rpartials));
-    c->rpartials = nullptr; c->rpartials_cap = 0;
-    HIPC(hipMalloc((void**)&c->rpartials, sizeof(float) * (size_t)cap * rtiles));
-    c->rpartials_cap = cap; c->rpartials_tiles = rtiles;
-  }
-  int rc = ensure_sums(s, nsteps);
-  if (rc) return rc;
-  lbm::RegTileArgs a;
-  a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
-  a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = c->p.ny;
-  a.blocked = s.blocked; a.omega = c->p.omega;
-  a.accel_row = c->p.ny - 2;
-  a.a1 = c->p.density * c->p.accel / 9.f; a.a2 = c->p.density * c->p.accel / 36.f;
-  a.ty = t.ty; a.ntx = t.ntx; a.nty = t.nty;
-  a.nsteps = nsteps; a.tag0 = c->rtag;
-  a.mail = c->tmail; a.mail_bytes = (unsigned)mail_bytes; a.partials = c->rpartials; a.abort_word = c->rabort;
-  a.fault = getenv("LBM_REGTILE_FAULT") ? 1 : 0;   // (tests: a tile that never starts)
-  a.stats = nullptr;
-  a.snap = sn ? sn->at[0] : nullptr; a.snap_stride = sn ? sn->stride[0] : 0; a.every = sn ? sn->every : 0;
-  a.density = c->p.density;
-  a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
-  static unsigned long long* stats_buf = nullptr;
-  constexpr size_t kStatsWords = 4 + 16 * 4 * 16 + 72;    // (+ the first wave that gave up: lbm_regtile.hip.h, await)
-  if (want_stats) {
-    if (!stats_buf) HIPC(hipMalloc((void**)&stats_buf, kStatsWords * 8));
-    unsigned long long head[4] = {0, 0, (unsigned long long)(getenv("LBM_REGTILE_TRACE_TILE") ? atoi(getenv("LBM_REGTILE_TRACE_TILE")) : ntiles / 2 + t.ntx / 2),
-                                  (unsigned long long)(getenv("LBM_REGTILE_TRACE_STEP") ? atoi(getenv("LBM_REGTILE_TRACE_STEP")) : nsteps / 2)};
-    HIPC(hipMemsetAsync(stats_buf, 0, kStatsWords * 8, s.sc));
-    HIPC(hipMemcpyAsync(stats_buf, head, sizeof head, hipMemcpyHostToDevice, s.sc));
-    HIPC(hipStreamSynchronize(s.sc));
-    a.stats = stats_buf;
-  }
-  c->rtag += (uint32_t)nsteps + 1u;   // (the last step's mail is sent too, and must never be taken for the next run's state 0)
-  s.err_host[1] = 0;   // lbm_fold_steps stores the abort word here
-  const auto wall0 = std::chrono::steady_clock::now();
-  HIPC(hipEventRecord(s.ev_t0, s.sc));
-  hipLaunchKernelGGL(fn, grid, block, shm_run, s.sc, a);
-  HIPC(hipGetLastError());
-  hipLaunchKernelGGL(lbm::lbm_fold_steps, dim3(cdiv(nsteps, lbm::kBlock / 64)), dim3(lbm::kBlock), 0, s.sc,
-                     c->rpartials, ntiles, nsteps, s.sums, c->rabort, s.err_host + 1);
-  HIPC(hipGetLastError());
-  if (fk) {
-    hipLaunchKernelGGL(lbm::lbm_fold_forces, dim3(cdiv(c->fplan->nval, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
-                       s.fpart, s.fnslots, nsteps, c->fplan->nb, s.sums + nsteps + 1);
-    HIPC(hipGetLastError());
-  }
-  HIPC(hipEventRecord(s.ev_t1, s.sc));
-  rc = collect_sums(c, nsteps, av_vels, wall0);
-  if (rc) return rc;
-  if (want_stats) {
-    std::vector<unsigned long long> st(kStatsWords);
-    HIPC(hipMemcpy(st.data(), stats_buf, kStatsWords * 8, hipMemcpyDeviceToHost));
-    fprintf(stderr, "lbm_regtile: %d steps, %d waves: %llu waits found their mail missing (%.3f per wave and step), %llu extra fetches\n",
-            nsteps, ntiles * t.nw, st[0], (double)st[0] / ((double)nsteps * ntiles * t.nw), st[1]);
-    if (st[1028] != 0) {
-      fprintf(stderr, "lbm_regtile: the first wave to give up: tile %llu (of %d x %d) wave %llu row %llu, waiting for tag %llu (run's tag0 %u); tags it holds, lane: couriers / edge row\n",
-              st[1028] - 1, t.ntx, t.nty, st[1029], st[1030], st[1031], a.tag0);
-      for (int l : {0, 1, 2, 3, 31, 60, 61, 62, 63}) fprintf(stderr, "   lane %2d: %llu / %llu\n", l, st[1032 + l] >> 32, st[1032 + l] & 0xffffffffull);
-    }
-    if (getenv("LBM_REGTILE_TRACE")) {
-      unsigned long long t0 = ~0ull;
-      for (size_t i = 4; i < 4 + 16 * 4 * 16; ++i) if (st[i] && st[i] < t0) t0 = st[i];
-      fprintf(stderr, "trace of tile %llu from step %llu (shader clocks / 100 since the first stamp; slots: barrier | per row: start, mail, done | end)\n", st[2], st[3]);
-      for (int ww = 0; ww < t.nw; ++ww)
-        for (int q = 0; q < 4; ++q) {
-          fprintf(stderr, "  wave %2d step +%d:", ww, q);
-          for (int k = 0; k < 14; ++k) {
-            const unsigned long long v = st[4 + ((ww * 4 + q) * 16 + k)];
-            if (k == 1 || k == 13 || (k > 1 && (k - 1) % 3 == 0)) fprintf(stderr, " |");
-            fprintf(stderr, " %6.1f", v ? (double)(v - t0) / 100.0 : -1.0);
-          }
-          fprintf(stderr, "\n");
-        }
-    }
-  }
-  if (s.err_host[1] != 0) {
-    HIPC(hipMemsetAsync(c->rabort, 0, 64, s.sc));
-    HIPC(hipStreamSynchronize(s.sc));
-    resident_give_up(c, "a tile waited 1 s for a neighbour: not every tile was running at once");
-    return LBM_OK;
-  }
-  c->cur ^= 1;
-  *done = true;
-  return LBM_OK;
+size_t regtile_mail_bytes(const lbm_ctx* c) {
+  return (size_t)c->tplan.ntx * c->tplan.nty * 2 * (size_t)lbm::regtile_box(c->tplan.ty);
 }
 
-// ---- register tiles ACROSS SLABS (SURVEY 8 f1, the multi-GPU half): every slab keeps its rows in the registers of its
-// own GPU for the whole run, and the granules that leave a slab through its bottom / top edge go straight into the
-// neighbouring slab's mailboxes (lbm_regtile.hip.h, kRegSlab) -- over xGMI when that slab lives on another GPU.  Same
-// tiling on every slab (equal slabs, 64-column tiles of ty rows); the slabs of one device go in ONE launch (their tiles
-// wait for each other, so they must be resident together).  Contexts whose neighbours can store into each other's
-// memory: slabs of one process (copy and peer-to-peer contexts: pointers, peer access across devices), and one process
-// per GPU with peer-to-peer halos (hipIpc mappings, handles in the halo block; needs the communicator, through which the
-// ranks agree after every run whether anybody gave up).
-int regtile_slab_count(const lbm_ctx* c) { return c->rank_mode ? c->nranks : (int)c->slabs.size(); }
-
-bool regtile_slabs_possible(const lbm_ctx* c) {
-  if (c->exchange != LBM_EXCHANGE_P2P && c->exchange != LBM_EXCHANGE_COPY) return false;
-  // (ranks without a communicator cannot agree on whether anybody gave up: the streaming kernels, unless a test that adds up
-  // the ranks' results itself says otherwise)
-  static const bool trust = getenv("LBM_REGTILE_SLABS_NO_AGREEMENT") && atoi(getenv("LBM_REGTILE_SLABS_NO_AGREEMENT"));
-  if (c->rank_mode && c->nranks > 1 && ((c->no_comm && !trust) || c->exchange != LBM_EXCHANGE_P2P)) return false;
-  const int n = regtile_slab_count(c);
-  return c->p.nx % 64 == 0 && n >= 1 && c->p.ny % n == 0;
-}
-
-// Tiling: as for a lattice alone (as few rows per wave as fit, on at most half the CUs where possible), counted per device.
-bool plan_regtile_slabs(lbm_ctx* c) {
-  c->splan.ty = 0;
-  if (!regtile_slabs_possible(c)) return false;
-  const char* off = getenv("LBM_REGTILE_SLABS");
-  if (off && atoi(off) == 0) return false;
-  const int nyl = c->p.ny / regtile_slab_count(c);
-  int per_dev = 1;
-  for (auto& a : c->slabs) {
-    int n = 0;
-    for (auto& b : c->slabs) n += (b.dev == a.dev) ? 1 : 0;
-    per_dev = std::max(per_dev, n);
-  }
-  // (development: LBM_REGTILE_SLAB_TILING = rows per tile x 10 + rows per wave, as the `regtile` option of a lone lattice)
-  const int forced = getenv("LBM_REGTILE_SLAB_TILING") ? atoi(getenv("LBM_REGTILE_SLAB_TILING")) : 0;
-  int ty = 0, r = 0;
-  if (forced > 0) {
-    ty = forced / 10; r = forced % 10;
-    if (!(r == 1 || r == 2 || r == 4) || ty < r || ty % r != 0 || ty / r > 16 || nyl % ty != 0 ||
-        (long)per_dev * (c->p.nx / 64) * (nyl / ty) > (long)c->ncu) return false;
-  } else if (!regtile_default_tiling(c, nyl, per_dev, &ty, &r)) return false;
-  c->splan.ty = ty; c->splan.r = r; c->splan.nw = ty / r; c->splan.ntx = c->p.nx / 64; c->splan.nty = nyl / ty; c->splan.bpc = 0;
-  return true;
-}
-
-typedef void (*regtile_slabs_fn)(const lbm::RegTileArgs*);
-regtile_slabs_fn regtile_slabs_force_kernel(int r, bool fast, bool async) {
-  constexpr int AS_ = lbm::kRegAsync, FO_ = lbm::kRegForce, SL_ = lbm::kRegSlab;
-  if (async && r == 4) return fast ? lbm::lbm_regtile_slabs<4, SL_ | FO_ | AS_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | FO_ | AS_>;
-  if (async && r == 2) return fast ? lbm::lbm_regtile_slabs<2, SL_ | FO_ | AS_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | FO_ | AS_>;
-  switch (r) {
-    case 4: return fast ? lbm::lbm_regtile_slabs<4, SL_ | FO_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | FO_>;
-    case 2: return fast ? lbm::lbm_regtile_slabs<2, SL_ | FO_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | FO_>;
-    default: return fast ? lbm::lbm_regtile_slabs<1, SL_ | FO_ | 1> : lbm::lbm_regtile_slabs<1, SL_ | FO_>;
-  }
-}
-regtile_slabs_fn regtile_slabs_kernel(int r, bool fast, bool async, bool snap) {
-  constexpr int AS_ = lbm::kRegAsync, SN_ = lbm::kRegSnap, SL_ = lbm::kRegSlab;
-  if (snap) {
-    if (async && r == 4) return fast ? lbm::lbm_regtile_slabs<4, SL_ | SN_ | AS_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | SN_ | AS_>;
-    if (async && r == 2) return fast ? lbm::lbm_regtile_slabs<2, SL_ | SN_ | AS_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | SN_ | AS_>;
-    switch (r) {
-      case 4: return fast ? lbm::lbm_regtile_slabs<4, SL_ | SN_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | SN_>;
-      case 2: return fast ? lbm::lbm_regtile_slabs<2, SL_ | SN_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | SN_>;
-      default: return fast ? lbm::lbm_regtile_slabs<1, SL_ | SN_ | 1> : lbm::lbm_regtile_slabs<1, SL_ | SN_>;
-    }
-  }
-  if (async && r == 4) return fast ? lbm::lbm_regtile_slabs<4, SL_ | AS_ | 1> : lbm::lbm_regtile_slabs<4, SL_ | AS_>;
-  if (async && r == 2) return fast ? lbm::lbm_regtile_slabs<2, SL_ | AS_ | 1> : lbm::lbm_regtile_slabs<2, SL_ | AS_>;
-  switch (r) {
-    case 4: return fast ? lbm::lbm_regtile_slabs<4, SL_ | 1> : lbm::lbm_regtile_slabs<4, SL_>;
-    case 2: return fast ? lbm::lbm_regtile_slabs<2, SL_ | 1> : lbm::lbm_regtile_slabs<2, SL_>;
-    default: return fast ? lbm::lbm_regtile_slabs<1, SL_ | 1> : lbm::lbm_regtile_slabs<1, SL_>;
-  }
-}
-
-size_t regtile_slab_mail_bytes(const lbm_ctx* c) {
-  return (size_t)c->splan.ntx * c->splan.nty * 2 * (size_t)lbm::regtile_box(c->splan.ty);
-}
-
-// A slab's mail area.  Uncached device memory, like the peer-to-peer halo blocks: a neighbour on another GPU stores into it
-// behind this GPU's L2 (LBM_REGTILE_MAIL_CACHED=1: ordinary device memory, to measure what that costs on one GPU).
-int regtile_slab_mail_alloc(lbm_ctx* c, Slab& s) {
+// A slab's mail area.  Uncached device memory: the granules are written once and read once, by another CU, and every
+// access is sc1 anyway -- without the L2 allocation a hand-off is shorter (1024x1024: 4.14 -> 3.48 us per step, found when
+// the slabs' mail areas, uncached for the sake of stores from other GPUs, ran faster than a lone lattice's); a slab's
+// neighbour on another GPU stores into it behind this GPU's L2.  A lattice alone takes ordinary device memory where the
+// device refuses uncached memory; slabs do not (LBM_REGTILE_MAIL_CACHED=1: ordinary device memory, to measure what that costs).
+int regtile_mail_alloc(lbm_ctx* c, Slab& s) {
   if (s.tmail) return LBM_OK;
   HIPC(hipSetDevice(s.dev));
-  const size_t bytes = regtile_slab_mail_bytes(c);
+  const size_t bytes = regtile_mail_bytes(c);
   static const bool cached = getenv("LBM_REGTILE_MAIL_CACHED") && atoi(getenv("LBM_REGTILE_MAIL_CACHED"));
   hipError_t e = cached ? hipMalloc((void**)&s.tmail, bytes) : hipExtMallocWithFlags((void**)&s.tmail, bytes, hipDeviceMallocUncached);
+  if (e != hipSuccess && c->exchange == 0) {
+    (void)hipGetLastError();
+    e = hipMalloc((void**)&s.tmail, bytes);
+  }
   if (e != hipSuccess) { (void)hipGetLastError(); s.tmail = nullptr; return fail(LBM_EHIP, "cannot allocate the mail area of a slab: %s", hipGetErrorString(e)); }
   HIPC(hipMemset(s.tmail, 0, bytes));
   HIPC(hipDeviceSynchronize());
@@ -484,7 +314,8 @@ int regtile_slab_mail_alloc(lbm_ctx* c, Slab& s) {
   return LBM_OK;
 }
 
-void regtile_slabs_free(lbm_ctx* c) {
+// Every buffer of the register tiles: a new tiling (option "regtile") starts without them.
+void regtile_free(lbm_ctx* c) {
   for (auto& s : c->slabs) {
     (void)hipSetDevice(s.dev);
     for (int side = 0; side < 2; ++side) {
@@ -501,32 +332,31 @@ void regtile_slabs_free(lbm_ctx* c) {
   c->rtable = c->rtable_dev = nullptr;
 }
 
-bool regtile_slabs_usable(const lbm_ctx* c) {
-  if (c->splan.ty <= 0 || c->resident_broken || (c->variant & 8) != 0 || !(c->engine == 0 || c->engine == 3)) return false;
-  if (!regtile_slabs_possible(c)) return false;
-  if (c->rank_mode && c->nranks > 1) {
-    if (!c->p2p_connected) return false;
-    for (int side = 0; side < 2; ++side) if (!c->slabs[0].tmail_nb[side]) return false;
-  }
-  return true;
-}
-
-int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const SnapPlan* sn) {
+// A run of the register tiles, a lattice alone (one device group of one slab) or the slabs of a context.  *done: the steps
+// ran; false with LBM_OK: nothing was queued or the tiles gave up with the lattice untouched -- the caller runs the streaming
+// kernels.
+int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   *done = false;
-  const auto& t = c->splan;
+  const bool lone = c->exchange == 0;
+  const auto& t = c->tplan;
   const int ns = (int)c->slabs.size(), ntiles = t.ntx * t.nty;
-  const bool fast = (c->variant & lbm::kFastMath) != 0;
+  const bool fast = (c->variant & lbm::kFastMath) != 0, async = c->regtile_async != 0;
+  const bool fk = k.nb > 0 && k.force_tiles;            // lbm_run_forces: the kRegForce flavour, with its larger LDS
+  const int flavour = fk ? lbm::kRegForce : k.snap ? lbm::kRegSnap : 0;
+  auto kernel = [&](int fl) {
+    return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
+                : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
+  };
   const dim3 block(64 * t.nw);
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const regtile_slabs_fn fn0 = regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, false);
-  const bool fk = c->fplan && c->fplan->in_kernel;
-  const regtile_slabs_fn fn = fk ? regtile_slabs_force_kernel(t.r, fast, c->regtile_async != 0)
-                                 : sn ? regtile_slabs_kernel(t.r, fast, c->regtile_async != 0, true) : fn0;
   const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : shm;
+  static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run
+  const bool stats = lone && want_stats;
   int rc;
-  // device groups: the local slabs in the order of their devices' first appearance
-  std::vector<int> order, gstart;          // order[k] = slab index; gstart[g] = first k of group g (+ end)
-  {
+  // device groups: the local slabs in the order of their devices' first appearance (found once)
+  auto& order = c->tplan.order;            // order[k] = slab index; gstart[g] = first k of group g (+ end)
+  auto& gstart = c->tplan.gstart;
+  if (gstart.empty()) {
     std::vector<bool> taken(ns, false);
     for (int i = 0; i < ns; ++i) {
       if (taken[i]) continue;
@@ -536,33 +366,32 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
     gstart.push_back((int)order.size());
   }
   const int ngroups = (int)gstart.size() - 1;
-  if (c->splan.bpc == 0) {           // first run: is every tile of every device resident at once?
+  auto lead = [&](int g) -> Slab& { return c->slabs[order[gstart[g]]]; };
+  if (t.bpc == 0) {                     // first run of this tiling: is every tile of every device resident at once?
     int worst = 1 << 30, most = 1;
     for (int g = 0; g < ngroups; ++g) {
-      Slab& l = c->slabs[order[gstart[g]]];
-      HIPC(hipSetDevice(l.dev));
-      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn0), l.dev, (int)block.x, shm);
-      if (n < 0) { c->splan.bpc = -1; snprintf(c->resident_why, sizeof(c->resident_why), "%s", lbm_last_error()); break; }
+      HIPC(hipSetDevice(lead(g).dev));
+      const int n = regtile_prepare(c, kernel(0), lead(g).dev, (int)block.x, shm);
+      if (n < 0) { c->tplan.bpc = -1; snprintf(c->resident_why, sizeof(c->resident_why), "%s", lbm_last_error()); break; }
       worst = std::min(worst, n); most = std::max(most, gstart[g + 1] - gstart[g]);
     }
-    if (c->splan.bpc == 0) {
-      c->splan.bpc = worst;
+    if (t.bpc == 0) {
+      c->tplan.bpc = worst;
       if ((long)worst * std::max(c->ncu, 1) < (long)ntiles * most) {
-        c->splan.bpc = -1;
-        snprintf(c->resident_why, sizeof(c->resident_why), "%d slabs x %d tiles of %d waves on one device, but it takes %d block(s) per CU on %d CUs at once", most, ntiles, t.nw, worst, c->ncu);
+        c->tplan.bpc = -1;
+        snprintf(c->resident_why, sizeof(c->resident_why), "%d slab(s) x %d tiles of %d waves on one device, but it takes %d block(s) per CU on %d CUs at once", most, ntiles, t.nw, worst, c->ncu);
       }
     }
   }
-  if (c->splan.bpc < 0) return fail(LBM_EINVAL, "register tiling across slabs not usable: %s", c->resident_why);
-  if (sn || fk)                                        // the snapshot / force flavour must be resident at once too (else: the split
+  if (t.bpc < 0) return fail(LBM_EINVAL, "register tiling%s not usable: %s", lone ? "" : " across slabs", c->resident_why);
+  if (flavour != 0)                                     // the snapshot / force flavour must be resident at once too (else: the split
     for (int g = 0; g < ngroups; ++g) {                 // run / the force kernel; lbm_run_forces has asked every rank already)
-      Slab& l = c->slabs[order[gstart[g]]];
-      HIPC(hipSetDevice(l.dev));
-      const int n = regtile_prepare(c, reinterpret_cast<const void*>(fn), l.dev, (int)block.x, shm_run);
+      HIPC(hipSetDevice(lead(g).dev));
+      const int n = regtile_prepare(c, kernel(flavour), lead(g).dev, (int)block.x, shm_run);
       if (n < 0 || (long)n * std::max(c->ncu, 1) < (long)ntiles * (gstart[g + 1] - gstart[g])) { (void)hipGetLastError(); return LBM_OK; }
     }
   // peer access between the devices of neighbouring slabs (one process; asked once)
-  if (!c->rank_mode && !c->splan_peers)
+  if (!c->rank_mode && !c->regtile_peers)
     for (int i = 0; i < ns; ++i)
       for (int d : {(i + ns - 1) % ns, (i + 1) % ns}) {
         const int a = c->slabs[i].dev, b = c->slabs[d].dev;
@@ -574,12 +403,12 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
         (void)hipGetLastError();
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(LBM_EHIP, "hipDeviceEnablePeerAccess(%d -> %d): %s", a, b, hipGetErrorString(e));
       }
-  c->splan_peers = true;
+  c->regtile_peers = true;
+  // buffers: the mail areas, the per-step tile sums, the groups' abort words, the table of arguments
   for (auto& s : c->slabs) {
-    if ((rc = regtile_slab_mail_alloc(c, s))) return rc;
-    HIPC(hipSetDevice(s.dev));
-    if (!s.ev_rt) HIPC(hipEventCreateWithFlags(&s.ev_rt, hipEventDisableTiming));
+    if ((rc = regtile_mail_alloc(c, s))) return rc;
     if (s.rpartials_cap < nsteps) {
+      HIPC(hipSetDevice(s.dev));
       long cap = std::max(1024L, s.rpartials_cap);
       while (cap < nsteps) cap *= 2;
       if (s.rpartials) HIPC(hipFree(s.rpartials));
@@ -590,30 +419,40 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
     if ((rc = ensure_sums(s, nsteps + 1))) return rc;
   }
   for (int g = 0; g < ngroups; ++g) {
-    Slab& l = c->slabs[order[gstart[g]]];
+    Slab& l = lead(g);
     if (!l.rabort) {
       HIPC(hipSetDevice(l.dev));
       HIPC(hipMalloc((void**)&l.rabort, 64));
-      HIPC(hipMemset(l.rabort, 0, 64));
+      HIPC(hipMemsetAsync(l.rabort, 0, 64, l.sc));   // (in front of the group's launch on this stream)
+    }
+    if (!l.ev_rt && gstart[g + 1] - gstart[g] > 1) {
+      HIPC(hipSetDevice(l.dev));
+      HIPC(hipEventCreateWithFlags(&l.ev_rt, hipEventDisableTiming));
     }
   }
   if (!c->rtable) {
     HIPC(hipHostMalloc((void**)&c->rtable, sizeof(lbm::RegTileArgs) * ns, hipHostMallocPortable | hipHostMallocMapped));
     HIPC(hipHostGetDevicePointer((void**)&c->rtable_dev, c->rtable, 0));
   }
-  // tags: as for a lattice alone; every slab (every rank) counts the same runs, so all hold the same tag0.  Before the
-  // 31-bit tags would wrap the mail areas are cleared and the count starts over -- at the END of a run (below), behind the
-  // slab's own launch and in front of the all-reduce that closes the run: no rank is past that all-reduce before every rank
-  // has cleared, so no early mail of the next run can be wiped (late mail of THIS run that lands after the clearing carries
-  // a tag of the old count: never asked for again)
-  if ((unsigned long long)c->rtag + (unsigned long long)nsteps >= 0x7fffff00ull)
-    return fail(LBM_EINVAL, "a run of %d steps does not fit the mailbox tags left (split it)", nsteps);
-  const bool restart_tags = (unsigned long long)c->rtag + (unsigned long long)nsteps >= 0x60000000ull;
+  // Tags only ever grow (a freshly zeroed mailbox is valid for any tag >= 1); every slab (every rank) counts the same runs,
+  // so all hold the same tag0.  Before the 31-bit tags would wrap the mail areas are cleared and the count starts over.  A
+  // lattice alone clears them in front of the run that would wrap them.  Slabs clear at the END of the run that passes
+  // 0x60000000 (below), behind the slab's own launch and in front of the all-reduce that closes the run: no rank is past
+  // that all-reduce before every rank has cleared, so no early mail of the next run can be wiped (late mail of THIS run
+  // that lands after the clearing carries a tag of the old count: never asked for again)
+  const bool wraps = (unsigned long long)c->rtag + (unsigned long long)nsteps >= 0x7fffff00ull;
+  if (wraps && !lone) return fail(LBM_EINVAL, "a run of %d steps does not fit the mailbox tags left (split it)", nsteps);
+  if (wraps) {
+    HIPC(hipSetDevice(c->slabs[0].dev));
+    HIPC(hipMemsetAsync(c->slabs[0].tmail, 0, c->slabs[0].tmail_bytes, c->slabs[0].sc));
+    c->rtag = 1;
+  }
+  const bool restart_tags = !lone && (unsigned long long)c->rtag + (unsigned long long)nsteps >= 0x60000000ull;
   for (int g = 0; g < ngroups; ++g)
-    for (int k = gstart[g]; k < gstart[g + 1]; ++k) {
-      const int i = order[k];
+    for (int q = gstart[g]; q < gstart[g + 1]; ++q) {
+      const int i = order[q];
       Slab& s = c->slabs[i];
-      lbm::RegTileArgs& a = c->rtable[k];
+      lbm::RegTileArgs& a = c->rtable[q];
       a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
       a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = s.nyl;
       a.blocked = s.blocked; a.omega = c->p.omega;
@@ -622,10 +461,10 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
       a.ty = t.ty; a.ntx = t.ntx; a.nty = t.nty;
       a.nsteps = nsteps; a.tag0 = c->rtag;
       a.mail = s.tmail; a.mail_bytes = (unsigned)s.tmail_bytes;
-      a.partials = s.rpartials; a.abort_word = c->slabs[order[gstart[g]]].rabort;
-      a.fault = (getenv("LBM_REGTILE_FAULT") && i == 0) ? 1 : 0;
+      a.partials = s.rpartials; a.abort_word = lead(g).rabort;
+      a.fault = (getenv("LBM_REGTILE_FAULT") && i == 0) ? 1 : 0;   // (tests: a tile that never starts)
       a.stats = nullptr;
-      a.snap = sn ? sn->at[i] : nullptr; a.snap_stride = sn ? sn->stride[i] : 0; a.every = sn ? sn->every : 0;
+      a.snap = k.snap ? k.snap->at[i] : nullptr; a.snap_stride = k.snap ? k.snap->stride[i] : 0; a.every = k.snap ? k.snap->every : 0;
       a.density = c->p.density;
       a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
       if (c->rank_mode && c->nranks > 1) {
@@ -639,29 +478,39 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
       }
       a.nty_s = t.nty; a.nty_n = t.nty;
     }
-  c->rtag += (uint32_t)nsteps + 1u;
+  static unsigned long long* stats_buf = nullptr;
+  constexpr size_t kStatsWords = 1028 + 72;   // [0], [1]: the counts; [1028 ..]: the first wave to give up (lbm_regtile.hip.h, await)
+  if (stats) {
+    HIPC(hipSetDevice(c->slabs[0].dev));
+    if (!stats_buf) HIPC(hipMalloc((void**)&stats_buf, kStatsWords * 8));
+    HIPC(hipMemsetAsync(stats_buf, 0, kStatsWords * 8, c->slabs[0].sc));
+    c->rtable[0].stats = stats_buf;
+  }
+  c->rtag += (uint32_t)nsteps + 1u;   // (the last step's mail is sent too, and must never be taken for the next run's state 0)
   const auto wall0 = std::chrono::steady_clock::now();
   for (auto& s : c->slabs) {
     HIPC(hipSetDevice(s.dev));
-    s.err_host[1] = 0;
+    s.err_host[1] = 0;                // lbm_fold_steps stores the abort word here
     HIPC(hipEventRecord(s.ev_t0, s.sc));
   }
   for (int g = 0; g < ngroups; ++g) {
-    Slab& l = c->slabs[order[gstart[g]]];
+    Slab& l = lead(g);
+    const int n = gstart[g + 1] - gstart[g];
     HIPC(hipSetDevice(l.dev));
-    for (int k = gstart[g] + 1; k < gstart[g + 1]; ++k) HIPC(hipStreamWaitEvent(l.sc, c->slabs[order[k]].ev_t0, 0));
-    hipLaunchKernelGGL(fn, dim3(ntiles, gstart[g + 1] - gstart[g]), block, shm_run, l.sc, c->rtable_dev + gstart[g]);
+    for (int q = gstart[g] + 1; q < gstart[g + 1]; ++q) HIPC(hipStreamWaitEvent(l.sc, c->slabs[order[q]].ev_t0, 0));
+    if (lone) hipLaunchKernelGGL(regtile_kernel<false>(t.r, fast, async, flavour), dim3(ntiles), block, shm_run, l.sc, c->rtable[0]);
+    else hipLaunchKernelGGL(regtile_kernel<true>(t.r, fast, async, flavour), dim3(ntiles, n), block, shm_run, l.sc, c->rtable_dev + gstart[g]);
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(l.ev_rt, l.sc));
-    for (int k = gstart[g]; k < gstart[g + 1]; ++k) {
-      Slab& s = c->slabs[order[k]];
-      if (k > gstart[g]) HIPC(hipStreamWaitEvent(s.sc, l.ev_rt, 0));
+    if (n > 1) HIPC(hipEventRecord(l.ev_rt, l.sc));
+    for (int q = gstart[g]; q < gstart[g + 1]; ++q) {
+      Slab& s = c->slabs[order[q]];
+      if (q > gstart[g]) HIPC(hipStreamWaitEvent(s.sc, l.ev_rt, 0));
       hipLaunchKernelGGL(lbm::lbm_fold_steps, dim3(cdiv(nsteps, lbm::kBlock / 64)), dim3(lbm::kBlock), 0, s.sc,
                          s.rpartials, ntiles, nsteps, s.sums, l.rabort, s.err_host + 1);
       HIPC(hipGetLastError());
       if (fk) {
-        hipLaunchKernelGGL(lbm::lbm_fold_forces, dim3(cdiv(c->fplan->nval, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
-                           s.fpart, s.fnslots, nsteps, c->fplan->nb, s.sums + nsteps + 1);
+        hipLaunchKernelGGL(lbm::lbm_fold_forces, dim3(cdiv(k.nval, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
+                           s.fpart, s.fnslots, nsteps, k.nb, s.sums + nsteps + 1);
         HIPC(hipGetLastError());
       }
       HIPC(hipEventRecord(s.ev_t1, s.sc));
@@ -681,19 +530,30 @@ int run_regtile_slabs(lbm_ctx* c, int nsteps, float* av_vels, bool* done, const 
     hipLaunchKernelGGL(lbm::lbm_abort_to_sum, dim3(1), dim3(64), 0, s.sc, s.rabort, s.sums + nsteps);
     HIPC(hipGetLastError());
   }
-  rc = collect_sums(c, nsteps, av_vels, wall0, agree ? 1 : 0);
-  if (rc) return rc;
+  if ((rc = collect_sums(c, nsteps, av_vels, wall0, k, agree ? 1 : 0))) return rc;
+  if (stats) {
+    std::vector<unsigned long long> st(kStatsWords);
+    HIPC(hipMemcpy(st.data(), stats_buf, kStatsWords * 8, hipMemcpyDeviceToHost));
+    fprintf(stderr, "lbm_regtile: %d steps, %d waves: %llu waits found their mail missing (%.3f per wave and step), %llu extra fetches\n",
+            nsteps, ntiles * t.nw, st[0], (double)st[0] / ((double)nsteps * ntiles * t.nw), st[1]);
+    if (st[1028] != 0) {
+      fprintf(stderr, "lbm_regtile: the first wave to give up: tile %llu (of %d x %d) wave %llu row %llu, waiting for tag %llu (run's tag0 %u); tags it holds, lane: couriers / edge row\n",
+              st[1028] - 1, t.ntx, t.nty, st[1029], st[1030], st[1031], c->rtable[0].tag0);
+      for (int l : {0, 1, 2, 3, 31, 60, 61, 62, 63}) fprintf(stderr, "   lane %2d: %llu / %llu\n", l, st[1032 + l] >> 32, st[1032 + l] & 0xffffffffull);
+    }
+  }
   bool gave_up = false;
   for (auto& s : c->slabs) gave_up = gave_up || s.err_host[1] != 0;
   if (agree) gave_up = gave_up || c->slabs[0].sums_host[nsteps] != 0.0;
   if (gave_up) {
     for (int g = 0; g < ngroups; ++g) {
-      Slab& l = c->slabs[order[gstart[g]]];
+      Slab& l = lead(g);
       HIPC(hipSetDevice(l.dev));
       HIPC(hipMemsetAsync(l.rabort, 0, 64, l.sc));
       HIPC(hipStreamSynchronize(l.sc));
     }
-    resident_give_up(c, "a tile waited 1 s for a neighbour (register tiles across slabs): not every tile was running at once");
+    resident_give_up(c, lone ? "a tile waited 1 s for a neighbour: not every tile was running at once"
+                             : "a tile waited 1 s for a neighbour (register tiles across slabs): not every tile was running at once");
     return LBM_OK;
   }
   if (restart_tags) c->rtag = 1;
@@ -749,17 +609,17 @@ bool slab_wave_pays(const lbm_ctx* c, int rows, int K) {
 // The step loop with peer-to-peer halos: one stream per slab, no events, no host-side exchange.
 // Two-step launches carry the hand-off themselves (edge tiles first); single steps are bracketed
 // by a wait launch and a push launch.
-int run_p2p(lbm_ctx* c, int nsteps, float* av_vels) {
+int run_p2p(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (!c->p2p_connected) return fail(LBM_EINVAL, "peer-to-peer halos are not connected (lbm_p2p_connect)");
   const int nx = c->p.nx;
   const float a1 = c->p.density * c->p.accel / 9.f, a2 = c->p.density * c->p.accel / 36.f;
-  const bool pairs = !c->fplan && t2_eligible(c) && nsteps >= 2;   // (lbm_run_forces: one step per launch, forces behind each)
+  const bool pairs = k.nb == 0 && t2_eligible(c) && nsteps >= 2;   // (lbm_run_forces: one step per launch, forces behind each)
   const int ntx = nx / kT2X;
   const int push_grid = cdiv(nx, lbm::kBlock);
   int rc;
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
-  const bool march = !c->fplan && p2p_march_on(c) && nsteps >= slab_K(c);
+  const bool march = k.nb == 0 && p2p_march_on(c) && nsteps >= slab_K(c);
   if (march && (rc = check_march_partials(c, true))) return rc;   // (before anything is queued)
 
   auto push = [&](Slab& s, const float* lat, uint32_t seq, bool do_push) -> int {
@@ -901,7 +761,7 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels) {
       if ((rc = push(s, s.lat[c->cur ^ 1], seq, true))) return rc;   // the new edge rows, packed and pushed
     }
     c->cur ^= 1;
-    if (c->fplan && (rc = launch_forces(c, tt, q, nsteps))) return rc;
+    if (k.nb > 0 && (rc = launch_forces(c, tt, q, nsteps, k))) return rc;
   }
   const int ql = (li - 1) & 1;
   for (auto& s : c->slabs) {
@@ -913,7 +773,7 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels) {
     }
     HIPC(hipEventRecord(s.ev_t1, s.sc));
   }
-  return collect_sums(c, nsteps, av_vels, wall0);
+  return collect_sums(c, nsteps, av_vels, wall0, k);
 }
 
 }  // namespace

@@ -508,8 +508,8 @@ bool plan_regtile(lbm_ctx* c);    // resident engine, below
 bool plan_regtile_slabs(lbm_ctx* c);
 bool regtile_tiling_rule(int nx, int rows, int per_dev, int ncu, int* ty_out, int* r_out);
 struct Slab;
-int regtile_slab_mail_alloc(lbm_ctx* c, Slab& s);
-size_t regtile_slab_mail_bytes(const lbm_ctx* c);
+int regtile_mail_alloc(lbm_ctx* c, Slab& s);
+size_t regtile_mail_bytes(const lbm_ctx* c);
 typedef void (*wave_fn)(const lbm::WaveArgs);
 wave_fn wave_kernel(int K, bool slab, int C, int flavour);   // the lbm_wave instantiations, below
 bool march_slabs_setup(lbm_ctx* c);   // marching kernel across slabs, below
@@ -585,11 +585,11 @@ int finish_create(lbm_ctx* c, const int* obstacles, const float* cells) {
     if (exchanging && plan_regtile_slabs(c) && c->rank_mode && c->nranks > 1) {
       // one process per GPU: the neighbours find this slab's mail area through a hipIpc handle in its halo block
       Slab& s0 = c->slabs[0];
-      int rc = regtile_slab_mail_alloc(c, s0);
-      if (rc) { (void)hipGetLastError(); c->splan.ty = 0; }
+      int rc = regtile_mail_alloc(c, s0);
+      if (rc) { (void)hipGetLastError(); c->tplan.ty = 0; }
       else {
         hipIpcMemHandle_t h;
-        if (hipIpcGetMemHandle(&h, s0.tmail) != hipSuccess) { (void)hipGetLastError(); c->splan.ty = 0; }
+        if (hipIpcGetMemHandle(&h, s0.tmail) != hipSuccess) { (void)hipGetLastError(); c->tplan.ty = 0; }
         else HIPC(hipMemcpy(s0.comm_block + 4 * s0.halo_bytes + 512 + 192, &h, sizeof(h), hipMemcpyHostToDevice));
       }
     }

@@ -48,8 +48,6 @@
 namespace lbm {
 
 constexpr long long kResidentTimeoutTicks = 100000000LL;       // a wait for mail gives up after 1 s of the 100 MHz wall clock
-// timing experiments only (wrong results): LBM_RESIDENT_DEBUG=1 never waits for a tag, 2 also sends nothing
-constexpr int kResDebugNoWait = 64, kResDebugNoSend = 128;
 constexpr int kRegAsync = 4096;   // lbm_regtile: mail loads / stores of the loop as inline asm with counted s_waitcnt vmcnt(N)
 constexpr int kRegSlab = 8192;    // lbm_regtile: the lattice is a slab with neighbours -- the tile rows below its first and above its
                                   // last belong to OTHER slabs (same tiling), whose mailboxes live in their own mail areas
@@ -156,12 +154,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool SLAB = (MODE & kRegSlab) != 0;
   constexpr bool SNAP = (MODE & kRegSnap) != 0;
   constexpr bool FORCE = (MODE & kRegForce) != 0;
-  // timing experiments only (wrong results), LBM_RESIDENT_DEBUG: 1 = one pass over the inbox, no waiting; 2 = also no
-  // stores to other tiles; 3 = also no inbox loads at all; 4 = like 1, the stores issued but dropped by an empty buffer
-  // descriptor (what the instructions cost without their memory traffic); 5 = like 1, stores without sc1
-  constexpr bool DBG_NOWAIT = (MODE & kResDebugNoWait) != 0, DBG_NOSEND = (MODE & kResDebugNoSend) != 0, DBG_NOLOAD = (MODE & 256) != 0;
-  constexpr bool DBG_DROP = (MODE & 512) != 0, DBG_PLAIN = (MODE & 1024) != 0;
-  constexpr bool TRACE = (MODE & 2048) != 0;     // development: time stamps of one tile's waves (LBM_REGTILE_TRACE)
   // The mail of the loop issued and waited for BY HAND (R > 1): see "the asynchronous loop" below
   constexpr bool ASYNC = (MODE & kRegAsync) != 0 && R > 1;
   static_assert(R == 1 || R == 2 || R == 4, "rows per wave");
@@ -197,12 +189,11 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   // mailbox sections (byte offsets inside a box); the whole mail area is a few MB: 32-bit offsets behind one descriptor
   const unsigned oS = 0u, oN = 1024u, oW = 2048u, oE = 2048u + 16u * (unsigned)(TY + 2);
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(a.mail, 0, (int)a.mail_bytes, 0x00020000);
-  const auto rsrc_st = DBG_DROP ? __builtin_amdgcn_make_buffer_rsrc(a.mail, 0, 0, 0x00020000) : rsrc;
   // where the granules that leave through the tile's bottom / top edge (and the two corners on that side) are stored: this
   // slab's mail area, or the neighbouring slab's for the slab's first / last tile row (wave-uniform, fixed for the run)
   const bool south_out = SLAB && by == 0, north_out = SLAB && by == a.nty - 1;
-  const auto rsrc_s = south_out ? __builtin_amdgcn_make_buffer_rsrc(a.mail_s, 0, (int)a.mail_bytes_s, 0x00020000) : rsrc_st;
-  const auto rsrc_n = north_out ? __builtin_amdgcn_make_buffer_rsrc(a.mail_n, 0, (int)a.mail_bytes_n, 0x00020000) : rsrc_st;
+  const auto rsrc_s = south_out ? __builtin_amdgcn_make_buffer_rsrc(a.mail_s, 0, (int)a.mail_bytes_s, 0x00020000) : rsrc;
+  const auto rsrc_n = north_out ? __builtin_amdgcn_make_buffer_rsrc(a.mail_n, 0, (int)a.mail_bytes_n, 0x00020000) : rsrc;
   using ToOwn = std::integral_constant<int, 0>;
   using ToSouth = std::integral_constant<int, 1>;
   using ToNorth = std::integral_constant<int, 2>;
@@ -213,8 +204,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     constexpr int TO = decltype(to)::value;
     rt_u4 g;
     g.x = __float_as_uint(v0); g.y = __float_as_uint(v1); g.z = __float_as_uint(v2); g.w = tag;
-    if (DBG_NOSEND) return;
-    if constexpr (!SLAB || TO == 0) __builtin_amdgcn_raw_buffer_store_b128(g, rsrc_st, voff, soff, DBG_PLAIN ? 0 : 16);      // aux 16 = sc1
+    if constexpr (!SLAB || TO == 0) __builtin_amdgcn_raw_buffer_store_b128(g, rsrc, voff, soff, 16);      // aux 16 = sc1
     else __builtin_amdgcn_raw_buffer_store_b128(g, TO == 1 ? rsrc_s : rsrc_n, voff, soff, 17);
   };
   auto load = [&](unsigned voff, unsigned soff) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 16); };
@@ -361,7 +351,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   struct Mail { rt_u4 g, e, x; };
   auto fetch = [&](auto rc, unsigned pb, Mail& m) {
     constexpr int r = decltype(rc)::value;
-    if (DBG_NOLOAD) return;
     m.g = load(rv_voff, mybox + pb + 16u * r);
     if (r == 0) m.e = load(first_voff, mybox + oS + pb);
     if (r == R - 1) {
@@ -378,22 +367,12 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     return __all(ok) != 0;
   };
   unsigned nmiss = 0u, nspin = 0u;
-  // development trace (a.stats != nullptr): shader-clock stamps of the waves of one tile over four steps,
-  // stats[2 + ((wave * 4 + step - s0) * 16 + slot)]
-  const bool tracing = TRACE && a.stats != nullptr && tile == (int)a.stats[2];
-  const int trace_s0 = (TRACE && a.stats != nullptr) ? (int)a.stats[3] : 0;
-  auto stamp = [&](int s, int slot) {
-    if constexpr (TRACE) {
-      if (tracing && s >= trace_s0 && s < trace_s0 + 4 && lane == 0)
-        a.stats[4 + ((w * 4 + (s - trace_s0)) * 16 + slot)] = __builtin_amdgcn_s_memtime();
-    }
-  };
   // Wait until the mail of a row is there.  With several rows per wave the fetch that was started a row earlier
   // usually has it, and if not it is fetched again.  A one-row wave (the small decks: the step IS the hand-off) polls
   // with THREE loads in flight, a hundred cycles apart, each tested as it returns: the hand-off is seen one load
   // latency (~2000 cycles through memory) after the granule became visible, not up to two.
   auto await = [&](auto rc, unsigned pb, uint32_t want, Mail& m) {
-    if (DBG_NOLOAD || DBG_NOWAIT || arrived(rc, m, want)) return;
+    if (arrived(rc, m, want)) return;
     const long long t0 = wall_clock64();
     ++nmiss;
     for (;;) {
@@ -586,7 +565,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
         if (*lds_abort != 0u) { aborted = true; break; }
-        stamp(s, 0);
         if (s > 1 && tid < 64) {                       // speed sum of step s-1 (DPP adds: the LDS-permute form cost wave 0 ~1300 cycles at
           float v = (lane < nw) ? red[par * 16 + lane] : 0.f;    // the head of EVERY step, and the tile's barrier waits for its slowest wave)
           v = wave_sum_dpp(v);
@@ -603,7 +581,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           using RC = std::integral_constant<int, r>;
           Slot& m = slot[i % D];
           __builtin_amdgcn_s_setprio(3 - (i * 4) / R);
-          stamp(s, 1 + 3 * i);
           // ---- wait for this row's mail: all but the N(i) youngest operations are done
           constexpr int N = [] { int n = 0; for (int k = 1; k < D; ++k) { int j = (((i + k) % R) + R) % R; n += (j == 0 || j == R - 1) ? 2 : 1; }
                                   for (int k = 1; k <= D; ++k) { int j = (((i - k) % R) + R) % R; n += (j == 0 || j == R - 1) ? 3 : 1; } return n; }();
@@ -612,7 +589,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           if (firststep) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           aretire(RC{}, std::integral_constant<int, N>{}, m);
           if (!aarrived(RC{}, m, want)) aslow(RC{}, pb, want, m);
-          stamp(s, 2 + 3 * i);
           // ---- unpack: couriers -> edge lanes; the row below / above the tile
           const float m0 = __uint_as_float(m.g.x);
           const float m1w = rt_row_shl<1>(m.g.y), m1e = rt_row_shr<1>(m.g.y);
@@ -694,13 +670,11 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
             }
           }
           __builtin_amdgcn_sched_barrier(0);           // one row at a time
-          stamp(s, 3 + 3 * i);
         };
         one(std::integral_constant<int, 0>{});
         one(std::integral_constant<int, 1>{});
         if constexpr (R > 2) { one(std::integral_constant<int, 2>{}); one(std::integral_constant<int, 3>{}); }
         if (!laststep) publish_lds(s & 1);
-        stamp(s, 13);
         sp = wave_sum_dpp(sp);
         if (lane == 0) red[(s & 1) * 16 + w] = sp;
         if (sample) snap_left = snap_next();
@@ -753,7 +727,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
     if (*lds_abort != 0u) { aborted = true; break; }                  // (set before the barrier: every wave leaves here together)
-    stamp(s, 0);
     if (s > 1 && tid < 64) {                       // speed sum of step s-1
       float v = (lane < nw) ? red[par * 16 + lane] : 0.f;   // (written with parity (s-1)&1 at the end of step s-1)
       v = wave_sum_dpp(v);
@@ -777,10 +750,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     };
     auto do_row = [&](auto rc, auto next_c, auto prev_c, Mail& m, Mail& mnext, float (&lo)[3], float (&hi)[3]) {
       constexpr int r = decltype(rc)::value, rnext = decltype(next_c)::value, rprev = decltype(prev_c)::value;
-      const int ord = down ? R - 1 - r : r;
-      stamp(s, 1 + 3 * ord);
       await(rc, pb, want, m);
-      stamp(s, 2 + 3 * ord);
       if constexpr (rprev >= 0) { if (!laststep) send_stored(prev_c); }   // (behind the wait: see the note on the stores above)
       if (r == 0) {
         if (first) { lo[0] = __uint_as_float(m.e.x); lo[1] = __uint_as_float(m.e.y); lo[2] = __uint_as_float(m.e.z); }
@@ -827,7 +797,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       else { f[r][0] = p[0]; f[r][1] = p[1]; f[r][3] = p[3]; }
       __builtin_amdgcn_sched_barrier(0);             // one row at a time: interleaving the rows costs more registers than the tile has to spare
       if constexpr (rnext < 0) { if (!laststep) send_row(rc, tagn, pbn, p); }   // the wave's last row of the step sends at once
-      stamp(s, 3 + 3 * ord);
     };
     // the wave's rows in order i = 0 .. R-1: row i going up, row R-1-i going down
     auto sweep = [&](auto up_c) {
@@ -858,7 +827,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         sv[0] = keep[0]; sv[1] = keep[1]; sv[2] = keep[2];
       };
       Mail ma, mb;
-      if (DBG_NOLOAD) { blank(ma); blank(mb); }
       one(I0{}, pre, ma);
       if constexpr (R > 1) one(I1{}, ma, mb);
       if constexpr (R > 2) { one(I2{}, mb, ma); one(I3{}, ma, mb); }
@@ -868,7 +836,6 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     };
     if (!down) sweep(std::true_type{}); else sweep(std::false_type{});
     if (!laststep) publish_lds(s & 1);
-    stamp(s, 13);
     sp = wave_sum_dpp(sp);
     if (lane == 0) red[(s & 1) * 16 + w] = sp;
     if (sample) snap_left = snap_next();

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """us/step of lbm_regtile on a shipped deck for a list of tilings (rows per tile x 10 + rows per wave; none = the
-default), best of three runs by HIP events.  LBM_RESIDENT_DEBUG=1/2/3 selects the timing-only variants (wrong
-results), LBM_REGTILE_STATS=1 prints how many polls found their mail missing.
+default), best of three runs by HIP events.  LBM_REGTILE_STATS=1 prints how many polls found their mail missing.
     python tools/regtile_timing.py deck steps [tiling ...]"""
 import os
 import sys
@@ -29,5 +28,5 @@ for t in tilings:
             g, w = lat.last_run_ms()
             best = min(best, g)
         assert int(lat.info("engine_last")) == 3
-        print(f"dbg={os.environ.get('LBM_RESIDENT_DEBUG', '0')} async={int(lat.info('regtile_async'))} {deck} regtile {int(lat.info('regtile'))} "
+        print(f"async={int(lat.info('regtile_async'))} {deck} regtile {int(lat.info('regtile'))} "
               f"{best * 1e3 / steps:.3f} us/step  {p.nx * p.ny * steps / best / 1e6:.1f} GLUPS", flush=True)
