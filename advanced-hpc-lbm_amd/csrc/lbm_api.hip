@@ -1135,7 +1135,8 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
   }
   if (!strcmp(key, "time_block")) {
     if (value != 1 && value != 2 && value != 4 && value != 6 && value != 8) return fail(LBM_EINVAL, "time_block must be 1, 2, 4, 6 or 8");
-    if (value != c->time_block) { c->wave_rows = 0; c->wave_capacity = 0; if (c->march_slabs == 0) c->march_slabs = -1; }   // (what the slabs can march depends on K)
+    // (what the slabs can march depends on K, either way: a yes for K = 4 is no yes for K = 8, whose slabs need 32 rows)
+    if (value != c->time_block) { c->wave_rows = 0; c->wave_capacity = 0; c->march_slabs = -1; }
     c->time_block = (int)value;
     c->engine = 1;
     return LBM_OK;
