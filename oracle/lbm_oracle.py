@@ -179,6 +179,117 @@ class ReferenceStrict:
         return self.lib.calc_reynolds(rp, cells.ctypes.data, obstacles.ctypes.data)
 
 
+
+# ---------------------------------------------------------------- row bands and chunks
+# One D2Q9 step of a row reads only the rows either side of it, so K steps of rows [j0, j1) depend on rows
+# [j0 - K, j1 + K) alone.  Those rows, treated as a periodic lattice of their own, advance rows [j0, j1) exactly as the
+# whole lattice would: the wrong values the band's own wrap brings in move one row per step and reach row j0 - K + K =
+# j0 only after K steps.  The cell arithmetic is the oracle's (orc_sweep_rows_ / orc_accelerate_row_), so a band equals
+# Oracle.run of the whole lattice bit for bit, in either flavour, for a cost that does not grow with ny.
+
+def band_rows(ny: int, j0: int, j1: int, K: int) -> np.ndarray:
+    """Global rows j0 - K .. j1 + K - 1, wrapped into [0, ny)."""
+    return np.arange(j0 - K, j1 + K) % ny
+
+
+def band_param(prm: OrcParam, rows: int) -> OrcParam:
+    return OrcParam(prm.nx, rows, prm.maxIters, prm.reynolds_dim, prm.density, prm.accel, prm.omega)
+
+
+def _oracle_for(dtype):
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype must be float32 (the strict float oracle) or float64")
+    return Oracle("strict")
+
+
+def run_band(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, j0: int, j1: int, K: int,
+             dtype=np.float64) -> np.ndarray:
+    """Rows [j0, j1) (taken modulo ny; 0 <= j0 < ny, j0 < j1 <= j0 + ny) of the lattice `cells` (ny, nx, 9) after K
+    steps of the strict oracle in `dtype` (float32: the reference's float arithmetic; float64: the double oracle from
+    the same float input).  Only rows j0 - K .. j1 + K - 1 are read and stepped; where those would cover the lattice
+    the whole lattice is run instead.  Returns (j1 - j0, nx, 9) in `dtype`."""
+    ny, nx = prm.ny, prm.nx
+    if not (0 <= j0 < ny and j0 < j1 <= j0 + ny and K >= 0):
+        raise ValueError(f"band [{j0}, {j1}) of {K} steps on {ny} rows")
+    orc = _oracle_for(dtype)
+    out_rows = np.arange(j0, j1) % ny
+    if 2 * K + (j1 - j0) >= ny:
+        a = np.ascontiguousarray(cells, dtype=dtype).copy()
+        if K:
+            orc.run(prm, a, np.ascontiguousarray(obstacles, dtype=np.int32), K)
+        return a[out_rows]
+    rows = band_rows(ny, j0, j1, K)
+    a = np.ascontiguousarray(cells[rows], dtype=dtype)
+    b = np.empty_like(a)
+    ob = np.ascontiguousarray(obstacles[rows], dtype=np.int32)
+    bp = band_param(prm, len(rows))
+    acc = np.nonzero(rows == ny - 2)[0]          # the accelerate row, where the band holds it (at most once here)
+    for _ in range(K):
+        for r in acc:
+            orc.accelerate_row(bp, a, ob, int(r))
+        orc.sweep_rows(bp, a, b, ob, 0, len(rows))
+        a, b = b, a
+    return a[K:K + (j1 - j0)].copy()
+
+
+def step_chunks(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, rows_per_chunk: int, dtype=np.float64):
+    """One whole-lattice step (accelerate + sweep) of the strict oracle in `dtype`, chunk by chunk: yields
+    (r0, r1, new rows [r0, r1) as (r1 - r0, nx, 9) in dtype, speed sum of the chunk, fluid cells of the chunk).  Each
+    chunk reads its rows and one row either side; nothing lattice-sized is allocated.  The speed sum adds up the rows' sums
+    (each in dtype, over nx cells) in double, so that in float it carries the rounding of one row's sum, not of a lattice's."""
+    ny = prm.ny
+    if rows_per_chunk < 1:
+        raise ValueError("rows_per_chunk must be >= 1")
+    orc = _oracle_for(dtype)
+    for r0 in range(0, ny, rows_per_chunk):
+        r1 = min(ny, r0 + rows_per_chunk)
+        rows = band_rows(ny, r0, r1, 1)
+        a = np.ascontiguousarray(cells[rows], dtype=dtype)
+        b = np.empty_like(a)
+        ob = np.ascontiguousarray(obstacles[rows], dtype=np.int32)
+        bp = band_param(prm, len(rows))
+        for r in np.nonzero(rows == ny - 2)[0]:   # in a halo row, or the chunk's own (or both, on a lattice of few rows)
+            orc.accelerate_row(bp, a, ob, int(r))
+        tot, cnt = 0.0, 0
+        for r in range(1, len(rows) - 1):         # (a row's speeds summed in dtype, the rows in double)
+            t, n = orc.sweep_rows(bp, a, b, ob, r, r + 1)
+            tot += float(t)
+            cnt += n
+        yield r0, r1, b[1:len(rows) - 1], tot, cnt
+
+
+def step_chunked(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, rows_per_chunk: int, dtype=np.float64,
+                 visit=None):
+    """step_chunks gathered: (new lattice in dtype -- or None where `visit(r0, r1, rows)` takes each chunk instead --,
+    speed sum over all fluid cells added up in double, fluid cells).  speed sum / fluid cells is the step's av_vels
+    entry; in float64 it is the double oracle's up to the order of the double additions."""
+    out = None if visit is not None else np.empty(cells.shape, dtype=dtype)
+    tot, cnt = 0.0, 0
+    for r0, r1, new, t, n in step_chunks(prm, cells, obstacles, rows_per_chunk, dtype):
+        if visit is None:
+            out[r0:r1] = new
+        else:
+            visit(r0, r1, new)
+        tot += t
+        cnt += n
+    return out, tot, cnt
+
+
+def av_velocity_chunked(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, rows_per_chunk: int):
+    """(speed sum, fluid cells) of the lattice `cells` as the double oracle's av_velocity sees it, chunk by chunk:
+    sum / cells is its av_velocity up to the order of the double additions."""
+    orc = Oracle("strict")
+    tot, cnt = 0.0, 0
+    for r0 in range(0, prm.ny, rows_per_chunk):
+        r1 = min(prm.ny, r0 + rows_per_chunk)
+        ob = np.ascontiguousarray(obstacles[r0:r1], dtype=np.int32)
+        n = int((ob == 0).sum())
+        if n:
+            tot += orc.av_velocity(band_param(prm, r1 - r0), np.ascontiguousarray(cells[r0:r1], dtype=np.float64), ob) * n
+            cnt += n
+    return tot, cnt
+
+
 # ---------------------------------------------------------------- text formats
 
 def read_params(path: str) -> OrcParam:
