@@ -37,7 +37,7 @@ EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_P2P = 0, 1, 2, 3
 ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
-    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_set_bodies", "lbm_run_forces",
+    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
     "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
@@ -89,6 +89,7 @@ def load_library():
     lib.lbm_num_slabs.argtypes = [vp]
     lib.lbm_run.argtypes = [vp, C.c_int, vp]
     lib.lbm_run_sampled.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    lib.lbm_run_mean.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_set_bodies.argtypes = [vp, vp, C.c_int]
     lib.lbm_run_forces.argtypes = [vp, C.c_int, vp, vp]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
@@ -217,6 +218,27 @@ class Lattice:
             torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
         _check(self._lib.lbm_run_sampled(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, fields
+
+    def run_mean(self, nsteps: int, every: int = 1, out=None):
+        """lbm_run with the time-averaged fields over the sample steps every, 2 every, ...: returns (av_vels[nsteps], mean)
+        where mean is (rows, nx, 4) float32 (u_x, u_y, |u|, pressure; the float sum of run_sampled's snapshots in step
+        order, divided by their number), a numpy array -- or `out`, a contiguous float32 torch tensor of that shape on
+        the context's GPU, filled there."""
+        shape = (self._local_rows(), self.params.nx, 4)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        if out is None:
+            mean = np.empty(shape, dtype=np.float32)
+            ptr = mean.ctypes.data
+        else:
+            import torch
+            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
+                    or not out.is_contiguous() or tuple(out.shape) != shape):
+                raise LbmError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
+            mean = out
+            ptr = out.data_ptr()
+            torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        _check(self._lib.lbm_run_mean(self._ctx, nsteps, av.ctypes.data, every, ptr))
+        return av, mean
 
     def set_bodies(self, body, nbodies: int):
         """Labels blocked cells 1..nbodies (0: not counted) for run_forces: body is int[ny, nx] over the global lattice

@@ -236,6 +236,7 @@ struct lbm_ctx {
   int engine_last = 0;         // what the last lbm_run used: 1 streaming, 3 resident in registers
   int samples_in_kernel = 0;   // 1: the snapshots of the last lbm_run_sampled came from the register tiles
   int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
+  int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
   int nbodies = 0;             // lbm_set_bodies (0: none)
   // obstacle map of the local rows and one row either side (global rows keep_row0 .. keep_row0 + keep_rows - 1, taken
   // modulo ny), for the bodies' direction masks
@@ -615,8 +616,9 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 
 static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
 
-// The step loop of lbm_run.  k.snap (lbm_run_sampled): ONLY the register tiles are tried, with the snapshots in the kernel;
-// if they did not run (samples_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
+// The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean): ONLY the register tiles are tried, with the
+// snapshots (the sums) in the kernel; if they did not run (samples_in_kernel / mean_in_kernel stays 0), nothing has been
+// stepped and the caller runs the steps in pieces.
 static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind()) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
@@ -637,7 +639,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
     if (rr) return rr;
     if (done) {
       c->engine_last = 3;
-      if (k.snap) c->samples_in_kernel = 1;
+      if (k.snap && k.mean) c->mean_in_kernel = 1;
+      else if (k.snap) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
       return LBM_OK;
     }
@@ -797,6 +800,39 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
 
 extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) { return lbm_run_sampled(c, nsteps, av_vels, 0, nullptr); }
 
+// Output of lbm_run_sampled / lbm_run_mean (`what`: the argument's name): host memory, or device memory -- then of the device
+// that holds every slab, written in place.
+static int output_on_device(const lbm_ctx* c, const void* out, const char* what, bool* on_dev) {
+  *on_dev = false;
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeDevice) {
+    *on_dev = true;
+    for (auto& s : c->slabs)
+      if (s.dev != attr.device)
+        return fail(LBM_EINVAL, "%s is memory of device %d: device output needs every slab on that device (slab on %d)", what, attr.device, s.dev);
+  }
+  (void)hipGetLastError();      // (host memory unknown to HIP: an error the runtime remembers)
+  return LBM_OK;
+}
+
+// Before lbm_run_forces / lbm_run_mean queue anything: a rank context's ranks take the same path and fail together.  rc: this
+// rank's allocation result (`what` it was for); *in_kernel: would this rank use the register tiles -- on return, would every rank.
+// Returns what the call must return now, or LBM_OK.
+static int ranks_agree(lbm_ctx* c, int rc, bool* in_kernel, const char* what) {
+  if (!(c->rank_mode && c->slabs[0].comm != nullptr)) return rc;
+  // [0] ranks short of room, [1] ranks that would not use the tiles
+  Slab& s = c->slabs[0];
+  double v[2] = {rc ? 1.0 : 0.0, *in_kernel ? 0.0 : 1.0};
+  HIPC(hipSetDevice(s.dev));
+  HIPC(hipMemcpy(s.scratch_d, v, sizeof(v), hipMemcpyHostToDevice));
+  NCCLC(rccl::AllReduce(s.scratch_d, s.scratch_d, 2, rccl::kFloat64, rccl::kSum, s.comm, s.sc));
+  HIPC(hipStreamSynchronize(s.sc));
+  HIPC(hipMemcpy(v, s.scratch_d, sizeof(v), hipMemcpyDeviceToHost));
+  if (v[0] > 0.0) return rc ? rc : fail(LBM_ENOMEM, "another rank has no room for %s", what);
+  *in_kernel = *in_kernel && v[1] == 0.0;
+  return LBM_OK;
+}
+
 extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every, float* fields_out) {
   if (!c) return fail(LBM_EINVAL, "ctx is NULL");
   if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
@@ -815,17 +851,8 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
   if ((unsigned long long)m > (unsigned long long)(PTRDIFF_MAX / 4) / (unsigned long long)slot)
     return fail(LBM_EINVAL, "%d snapshots of %ld floats do not fit the address space", m, slot);
   bool on_dev = false;
-  {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, fields_out) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-      on_dev = true;
-      for (auto& s : c->slabs)
-        if (s.dev != attr.device)
-          return fail(LBM_EINVAL, "fields_out is memory of device %d: device output needs every slab on that device (slab on %d)", attr.device, s.dev);
-    }
-    (void)hipGetLastError();      // (host memory unknown to HIP: an error the runtime remembers)
-  }
   int rc;
+  if ((rc = output_on_device(c, fields_out, "fields_out", &on_dev))) return rc;
   if (regtile_is_next(c)) {
     // ---- in the kernel: straight into device output, or into one staging buffer per slab copied out after the run
     SnapPlan sp;
@@ -943,20 +970,7 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
     for (auto& s : c->slabs)
       if ((rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps))) break;
   }
-  if (c->rank_mode && c->slabs[0].comm != nullptr) {
-    // every rank takes the same path and fails together: [0] ranks short of room, [1] ranks that would not use the tiles
-    Slab& s = c->slabs[0];
-    double v[2] = {rc ? 1.0 : 0.0, in_kernel ? 0.0 : 1.0};
-    HIPC(hipSetDevice(s.dev));
-    HIPC(hipMemcpy(s.scratch_d, v, sizeof(v), hipMemcpyHostToDevice));
-    NCCLC(rccl::AllReduce(s.scratch_d, s.scratch_d, 2, rccl::kFloat64, rccl::kSum, s.comm, s.sc));
-    HIPC(hipStreamSynchronize(s.sc));
-    HIPC(hipMemcpy(v, s.scratch_d, sizeof(v), hipMemcpyDeviceToHost));
-    if (v[0] > 0.0) return rc ? rc : fail(LBM_ENOMEM, "another rank has no room for the force partials");
-    in_kernel = in_kernel && v[1] == 0.0;
-  } else if (rc) {
-    return rc;
-  }
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the force partials"))) return rc;
   RunKind k;
   k.nb = nb; k.nval = nval; k.force_tiles = in_kernel;
   if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
@@ -967,6 +981,96 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
     forces[k] = (float)acc;
   }
   return LBM_OK;
+}
+
+extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, float* mean_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
+  const int m = nsteps / every;
+  if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
+  if (!mean_out) return fail(LBM_EINVAL, "mean_out is NULL");
+  c->mean_in_kernel = 0;
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  const int nx = c->p.nx;
+  const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
+  bool on_dev = false;
+  int rc;
+  if ((rc = output_on_device(c, mean_out, "mean_out", &on_dev))) return rc;
+  // one float4 per cell and slab: the sums of the split path, and the staging of host output on either path
+  const size_t ns = c->slabs.size();
+  std::vector<DeviceTemp> acc(ns);
+  for (size_t i = 0; i < ns && !rc; ++i) {
+    Slab& s = c->slabs[i];
+    HIPC(hipSetDevice(s.dev));
+    const size_t bytes = sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx;
+    if (hipMalloc(&acc[i].p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      acc[i].p = nullptr;
+      rc = fail(LBM_ENOMEM, "no room on device %d for the sums of slab %zu (%zu bytes)", s.dev, i, bytes);
+    }
+  }
+  bool in_kernel = regtile_is_next(c);
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the sums"))) return rc;
+  auto out_of = [&](size_t i) { return on_dev ? mean_out + 4L * (c->slabs[i].row0 - base_row) * nx : (float*)acc[i].p; };
+  auto to_host = [&]() -> int {
+    if (on_dev) return LBM_OK;
+    for (size_t i = 0; i < ns; ++i) {
+      Slab& s = c->slabs[i];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemcpy(mean_out + 4L * (s.row0 - base_row) * nx, acc[i].p, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx, hipMemcpyDeviceToHost));
+    }
+    return LBM_OK;
+  };
+  if (in_kernel) {
+    // ---- in the kernel: the means straight into device output, or into the slab's buffer copied out after the run
+    SnapPlan sp;
+    sp.every = every;
+    for (size_t i = 0; i < ns; ++i) { sp.at.push_back(out_of(i)); sp.stride.push_back(0); }
+    RunKind k;
+    k.snap = &sp; k.mean = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->mean_in_kernel) return to_host();
+    // (the register tiles did not run, or gave up with the lattice untouched and nothing stored: the pieces below repeat the run)
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then the fields of the stored lattice added to
+  // the slab's sums (no snapshot, no host round trip per sample); the same adds in the same order as in the register tiles.
+  // Correct, not fast.
+  for (size_t i = 0; i < ns; ++i) {
+    Slab& s = c->slabs[i];
+    HIPC(hipSetDevice(s.dev));
+    HIPC(hipMemsetAsync(acc[i].p, 0, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx, s.sc));
+  }
+  double gpu_ms = 0.0, wall_ms = 0.0;
+  int done = 0;
+  for (int j = 0; j <= m; ++j) {
+    const int n = (j < m) ? every : nsteps - done;
+    if (n == 0) break;
+    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
+    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
+    done += n;
+    if (j < m)
+      for (size_t i = 0; i < ns; ++i) {
+        Slab& s = c->slabs[i];
+        HIPC(hipSetDevice(s.dev));
+        const long ncell = (long)s.nyl * nx;
+        hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
+                           nx, ncell, s.blocked, c->p.density, (float*)acc[i].p);
+        HIPC(hipGetLastError());
+      }
+  }
+  for (size_t i = 0; i < ns; ++i) {
+    Slab& s = c->slabs[i];
+    HIPC(hipSetDevice(s.dev));
+    const long ncell = (long)s.nyl * nx;
+    hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, (const float*)acc[i].p, ncell,
+                       (float)m, out_of(i));
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s.sc));
+  }
+  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  return to_host();
 }
 
 extern "C" int lbm_last_run_ms(const lbm_ctx* c, double* gpu_ms, double* wall_ms) {
@@ -1205,6 +1309,7 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "engine_last")) { *value = c->engine_last; return LBM_OK; }
   if (!strcmp(key, "samples_in_kernel")) { *value = c->samples_in_kernel; return LBM_OK; }
   if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first
     *value = regtile_is_next(c) ? 3 : 1;
     return LBM_OK;

@@ -14,9 +14,11 @@ struct SnapPlan {
 // (a plain lbm_run: the defaults).  snap (lbm_run_sampled): ONLY the register tiles are tried, with the snapshots in the
 // kernel.  nb > 0 (lbm_run_forces): nb bodies; the run's forces are nval = 2 nb nsteps doubles at sums + nsteps + 1 of every
 // slab (behind the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with
-// them; force_tiles: the register tiles may run, in their kRegForce flavour (else the run keeps off them).
+// them; force_tiles: the register tiles may run, in their kRegForce flavour (else the run keeps off them).  mean
+// (lbm_run_mean, with snap): as snap, but the kRegMean flavour -- snap->at[i] is where slab i's means go, the strides unused.
 struct RunKind {
   const SnapPlan* snap = nullptr;
+  bool mean = false;
   int nb = 0;
   long nval = 0;
   bool force_tiles = false;
@@ -236,7 +238,7 @@ bool regtile_is_next(const lbm_ctx* c) {
   return true;
 }
 
-// The instantiation of the register tiles for a tiling and a flavour (0, kRegSnap, kRegForce): lbm_regtile, its arguments
+// The instantiation of the register tiles for a tiling and a flavour (0, kRegSnap, kRegForce, kRegMean): lbm_regtile, its arguments
 // by value (a lattice alone), or lbm_regtile_slabs, a table of them (SLAB)
 template <bool SLAB, int R, int MODE>
 constexpr auto regtile_instance() {
@@ -258,6 +260,7 @@ template <bool SLAB>
 auto regtile_kernel(int r, bool fast, bool async, int flavour) {
   if (flavour == lbm::kRegSnap) return regtile_flavour<SLAB, lbm::kRegSnap>(r, fast, async);
   if (flavour == lbm::kRegForce) return regtile_flavour<SLAB, lbm::kRegForce>(r, fast, async);
+  if (flavour == lbm::kRegMean) return regtile_flavour<SLAB, lbm::kRegMean>(r, fast, async);
   return regtile_flavour<SLAB, 0>(r, fast, async);
 }
 
@@ -342,14 +345,15 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const int ns = (int)c->slabs.size(), ntiles = t.ntx * t.nty;
   const bool fast = (c->variant & lbm::kFastMath) != 0, async = c->regtile_async != 0;
   const bool fk = k.nb > 0 && k.force_tiles;            // lbm_run_forces: the kRegForce flavour, with its larger LDS
-  const int flavour = fk ? lbm::kRegForce : k.snap ? lbm::kRegSnap : 0;
+  const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
+  const int flavour = fk ? lbm::kRegForce : mk ? lbm::kRegMean : k.snap ? lbm::kRegSnap : 0;
   auto kernel = [&](int fl) {
     return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
                 : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
   };
   const dim3 block(64 * t.nw);
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : shm;
+  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : mk ? (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r) : shm;
   static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run
   const bool stats = lone && want_stats;
   int rc;
@@ -384,7 +388,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
     }
   }
   if (t.bpc < 0) return fail(LBM_EINVAL, "register tiling%s not usable: %s", lone ? "" : " across slabs", c->resident_why);
-  if (flavour != 0)                                     // the snapshot / force flavour must be resident at once too (else: the split
+  if (flavour != 0)                                     // the snapshot / force / mean flavour must be resident at once too (else: the split
     for (int g = 0; g < ngroups; ++g) {                 // run / the force kernel; lbm_run_forces has asked every rank already)
       HIPC(hipSetDevice(lead(g).dev));
       const int n = regtile_prepare(c, kernel(flavour), lead(g).dev, (int)block.x, shm_run);

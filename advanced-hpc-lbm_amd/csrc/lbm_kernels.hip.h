@@ -1154,6 +1154,34 @@ __global__ __launch_bounds__(kBlock) void lbm_derive(const float* lat, long plan
   if (threadIdx.x == 0) { partials[blockIdx.x] = bs; mass_partials[blockIdx.x] = bm; }
 }
 
+// lbm_run_mean on every engine but the register tiles' mean flavour: behind each piece of `every` steps the fields of the
+// stored lattice (derive_cell, as lbm_derive) are ADDED to acc4[cell] -- zeroed before the run, so that the first sample
+// is an add to +0 like every other; float, one rounding per add, the order of the steps: the sums the register tiles keep.
+__global__ __launch_bounds__(kBlock) void lbm_mean_add(const float* lat, long plane, int pitch, int nx, long ncell,
+                                                       const uint8_t* blocked, float density, float* acc4) {
+#pragma clang fp contract(off)
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncell) return;
+  const long y = c / nx; const int x = (int)(c - y * nx);
+  const long o = y * pitch + x;
+  float f[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
+  float rho;
+  const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
+  f4a s = *reinterpret_cast<const f4a*>(acc4 + 4 * c);
+  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+  *reinterpret_cast<f4a*>(acc4 + 4 * c) = s;
+}
+// ... and after the last piece: out4[cell] = acc4[cell] / m (IEEE division; out4 may be acc4)
+__global__ __launch_bounds__(kBlock) void lbm_mean_div(const float* acc4, long ncell, float m, float* out4) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncell) return;
+  f4a s = *reinterpret_cast<const f4a*>(acc4 + 4 * c);
+  s.x = s.x / m; s.y = s.y / m; s.z = s.z / m; s.w = s.w / m;
+  *reinterpret_cast<f4a*>(out4 + 4 * c) = s;
+}
+
 __global__ __launch_bounds__(kBlock) void lbm_fold_double(const double* in, int count, double* out) {
   __shared__ double red_d[kBlock / 64];
   double s = 0.0;

@@ -55,6 +55,8 @@ constexpr int kRegSnap = 16384;   // lbm_regtile: snapshots during the run (lbm_
                                   // the count-down and the store cost the unsampled loop ~2 % (1024^2, 3.09 against 3.02 us per step)
 constexpr int kRegForce = 32768;  // lbm_regtile: drag and lift on labelled bodies during the run (lbm_run_forces).  A flavour of
                                   // its own, like kRegSnap: lbm_run's kernels keep their registers and their loop
+constexpr int kRegMean = 65536;   // lbm_regtile: time-averaged fields summed during the run (lbm_run_mean).  A flavour of its own, like
+                                  // kRegSnap: three sums per cell in LDS, one in a register, one 16-byte store per cell after the last step
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
 // Per-step forces of a whole-run launch with kRegForce: partials[step][slot][8] (8 = four labels x two components, the
@@ -114,6 +116,9 @@ struct RegTileArgs {
   // ---- snapshots (lbm_run_sampled): after steps every, 2 every, ... the derived fields of every cell (derive_cell, from the
   // post-collision populations, before the next step's accelerate) go to snap + j snap_stride + 4 (row nx + column), rows
   // counted in this lattice / slab (flavour kRegSnap only; every = 0: none)
+  // ---- means (lbm_run_mean, flavour kRegMean only): on the same sample steps the fields are ADDED to per-cell sums that
+  // stay in the tile (float, step order); after the last step sum / (nsteps / every) goes to snap + 4 (row nx + column)
+  // (snap_stride unused)
   float* snap; long snap_stride;
   int every; float density;
   // ---- forces (lbm_run_forces, flavour kRegForce only): fslot[tile] = the tile's slot, or -1 for a tile without a blocked
@@ -126,6 +131,10 @@ struct RegTileArgs {
 __host__ __device__ constexpr int regtile_lds_bytes(int nw, int r) { return 4 * (nw * (2 * 6 * 64 + (r == 4 ? r * 3 * 64 : 0)) + 2 * 16 + 16 + 2 * 16); }
 // ... of the kRegForce flavour: behind those, the cells' force words [wave][R][64] and the waves' sums [parity][wave][8]
 __host__ __device__ constexpr int regtile_lds_bytes_force(int nw, int r) { return regtile_lds_bytes(nw, r) + 4 * nw * (r * 64 + 2 * 8); }
+
+// ... of the kRegMean flavour: behind those, the sums of u_x, u_y, |u| of every cell, [wave][R][3][64] (the pressure's sum
+// is a register per row: all four in LDS would miss the CU's 160 KB by 320 bytes on the 16 x 4 tiling)
+__host__ __device__ constexpr int regtile_lds_bytes_mean(int nw, int r) { return regtile_lds_bytes(nw, r) + 4 * nw * r * 3 * 64; }
 
 // bytes of one mailbox (one tile, one parity): Sin[64], Nin[64], Win[ty+2], Ein[ty+2] granules of 16 bytes
 __host__ __device__ constexpr int regtile_box(int ty) { return 16 * (2 * 64 + 2 * (ty + 2)); }
@@ -154,6 +163,8 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool SLAB = (MODE & kRegSlab) != 0;
   constexpr bool SNAP = (MODE & kRegSnap) != 0;
   constexpr bool FORCE = (MODE & kRegForce) != 0;
+  constexpr bool MEAN = (MODE & kRegMean) != 0;
+  static_assert(!(MEAN && (SNAP || FORCE)), "one flavour per launch");
   // The mail of the loop issued and waited for BY HAND (R > 1): see "the asynchronous loop" below
   constexpr bool ASYNC = (MODE & kRegAsync) != 0 && R > 1;
   static_assert(R == 1 || R == 2 || R == 4, "rows per wave");
@@ -167,8 +178,8 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   const int nw_ = (int)(blockDim.x >> 6);
   float* red = lds + nw_ * (2 * 6 * 64 + (R == 4 ? R * 3 * 64 : 0));
   uint32_t* lds_abort = reinterpret_cast<uint32_t*>(red + 32);
-  long long* lds_snap = reinterpret_cast<long long*>(red + 34);     // [1] snap_stride, [2] every | density << 32 (red + 36 .. 39)
-  long long* lds_snap_at = reinterpret_cast<long long*>(red + 48);  // [wave]: where its next snapshot goes (red + 48 .. 79)
+  long long* lds_snap = reinterpret_cast<long long*>(red + 34);     // [1] snap_stride (MEAN: nx), [2] every | density << 32 (red + 36 .. 39)
+  long long* lds_snap_at = reinterpret_cast<long long*>(red + 48);  // [wave]: where its next snapshot goes (MEAN: the means) (red + 48 .. 79)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6), nw = (int)(blockDim.x >> 6);
@@ -215,8 +226,8 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   const int rho0 = w * R;                                   // tile row of this wave's first row
   const int gx = bx * 64 + lane, gy0 = by * TY + rho0;
   if (tid == 0) *lds_abort = 0u;
-  if constexpr (SNAP) {
-    if (tid == 0) { lds_snap[1] = a.snap_stride; lds_snap[2] = (long long)(unsigned)a.every | ((long long)__float_as_uint(a.density) << 32); }
+  if constexpr (SNAP || MEAN) {
+    if (tid == 0) { lds_snap[1] = MEAN ? (long long)a.nx : a.snap_stride; lds_snap[2] = (long long)(unsigned)a.every | ((long long)__float_as_uint(a.density) << 32); }
     if (lane == 0) lds_snap_at[w] = (long long)a.snap;
   }
   // forces (FORCE): the tile's slot (-1: nothing to count here); frow = bit 4 r + b: row r of this wave holds a cell of
@@ -288,8 +299,42 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   };
   // after a sample step: the wave's next snapshot, and the steps to it
   auto snap_next = [&]() {
-    if (lane == 0) lds_snap_at[w] += lds_snap[1] * (long long)sizeof(float);
+    if (!MEAN && lane == 0) lds_snap_at[w] += lds_snap[1] * (long long)sizeof(float);
     return __builtin_amdgcn_readfirstlane((int)(unsigned)lds_snap[2]);
+  };
+  // means (MEAN): the sums of a lane's cells -- u_x, u_y, |u| in LDS behind the tile's other LDS (macc[(r * 3 + j) * 64]: only
+  // this lane ever touches them, no barrier), the pressure's in mw[r].  A sample step adds the row's fields (derive_cell of
+  // the row after collide_cell, as a snapshot would store them): one rounding per add, in step order, the first sample added
+  // to +0 like every other.  LDS and VALU work only: no vector-memory operation, the counted vmcnt waits of the
+  // asynchronous loop see exactly the operations they see without it.
+  float* macc = lds + regtile_lds_bytes(nw_, R) / 4 + w * (R * 3 * 64) + lane;
+  float mw[R];
+  if constexpr (MEAN) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) { macc[(r * 3 + 0) * 64] = 0.f; macc[(r * 3 + 1) * 64] = 0.f; macc[(r * 3 + 2) * 64] = 0.f; mw[r] = 0.f; }
+  }
+  auto mean_row = [&](auto rc, const float (&p)[9], bool b) {
+#pragma clang fp contract(off)
+    constexpr int r = decltype(rc)::value;
+    float rho;
+    const f4a v = derive_cell(p, b, __uint_as_float((unsigned)(lds_snap[2] >> 32)), rho);
+    float* at = macc + (r * 3) * 64;
+    at[0] = at[0] + v.x; at[64] = at[64] + v.y; at[128] = at[128] + v.z;
+    mw[r] = mw[r] + v.w;
+  };
+  // after the last step: sum / m (IEEE division), one 16-byte store per cell, 1 KB contiguous per wave-row.  nx and `every`
+  // come back from LDS (kept in scalar registers across the loop they would be spilled around the asm mail operations)
+  auto mean_store = [&](int gyq, int gxq) {
+    const int ev = __builtin_amdgcn_readfirstlane((int)(unsigned)lds_snap[2]);
+    const long nxq = (long)__builtin_amdgcn_readfirstlane((int)lds_snap[1]);
+    const float fm = (float)(a.nsteps / ev);
+    float* at = reinterpret_cast<float*>(lds_snap_at[w]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      f4a v;
+      v.x = macc[(r * 3 + 0) * 64] / fm; v.y = macc[(r * 3 + 1) * 64] / fm; v.z = macc[(r * 3 + 2) * 64] / fm; v.w = mw[r] / fm;
+      __builtin_nontemporal_store(v, reinterpret_cast<f4a*>(at + 4 * ((long)(gyq + r) * nxq + gxq)));
+    }
   };
 
   // east / west mail: lane 63 stores its row into the west inbox of the tile to the east, lane 0 into the east inbox of
@@ -560,7 +605,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       for (int s = 1; s <= a.nsteps; ++s) {
         int par = (s - 1) & 1;
         asm volatile("" : "+s"(par));
-        const bool sample = SNAP && --snap_left == 0;
+        const bool sample = (SNAP || MEAN) && --snap_left == 0;
         const unsigned pb = (unsigned)par * BOX, pbn = BOX - pb;
         const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
@@ -646,7 +691,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           // with the loads, in issue order (MI355X_MICROARCH.md, vmcnt): one more operation younger than a pending fetch makes
           // the counted vmcnt(N) that retires it wait for MORE, never less -- the fixed counts stay safe, a sample step may
           // wait a little longer.  Nothing the asm loads write is read here.
-          if (sample) snap_row(r, p, blk[r]);
+          if (sample) { if constexpr (MEAN) mean_row(RC{}, p, blk[r]); else snap_row(r, p, blk[r]); }
           // forces (a row with a labelled cell only): LDS and DPP work and lane 0's LDS add, no vector-memory operation --
           // the counted vmcnt waits see exactly the operations they see without it
           if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
@@ -699,6 +744,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         for (int k = 2; k < 9; ++k)
           if (k != 3) __builtin_nontemporal_store(f[r][k], &a.dst[k * a.plane + o]);
       }
+      if constexpr (MEAN) mean_store(gyq, gxq);
     }
     if (tid < 64) {
       float v = (lane < nw) ? red[(a.nsteps & 1) * 16 + lane] : 0.f;
@@ -722,7 +768,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   for (int s = 1; s <= a.nsteps; ++s) {
     int par = (s - 1) & 1;                         // parity of the state being pulled
     asm volatile("" : "+s"(par));                  // (keeps both parities' addresses from being hoisted into registers)
-    const bool sample = SNAP && --snap_left == 0;
+    const bool sample = (SNAP || MEAN) && --snap_left == 0;
     const unsigned pb = (unsigned)par * BOX, pbn = BOX - pb;
     const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
@@ -789,7 +835,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       sp += collide_cell<FAST, true>(p, blk[r], a.omega);
       // snapshot (wave-uniform step), before the next step's accelerate.  Behind the fetch of the next row's mail: on a sample
       // step the compiler's wait for that mail also waits for this store (no counted waits here to keep exact)
-      if (sample) snap_row(r, p, blk[r]);
+      if (sample) { if constexpr (MEAN) mean_row(rc, p, blk[r]); else snap_row(r, p, blk[r]); }
       if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
       if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
       f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
@@ -855,6 +901,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       for (int k = 2; k < 9; ++k)
         if (k != 3) __builtin_nontemporal_store(f[r][k], &a.dst[k * a.plane + o]);
     }
+    if constexpr (MEAN) mean_store(gyq, gxq);
   }
   if (tid < 64) {
     float v = (lane < nw) ? red[(a.nsteps & 1) * 16 + lane] : 0.f;

@@ -151,6 +151,27 @@ int lbm_run(lbm_ctx* ctx, int nsteps, float* av_vels);
 int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* fields_out);
 
 /*
+ * lbm_run with the time-averaged fields of the run: the mean of u_x, u_y, |u| and pressure per cell over the sample steps
+ * of lbm_run_sampled (after steps every, 2 every, ..., m every; m = nsteps / every).  With X_j = snapshot j of
+ * lbm_run_sampled(ctx, nsteps, av_vels, every, ...), the definition is, per cell and field, bit for bit:
+ *     S_0 = +0.0f;  S_j = S_(j-1) + X_j  in float, in step order (one rounding per add, no fma, no reassociation);
+ *     mean_out = S_m / (float)m  (a correctly rounded float division).
+ * Blocked cells take part like any other (their X_j is the constant 0, 0, 0, density / 3).  mean_out: float[rows][nx][4]
+ * with the rows and the rank-local convention of lbm_final_state; host memory, or device memory of the device that holds
+ * every slab of the context (then nothing is copied to the host).  av_vels, the lattice and everything after are
+ * bit-identical to lbm_run(ctx, nsteps, av_vels).  The register-tile engines keep the sums inside their kernels (info
+ * "mean_in_kernel" = 1: no memory traffic for them until the run ends, then one 16-byte store per cell); the other engines
+ * run the steps in pieces of `every` with a small kernel behind each that adds into a per-slab buffer on the device
+ * (correct, not fast; same adds in the same order, the same bits).
+ * LBM_EINVAL when every <= 0, m = 0 (nothing to average), mean_out is NULL or nsteps < 0; LBM_ENOMEM when the per-slab
+ * buffer (16 bytes per cell) does not fit; in both cases before anything runs: the lattice is untouched.
+ * A window that starts late is lbm_run(ctx, skip, ...) followed by lbm_run_mean; the means of consecutive calls can be
+ * combined by the caller in double (weights m).  Accuracy: a plain float sum of m terms carries at most (m - 1) 2^-24
+ * relative to the sum of |X_j| per cell.  Not combined with snapshots or forces in one call.
+ */
+int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mean_out);
+
+/*
  * Drag and lift on labelled bodies, step by step.
  *
  * Directions are the reference's: 1 E, 2 N, 3 W, 4 S, 5 NE, 6 NW, 7 SW, 8 SE. c_i is the lattice vector and opp(i)
@@ -234,7 +255,8 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "regtile_async" (0, 1), "regtile_tag" (test hook: the next mailbox tag), "kernel_variant" (bits: 1 fast rcp / sqrt, 2 / 4 nontemporal stores / loads, 8 the reference's
  * form of the speed sum, d2q9-bgk.c:1783-1811, 256 one-step kernel only), "vector_width", "t2_threads".
  * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
- * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
+ * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */
