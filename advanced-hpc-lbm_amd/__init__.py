@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
+    "lbm_set_probes", "lbm_run_probes",
     "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
@@ -91,6 +92,8 @@ def load_library():
     lib.lbm_run_sampled.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_run_mean.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_set_bodies.argtypes = [vp, vp, C.c_int]
+    lib.lbm_set_probes.argtypes = [vp, vp, C.c_int]
+    lib.lbm_run_probes.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_run_forces.argtypes = [vp, C.c_int, vp, vp]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
@@ -239,6 +242,41 @@ class Lattice:
             torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
         _check(self._lib.lbm_run_mean(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, mean
+
+    def set_probes(self, xy):
+        """The cells run_probes records: xy is anything np.asarray turns into int32[n, 2] of (column, row) in the global
+        lattice, in the order the series are wanted; None or an empty set clears it."""
+        if xy is None or np.size(xy) == 0:
+            _check(self._lib.lbm_set_probes(self._ctx, None, 0))
+            self._nprobes = 0
+            return
+        arr = np.ascontiguousarray(np.asarray(xy), dtype=np.int32)
+        if arr.ndim != 2 or arr.shape[1] != 2:
+            raise LbmError(f"xy must have shape (n, 2), got {arr.shape}")
+        _check(self._lib.lbm_set_probes(self._ctx, arr.ctypes.data, arr.shape[0]))
+        self._nprobes = arr.shape[0]
+
+    def run_probes(self, nsteps: int, every: int = 1, out=None):
+        """lbm_run with the time series of the probes (set_probes): returns (av_vels[nsteps], probes) where probes is
+        (nsteps // every, nprobes, 4) float32 -- u_x, u_y, |u|, pressure of each probe after steps every, 2 every, ...,
+        the bits run_sampled has in those cells -- a numpy array, or `out`, a contiguous float32 torch tensor of that
+        shape on the context's GPU, filled there."""
+        n = getattr(self, "_nprobes", 0)
+        shape = (max(nsteps, 0) // every if every > 0 else 0, n, 4)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        if out is None:
+            probes = np.empty(shape, dtype=np.float32)
+            ptr = probes.ctypes.data if probes.size else None
+        else:
+            import torch
+            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
+                    or not out.is_contiguous() or tuple(out.shape) != shape):
+                raise LbmError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
+            probes = out
+            ptr = out.data_ptr()
+            torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        _check(self._lib.lbm_run_probes(self._ctx, nsteps, av.ctypes.data, every, ptr))
+        return av, probes
 
     def set_bodies(self, body, nbodies: int):
         """Labels blocked cells 1..nbodies (0: not counted) for run_forces: body is int[ny, nx] over the global lattice

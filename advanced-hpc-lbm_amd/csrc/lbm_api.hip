@@ -197,6 +197,13 @@ struct Slab {
   int fnslots = 0, fty = 0;
   float* fpart = nullptr;
   long fpart_cap = 0;              // floats
+  // probes (lbm_set_probes): the slab's probes, {column, local row, index in the set}; on the device as {offset in a plane,
+  // index} for lbm_probe_gather; the register tiles' tables (lbm_regtile.hip.h, kRegProbe) for tiles of pty rows (0: not built)
+  std::vector<int4> pcells_host;
+  int2* pcells = nullptr;
+  int* pslot = nullptr;
+  uint32_t* pwords = nullptr;
+  int pty = 0;
 };
 
 }  // namespace
@@ -237,7 +244,9 @@ struct lbm_ctx {
   int samples_in_kernel = 0;   // 1: the snapshots of the last lbm_run_sampled came from the register tiles
   int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
   int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
+  int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
   int nbodies = 0;             // lbm_set_bodies (0: none)
+  int nprobes = 0;             // lbm_set_probes (0: none)
   // obstacle map of the local rows and one row either side (global rows keep_row0 .. keep_row0 + keep_rows - 1, taken
   // modulo ny), for the bodies' direction masks
   std::vector<uint8_t> obst_keep;
@@ -616,9 +625,9 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 
 static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
 
-// The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean): ONLY the register tiles are tried, with the
-// snapshots (the sums) in the kernel; if they did not run (samples_in_kernel / mean_in_kernel stays 0), nothing has been
-// stepped and the caller runs the steps in pieces.
+// The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean; with k.probe: lbm_run_probes): ONLY the
+// register tiles are tried, with the snapshots (the sums, the probes) in the kernel; if they did not run (samples_in_kernel /
+// mean_in_kernel / probes_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
 static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind()) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
@@ -639,7 +648,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
     if (rr) return rr;
     if (done) {
       c->engine_last = 3;
-      if (k.snap && k.mean) c->mean_in_kernel = 1;
+      if (k.snap && k.probe) c->probes_in_kernel = 1;
+      else if (k.snap && k.mean) c->mean_in_kernel = 1;
       else if (k.snap) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
       return LBM_OK;
@@ -1073,6 +1083,162 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
   return to_host();
 }
 
+extern "C" int lbm_set_probes(lbm_ctx* c, const int* xy, int nprobes) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nprobes < 0 || nprobes > LBM_MAX_PROBES) return fail(LBM_EINVAL, "nprobes must be in [0, %d] (got %d)", LBM_MAX_PROBES, nprobes);
+  if (nprobes > 0 && !xy) return fail(LBM_EINVAL, "xy is NULL");
+  const int nx = c->p.nx, ny = c->p.ny;
+  // ---- the whole set is checked, and the slabs' new lists are on their devices, before anything of the earlier set goes
+  std::vector<std::pair<long, int>> seen((size_t)nprobes);
+  for (int i = 0; i < nprobes; ++i) {
+    const int x = xy[2 * i], y = xy[2 * i + 1];
+    if (x < 0 || x >= nx || y < 0 || y >= ny)
+      return fail(LBM_EINVAL, "xy[%d] = (%d, %d) is outside the %d x %d lattice", i, x, y, nx, ny);
+    seen[i] = {(long)y * nx + x, i};
+  }
+  std::sort(seen.begin(), seen.end());
+  for (int i = 1; i < nprobes; ++i)
+    if (seen[i].first == seen[i - 1].first)
+      return fail(LBM_EINVAL, "xy[%d] and xy[%d] are the same cell (%d, %d)", seen[i - 1].second, seen[i].second,
+                  (int)(seen[i].first % nx), (int)(seen[i].first / nx));
+  const size_t ns = c->slabs.size();
+  std::vector<std::vector<int4>> lists(ns);
+  std::vector<DeviceTemp> fresh(ns);
+  for (size_t k = 0; k < ns; ++k) {
+    Slab& s = c->slabs[k];
+    for (int i = 0; i < nprobes; ++i) {
+      const int y = xy[2 * i + 1] - s.row0;
+      if (y >= 0 && y < s.nyl) lists[k].push_back(int4{xy[2 * i], y, i, 0});
+    }
+    if (lists[k].empty()) continue;
+    std::vector<int2> dev(lists[k].size());
+    for (size_t j = 0; j < dev.size(); ++j) dev[j] = int2{lists[k][j].y * s.pitch + lists[k][j].x, lists[k][j].z};
+    HIPC(hipSetDevice(s.dev));
+    if (hipMalloc(&fresh[k].p, sizeof(int2) * dev.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      fresh[k].p = nullptr;
+      return fail(LBM_ENOMEM, "no room on device %d for %zu probe cells", s.dev, dev.size());
+    }
+    HIPC(hipMemcpy(fresh[k].p, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
+  }
+  for (size_t k = 0; k < ns; ++k) {
+    Slab& s = c->slabs[k];
+    HIPC(hipSetDevice(s.dev));
+    if (s.pcells) HIPC(hipFree(s.pcells));
+    s.pcells = (int2*)fresh[k].p; fresh[k].p = nullptr;
+    s.pcells_host.swap(lists[k]);
+    s.pty = 0;                      // (the register tiles' tables: rebuilt by the next lbm_run_probes)
+  }
+  c->nprobes = nprobes;
+  return LBM_OK;
+}
+
+extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every, float* probes_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (c->nprobes == 0) return fail(LBM_EINVAL, "no probes are set (lbm_set_probes)");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
+  const int m = nsteps / every;
+  if (m == 0) return fail(LBM_EINVAL, "nothing to record: no sample step in nsteps = %d step(s) at every = %d", nsteps, every);
+  if (!probes_out) return fail(LBM_EINVAL, "probes_out is NULL");
+  c->probes_in_kernel = 0;
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  const int np = c->nprobes;
+  const size_t ns = c->slabs.size();
+  const size_t nfloat = 4 * (size_t)m * (size_t)np;
+  bool on_dev = false;
+  int rc;
+  if ((rc = output_on_device(c, probes_out, "probes_out", &on_dev))) return rc;
+  bool in_kernel = regtile_is_next(c);
+  // host output: one staging buffer [m][nprobes][4] per slab that holds a probe (a slab stores into its probes' places only)
+  std::vector<DeviceTemp> stage(ns);
+  size_t local = 0;
+  for (size_t i = 0; i < ns && !rc; ++i) {
+    Slab& s = c->slabs[i];
+    local += s.pcells_host.size();
+    if (!on_dev && !s.pcells_host.empty()) {
+      HIPC(hipSetDevice(s.dev));
+      if (hipMalloc(&stage[i].p, sizeof(float) * nfloat) != hipSuccess) {
+        (void)hipGetLastError();
+        stage[i].p = nullptr;
+        rc = fail(LBM_ENOMEM, "no room on device %d for %d sample(s) of %d probe(s) of slab %zu (%zu bytes)", s.dev, m, np, i, sizeof(float) * nfloat);
+      }
+    }
+    if (!rc && in_kernel) rc = probe_tables(c, s, c->tplan.ty, c->tplan.ntx);
+  }
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the probes"))) return rc;
+  // the probes of other ranks' rows read +0.0f
+  if (local < (size_t)np) {
+    if (on_dev) {
+      Slab& s = c->slabs[0];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemsetAsync(probes_out, 0, sizeof(float) * nfloat, s.sc));
+      HIPC(hipStreamSynchronize(s.sc));
+    } else memset(probes_out, 0, sizeof(float) * nfloat);
+  }
+  auto out_of = [&](size_t i) { return on_dev ? probes_out : (float*)stage[i].p; };
+  auto to_host = [&]() -> int {
+    if (on_dev) return LBM_OK;
+    std::vector<float> tmp;
+    for (size_t i = 0; i < ns; ++i) {
+      Slab& s = c->slabs[i];
+      if (s.pcells_host.empty()) continue;
+      HIPC(hipSetDevice(s.dev));
+      if (s.pcells_host.size() == (size_t)np) {          // (every probe is this slab's)
+        HIPC(hipMemcpy(probes_out, stage[i].p, sizeof(float) * nfloat, hipMemcpyDeviceToHost));
+        continue;
+      }
+      tmp.resize(nfloat);
+      HIPC(hipMemcpy(tmp.data(), stage[i].p, sizeof(float) * nfloat, hipMemcpyDeviceToHost));
+      for (int j = 0; j < m; ++j)
+        for (const int4& q : s.pcells_host) {
+          const size_t o = 4 * ((size_t)j * np + (size_t)q.z);
+          memcpy(probes_out + o, tmp.data() + o, 4 * sizeof(float));
+        }
+    }
+    return LBM_OK;
+  };
+  if (in_kernel) {
+    // ---- in the kernel: every slab's tiles store their probes straight into their places of device output / of the slab's staging
+    SnapPlan sp;
+    sp.every = every;
+    for (size_t i = 0; i < ns; ++i) { sp.at.push_back(out_of(i)); sp.stride.push_back(4L * np); }
+    RunKind k;
+    k.snap = &sp; k.probe = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->probes_in_kernel) return to_host();
+    // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run and store every value again)
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then the probes' cells of the stored lattice
+  // gathered into row j.  Correct, not fast.
+  double gpu_ms = 0.0, wall_ms = 0.0;
+  int done = 0;
+  for (int j = 0; j <= m; ++j) {
+    const int n = (j < m) ? every : nsteps - done;
+    if (n == 0) break;
+    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
+    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
+    done += n;
+    if (j < m)
+      for (size_t i = 0; i < ns; ++i) {
+        Slab& s = c->slabs[i];
+        const int n_here = (int)s.pcells_host.size();
+        if (n_here == 0) continue;
+        HIPC(hipSetDevice(s.dev));
+        hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane,
+                           s.pcells, n_here, s.blocked, c->p.density, out_of(i) + 4 * (size_t)j * (size_t)np);
+        HIPC(hipGetLastError());
+      }
+  }
+  for (auto& s : c->slabs) {
+    HIPC(hipSetDevice(s.dev));
+    HIPC(hipStreamSynchronize(s.sc));
+  }
+  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  return to_host();
+}
+
 extern "C" int lbm_last_run_ms(const lbm_ctx* c, double* gpu_ms, double* wall_ms) {
   if (!c) return fail(LBM_EINVAL, "ctx is NULL");
   if (gpu_ms) *gpu_ms = c->gpu_ms;
@@ -1310,6 +1476,7 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "samples_in_kernel")) { *value = c->samples_in_kernel; return LBM_OK; }
   if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
   if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first
     *value = regtile_is_next(c) ? 3 : 1;
     return LBM_OK;

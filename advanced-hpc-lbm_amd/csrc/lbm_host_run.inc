@@ -16,9 +16,13 @@ struct SnapPlan {
 // slab (behind the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with
 // them; force_tiles: the register tiles may run, in their kRegForce flavour (else the run keeps off them).  mean
 // (lbm_run_mean, with snap): as snap, but the kRegMean flavour -- snap->at[i] is where slab i's means go, the strides unused.
+// probe (lbm_run_probes, with snap): as snap, but the kRegProbe flavour -- snap->at[i] is row 0 of the output slab i stores
+// into, stride[i] the floats from one sample's row to the next (4 x the probes of the whole set); the slabs' probe tables
+// (probe_tables) are in place.
 struct RunKind {
   const SnapPlan* snap = nullptr;
   bool mean = false;
+  bool probe = false;
   int nb = 0;
   long nval = 0;
   bool force_tiles = false;
@@ -107,6 +111,36 @@ int force_tables(lbm_ctx* c, Slab& s, int ty, int ntx, int nsteps) {
     }
     s.fpart_cap = need;
   }
+  return LBM_OK;
+}
+
+// ----------------------------------------------------------------- probes (lbm_run_probes)
+// The register tiles' tables of a slab for tiles of ty rows and ntx columns of tiles: slots in the order of the tiles (only
+// tiles that hold a probe have one; a slab without probes gets the table of -1s alone).  LBM_ENOMEM: nothing queued.
+int probe_tables(lbm_ctx* c, Slab& s, int ty, int ntx) {
+  (void)c;
+  if (s.pty == ty) return LBM_OK;
+  HIPC(hipSetDevice(s.dev));
+  const int nty = s.nyl / ty, ntiles = ntx * nty;
+  std::vector<int> slot(ntiles, -1);
+  for (const int4& q : s.pcells_host) slot[(q.y / ty) * ntx + q.x / 64] = 0;
+  int n = 0;
+  for (int& v : slot) if (v == 0) v = n++;
+  std::vector<uint32_t> words((size_t)n * ty * 64, 0u);
+  for (const int4& q : s.pcells_host) words[((size_t)slot[(q.y / ty) * ntx + q.x / 64] * ty + q.y % ty) * 64 + q.x % 64] = (uint32_t)q.z + 1u;
+  if (s.pslot) HIPC(hipFree(s.pslot));
+  if (s.pwords) HIPC(hipFree(s.pwords));
+  s.pslot = nullptr; s.pwords = nullptr; s.pty = 0;
+  if (hipMalloc((void**)&s.pslot, sizeof(int) * ntiles) != hipSuccess ||
+      (n > 0 && hipMalloc((void**)&s.pwords, sizeof(uint32_t) * words.size()) != hipSuccess)) {
+    (void)hipGetLastError();
+    if (s.pslot) (void)hipFree(s.pslot);
+    s.pslot = nullptr; s.pwords = nullptr;
+    return fail(LBM_ENOMEM, "no room on device %d for the probe tables (%d tiles)", s.dev, n);
+  }
+  HIPC(hipMemcpy(s.pslot, slot.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
+  if (n > 0) HIPC(hipMemcpy(s.pwords, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
+  s.pty = ty;
   return LBM_OK;
 }
 
@@ -238,7 +272,7 @@ bool regtile_is_next(const lbm_ctx* c) {
   return true;
 }
 
-// The instantiation of the register tiles for a tiling and a flavour (0, kRegSnap, kRegForce, kRegMean): lbm_regtile, its arguments
+// The instantiation of the register tiles for a tiling and a flavour (0, kRegSnap, kRegForce, kRegMean, kRegProbe): lbm_regtile, its arguments
 // by value (a lattice alone), or lbm_regtile_slabs, a table of them (SLAB)
 template <bool SLAB, int R, int MODE>
 constexpr auto regtile_instance() {
@@ -261,6 +295,7 @@ auto regtile_kernel(int r, bool fast, bool async, int flavour) {
   if (flavour == lbm::kRegSnap) return regtile_flavour<SLAB, lbm::kRegSnap>(r, fast, async);
   if (flavour == lbm::kRegForce) return regtile_flavour<SLAB, lbm::kRegForce>(r, fast, async);
   if (flavour == lbm::kRegMean) return regtile_flavour<SLAB, lbm::kRegMean>(r, fast, async);
+  if (flavour == lbm::kRegProbe) return regtile_flavour<SLAB, lbm::kRegProbe>(r, fast, async);
   return regtile_flavour<SLAB, 0>(r, fast, async);
 }
 
@@ -346,14 +381,16 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const bool fast = (c->variant & lbm::kFastMath) != 0, async = c->regtile_async != 0;
   const bool fk = k.nb > 0 && k.force_tiles;            // lbm_run_forces: the kRegForce flavour, with its larger LDS
   const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
-  const int flavour = fk ? lbm::kRegForce : mk ? lbm::kRegMean : k.snap ? lbm::kRegSnap : 0;
+  const bool pk = k.snap && k.probe;                    // lbm_run_probes: the kRegProbe flavour, with its larger LDS
+  const int flavour = fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : 0;
   auto kernel = [&](int fl) {
     return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
                 : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
   };
   const dim3 block(64 * t.nw);
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : mk ? (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r) : shm;
+  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : mk ? (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r)
+                                                                                    : pk ? (unsigned)lbm::regtile_lds_bytes_probe(t.nw, t.r) : shm;
   static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run
   const bool stats = lone && want_stats;
   int rc;
@@ -388,7 +425,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
     }
   }
   if (t.bpc < 0) return fail(LBM_EINVAL, "register tiling%s not usable: %s", lone ? "" : " across slabs", c->resident_why);
-  if (flavour != 0)                                     // the snapshot / force / mean flavour must be resident at once too (else: the split
+  if (flavour != 0)                                     // the snapshot / force / mean / probe flavour must be resident at once too (else: the split
     for (int g = 0; g < ngroups; ++g) {                 // run / the force kernel; lbm_run_forces has asked every rank already)
       HIPC(hipSetDevice(lead(g).dev));
       const int n = regtile_prepare(c, kernel(flavour), lead(g).dev, (int)block.x, shm_run);
@@ -471,6 +508,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       a.snap = k.snap ? k.snap->at[i] : nullptr; a.snap_stride = k.snap ? k.snap->stride[i] : 0; a.every = k.snap ? k.snap->every : 0;
       a.density = c->p.density;
       a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
+      if (pk) { a.fslot = s.pslot; a.fwords = s.pwords; a.fpart = nullptr; a.nslots = 0; }   // (the probe flavour's tables: same members)
       if (c->rank_mode && c->nranks > 1) {
         a.mail_s = s.tmail_nb[0]; a.mail_n = s.tmail_nb[1];
         a.mail_bytes_s = (unsigned)s.tmail_nb_bytes[0]; a.mail_bytes_n = (unsigned)s.tmail_nb_bytes[1];

@@ -362,6 +362,9 @@ void slab_free(Slab& s) {
   if (s.fcells) (void)hipFree(s.fcells);
   if (s.fslot) (void)hipFree(s.fslot);
   if (s.fwords) (void)hipFree(s.fwords);
+  if (s.pcells) (void)hipFree(s.pcells);
+  if (s.pslot) (void)hipFree(s.pslot);
+  if (s.pwords) (void)hipFree(s.pwords);
   if (s.fpart) (void)hipFree(s.fpart);
   if (s.sums && !s.sums_direct) (void)hipFree(s.sums);
   if (s.sums_host) (void)hipHostFree(s.sums_host);

@@ -1182,6 +1182,24 @@ __global__ __launch_bounds__(kBlock) void lbm_mean_div(const float* acc4, long n
   *reinterpret_cast<f4a*>(out4 + 4 * c) = s;
 }
 
+// lbm_run_probes on every engine but the register tiles' probe flavour: behind each piece of `every` steps one lane per probe
+// of the slab takes derive_cell of its cell from the stored lattice (the bits lbm_derive gives that cell) and stores them
+// into its place of the sample's row: cells[j] = {offset of the cell in the slab's planes, probe index}; row4 = the row of
+// this sample, float[nprobes][4].
+__global__ __launch_bounds__(kBlock) void lbm_probe_gather(const float* lat, long plane, const int2* cells, int n,
+                                                           const uint8_t* blocked, float density, float* row4) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int2 cw = cells[j];
+  float f[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + cw.x];
+  float rho;
+  const f4a v = derive_cell(f, blocked[cw.x] != 0, density, rho);
+  *reinterpret_cast<f4a*>(row4 + 4 * (long)cw.y) = v;
+}
+
 __global__ __launch_bounds__(kBlock) void lbm_fold_double(const double* in, int count, double* out) {
   __shared__ double red_d[kBlock / 64];
   double s = 0.0;

@@ -57,6 +57,8 @@ constexpr int kRegForce = 32768;  // lbm_regtile: drag and lift on labelled bodi
                                   // its own, like kRegSnap: lbm_run's kernels keep their registers and their loop
 constexpr int kRegMean = 65536;   // lbm_regtile: time-averaged fields summed during the run (lbm_run_mean).  A flavour of its own, like
                                   // kRegSnap: three sums per cell in LDS, one in a register, one 16-byte store per cell after the last step
+constexpr int kRegProbe = 131072; // lbm_regtile: per-step time series at chosen cells (lbm_run_probes).  A flavour of its own, like
+                                  // kRegSnap: one word per cell in LDS, on a sample step one 16-byte store per PROBE and nothing else
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
 // Per-step forces of a whole-run launch with kRegForce: partials[step][slot][8] (8 = four labels x two components, the
@@ -124,6 +126,11 @@ struct RegTileArgs {
   // ---- forces (lbm_run_forces, flavour kRegForce only): fslot[tile] = the tile's slot, or -1 for a tile without a blocked
   // labelled cell next to fluid; fwords[slot][ty][64] = per cell mask | label << 8 (0: not counted); the tile's halved sums
   // of step s go to fpart[s - 1][slot][2 (label - 1) + component]
+  // ---- probes (lbm_run_probes, flavour kRegProbe only) use the same members, so that the arguments of every other flavour
+  // keep their size and place: fslot[tile] = the tile's slot, or -1 for a tile without a probe; fwords[slot][ty][64] = per
+  // cell its probe's index + 1 (0: no probe); snap + j snap_stride + 4 index is where the probe's fields of sample j go
+  // (snap_stride = 4 x the number of probes of the WHOLE set: the index is global, every slab stores into the same rows);
+  // every, density as for snapshots; fpart, nslots unused
   const int* fslot; const uint32_t* fwords; float* fpart; int nslots;
 };
 
@@ -135,6 +142,9 @@ __host__ __device__ constexpr int regtile_lds_bytes_force(int nw, int r) { retur
 // ... of the kRegMean flavour: behind those, the sums of u_x, u_y, |u| of every cell, [wave][R][3][64] (the pressure's sum
 // is a register per row: all four in LDS would miss the CU's 160 KB by 320 bytes on the 16 x 4 tiling)
 __host__ __device__ constexpr int regtile_lds_bytes_mean(int nw, int r) { return regtile_lds_bytes(nw, r) + 4 * nw * r * 3 * 64; }
+
+// ... of the kRegProbe flavour: behind those, the cells' probe words [wave][R][64]
+__host__ __device__ constexpr int regtile_lds_bytes_probe(int nw, int r) { return regtile_lds_bytes(nw, r) + 4 * nw * r * 64; }
 
 // bytes of one mailbox (one tile, one parity): Sin[64], Nin[64], Win[ty+2], Ein[ty+2] granules of 16 bytes
 __host__ __device__ constexpr int regtile_box(int ty) { return 16 * (2 * 64 + 2 * (ty + 2)); }
@@ -164,7 +174,8 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool SNAP = (MODE & kRegSnap) != 0;
   constexpr bool FORCE = (MODE & kRegForce) != 0;
   constexpr bool MEAN = (MODE & kRegMean) != 0;
-  static_assert(!(MEAN && (SNAP || FORCE)), "one flavour per launch");
+  constexpr bool PROBE = (MODE & kRegProbe) != 0;
+  static_assert(!(MEAN && (SNAP || FORCE)) && !(PROBE && (SNAP || FORCE || MEAN)), "one flavour per launch");
   // The mail of the loop issued and waited for BY HAND (R > 1): see "the asynchronous loop" below
   constexpr bool ASYNC = (MODE & kRegAsync) != 0 && R > 1;
   static_assert(R == 1 || R == 2 || R == 4, "rows per wave");
@@ -178,7 +189,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   const int nw_ = (int)(blockDim.x >> 6);
   float* red = lds + nw_ * (2 * 6 * 64 + (R == 4 ? R * 3 * 64 : 0));
   uint32_t* lds_abort = reinterpret_cast<uint32_t*>(red + 32);
-  long long* lds_snap = reinterpret_cast<long long*>(red + 34);     // [1] snap_stride (MEAN: nx), [2] every | density << 32 (red + 36 .. 39)
+  long long* lds_snap = reinterpret_cast<long long*>(red + 34);     // [1] snap_stride (MEAN: nx; PROBE: 4 x probes), [2] every | density << 32 (red + 36 .. 39)
   long long* lds_snap_at = reinterpret_cast<long long*>(red + 48);  // [wave]: where its next snapshot goes (MEAN: the means) (red + 48 .. 79)
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -226,7 +237,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   const int rho0 = w * R;                                   // tile row of this wave's first row
   const int gx = bx * 64 + lane, gy0 = by * TY + rho0;
   if (tid == 0) *lds_abort = 0u;
-  if constexpr (SNAP || MEAN) {
+  if constexpr (SNAP || MEAN || PROBE) {
     if (tid == 0) { lds_snap[1] = MEAN ? (long long)a.nx : a.snap_stride; lds_snap[2] = (long long)(unsigned)a.every | ((long long)__float_as_uint(a.density) << 32); }
     if (lane == 0) lds_snap_at[w] = (long long)a.snap;
   }
@@ -286,6 +297,32 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       float* dst = a.fpart + (step * a.nslots + fs) * 8;
       dst[lane >> 4] = u0; dst[4 + (lane >> 4)] = u1;
     }
+  };
+  // probes (PROBE): the tile's slot (-1: no probe in it); the rows' words in LDS behind the tile's other LDS (pw, where the force
+  // flavour keeps its own); prow = bit r: row r of this wave holds a probe -- wave-uniform, so that on a sample step a row
+  // without one costs one scalar branch and a tile without one nothing but the `sample` test
+  uint32_t* pw = fw;
+  uint32_t prow = 0u;
+  if constexpr (PROBE) {
+    const int ps = __builtin_amdgcn_readfirstlane(a.fslot[tile]);
+    if (ps >= 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint32_t wd = a.fwords[((long)ps * TY + rho0 + r) * 64 + lane];
+        pw[(w * R + r) * 64 + lane] = wd;
+        if (__any(wd != 0u)) prow |= 1u << r;
+      }
+    }
+    prow = __builtin_amdgcn_readfirstlane(prow);
+  }
+  // a probed row on a sample step (p = the row after collide_cell, as a snapshot would store it): the fields snap_row gives,
+  // one 16-byte nontemporal store from each lane that holds a probe into its place of the sample's row, nothing from the others
+  auto probe_row = [&](int r, const float (&p)[9], bool b) {
+    const uint32_t wd = pw[(w * R + r) * 64 + lane];
+    float rho;
+    const f4a v = derive_cell(p, b, __uint_as_float((unsigned)(lds_snap[2] >> 32)), rho);
+    float* at = reinterpret_cast<float*>(lds_snap_at[w]);
+    if (wd != 0u) __builtin_nontemporal_store(v, reinterpret_cast<f4a*>(at + 4 * (long)(wd - 1u)));
   };
   // planes 0, 1, 3 of row r: in LDS where the registers are short (four rows per wave), in f otherwise
   constexpr bool OWN_LDS = (R == 4);
@@ -605,7 +642,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       for (int s = 1; s <= a.nsteps; ++s) {
         int par = (s - 1) & 1;
         asm volatile("" : "+s"(par));
-        const bool sample = (SNAP || MEAN) && --snap_left == 0;
+        const bool sample = (SNAP || MEAN || PROBE) && --snap_left == 0;
         const unsigned pb = (unsigned)par * BOX, pbn = BOX - pb;
         const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
@@ -691,7 +728,12 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           // with the loads, in issue order (MI355X_MICROARCH.md, vmcnt): one more operation younger than a pending fetch makes
           // the counted vmcnt(N) that retires it wait for MORE, never less -- the fixed counts stay safe, a sample step may
           // wait a little longer.  Nothing the asm loads write is read here.
-          if (sample) { if constexpr (MEAN) mean_row(RC{}, p, blk[r]); else snap_row(r, p, blk[r]); }
+          // (a probe's store, PROBE, stands where the snapshot's does: the same argument, from fewer lanes and fewer rows)
+          if (sample) {
+            if constexpr (MEAN) mean_row(RC{}, p, blk[r]);
+            else if constexpr (PROBE) { if ((prow >> r) & 1u) probe_row(r, p, blk[r]); }
+            else snap_row(r, p, blk[r]);
+          }
           // forces (a row with a labelled cell only): LDS and DPP work and lane 0's LDS add, no vector-memory operation --
           // the counted vmcnt waits see exactly the operations they see without it
           if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
@@ -768,7 +810,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   for (int s = 1; s <= a.nsteps; ++s) {
     int par = (s - 1) & 1;                         // parity of the state being pulled
     asm volatile("" : "+s"(par));                  // (keeps both parities' addresses from being hoisted into registers)
-    const bool sample = (SNAP || MEAN) && --snap_left == 0;
+    const bool sample = (SNAP || MEAN || PROBE) && --snap_left == 0;
     const unsigned pb = (unsigned)par * BOX, pbn = BOX - pb;
     const uint32_t want = a.tag0 + (uint32_t)(s - 1), tagn = want + 1u;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's edge rows of state s-1 are in LDS
@@ -835,7 +877,11 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
       sp += collide_cell<FAST, true>(p, blk[r], a.omega);
       // snapshot (wave-uniform step), before the next step's accelerate.  Behind the fetch of the next row's mail: on a sample
       // step the compiler's wait for that mail also waits for this store (no counted waits here to keep exact)
-      if (sample) { if constexpr (MEAN) mean_row(rc, p, blk[r]); else snap_row(r, p, blk[r]); }
+      if (sample) {
+        if constexpr (MEAN) mean_row(rc, p, blk[r]);
+        else if constexpr (PROBE) { if ((prow >> r) & 1u) probe_row(r, p, blk[r]); }
+        else snap_row(r, p, blk[r]);
+      }
       if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
       if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
       f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];

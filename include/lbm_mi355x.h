@@ -200,6 +200,39 @@ int lbm_set_bodies(lbm_ctx* ctx, const int* body, int nbodies);
    untouched when no bodies are set or forces is NULL with nsteps > 0; LBM_ENOMEM likewise when the partials do not fit. */
 int lbm_run_forces(lbm_ctx* ctx, int nsteps, float* av_vels, float* forces);
 
+/*
+ * Time series at chosen cells: u_x, u_y, |u| and pressure of a set of probes after every sample step of a run (pressure
+ * taps on a body, a velocity probe in a wake, a monitor point, a line of cells across the channel).
+ */
+#define LBM_MAX_PROBES 4096
+/* xy: int[nprobes][2] = (ii, jj), column and row in the GLOBAL lattice (in both modes).  Replaces any earlier set;
+   nprobes = 0 clears it (xy may then be NULL).  Blocked cells are legal probes.  The set survives runs of every kind,
+   lbm_set_bodies and option changes (a new "regtile" tiling rebuilds the register tiles' per-tile tables at the next
+   lbm_run_probes).  LBM_EINVAL (the earlier set kept) when nprobes is outside [0, LBM_MAX_PROBES], xy is NULL with
+   nprobes > 0, a coordinate is outside the lattice, or two entries name the same cell (the message says which two);
+   LBM_ENOMEM (the earlier set kept) when the per-slab lists do not fit on the device. */
+int lbm_set_probes(lbm_ctx* ctx, const int* xy, int nprobes);
+/* lbm_run that also writes probes_out[m][nprobes][4] = u_x, u_y, |u|, pressure of every probe after steps
+   every, 2 every, ..., m every (m = nsteps / every).
+   Definition, bit for bit: probes_out[j][p][:] equals fields_out[j][jj_p][ii_p][:] of
+   lbm_run_sampled(ctx, nsteps, av_vels, every, fields_out) from the same state; a blocked cell reads the constant
+   0, 0, 0, density / 3.  Probes keep the order in which they were given.  av_vels, the lattice and everything after the
+   call are bit-identical to lbm_run(ctx, nsteps, av_vels) (where the streaming engines run in pieces, av_vels as for
+   lbm_run_sampled / lbm_run_mean on those engines).  probes_out: host memory, or device memory of the device that holds
+   every slab of the context (then nothing is copied to the host).
+   Rank contexts: xy is global on every rank; each rank fills the entries of the probes that lie in its own rows
+   (lbm_slab_rows) and writes +0.0f to the others; no communication is added.  Combining the ranks' arrays is the caller's
+   business: a float sum turns a probe's -0.0f into +0.0f, so selecting each entry from the rank that owns its row is the
+   bit-exact way.
+   The register-tile engines take the values inside their kernels (info "probes_in_kernel" = 1): a sample step moves 16
+   bytes per probe and nothing else.  The other engines run the steps in pieces of `every` with a small gather kernel
+   behind each (correct, not fast; the same bits).
+   LBM_EINVAL with nothing queued and the lattice untouched when no probes are set, every <= 0, nsteps < 0, m = 0 or
+   probes_out is NULL; LBM_ENOMEM likewise when the device staging of host output (16 m nprobes bytes per slab that holds
+   a probe) or the register tiles' tables do not fit.  Rank contexts agree on both before anything is queued.
+   Not combined with snapshots, forces or means in one call. */
+int lbm_run_probes(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* probes_out);
+
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
 int lbm_last_run_ms(const lbm_ctx* ctx, double* gpu_ms, double* wall_ms);
@@ -256,7 +289,8 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * form of the speed sum, d2q9-bgk.c:1783-1811, 256 one-step kernel only), "vector_width", "t2_threads".
  * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
  * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
- * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles),
+ * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */
