@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
-    "lbm_set_probes", "lbm_run_probes",
+    "lbm_set_probes", "lbm_run_probes", "lbm_run_observed",
     "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
@@ -58,6 +58,12 @@ class Param(C.Structure):
     def __repr__(self):
         return ("Param(nx=%d, ny=%d, maxIters=%d, reynolds_dim=%d, density=%g, accel=%g, omega=%g)"
                 % (self.nx, self.ny, self.maxIters, self.reynolds_dim, self.density, self.accel, self.omega))
+
+
+class Observe(C.Structure):
+    """Field-for-field lbm_observe (include/lbm_mi355x.h): a NULL pointer = that observer is not wanted."""
+    _fields_ = [("forces", C.c_void_p), ("probes_out", C.c_void_p), ("mean_out", C.c_void_p), ("fields_out", C.c_void_p),
+                ("probes_every", C.c_int), ("mean_every", C.c_int), ("fields_every", C.c_int)]
 
 
 _lib = None
@@ -95,6 +101,7 @@ def load_library():
     lib.lbm_set_probes.argtypes = [vp, vp, C.c_int]
     lib.lbm_run_probes.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_run_forces.argtypes = [vp, C.c_int, vp, vp]
+    lib.lbm_run_observed.argtypes = [vp, C.c_int, vp, C.POINTER(Observe)]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
@@ -299,6 +306,51 @@ class Lattice:
         forces = np.empty((max(nsteps, 0), nb, 2), dtype=np.float32)
         _check(self._lib.lbm_run_forces(self._ctx, nsteps, av.ctypes.data, forces.ctypes.data if forces.size else None))
         return av, forces
+
+    def _output(self, out, shape, name):
+        """(array or tensor, pointer) of one output of run_observed: a fresh numpy array, or `out`, validated as the single
+        calls validate theirs."""
+        if out is None:
+            arr = np.empty(shape, dtype=np.float32)
+            return arr, (arr.ctypes.data if arr.size else None)
+        import torch
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
+                or not out.is_contiguous() or tuple(out.shape) != shape):
+            raise LbmError(f"{name} must be a contiguous float32 CUDA tensor of shape {shape}")
+        torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        return out, (out.data_ptr() if out.numel() else None)
+
+    def run_observed(self, nsteps: int, forces: bool = False, probes_every: int = 0, mean_every: int = 0,
+                     fields_every: int = 0, probes_out=None, mean_out=None, fields_out=None):
+        """lbm_run with any subset of the observers in ONE run: forces=True (run_forces), probes_every > 0 (run_probes),
+        mean_every > 0 (run_mean), fields_every > 0 (run_sampled).  Returns a dict with "av_vels" and one entry per wanted
+        observer -- "forces", "probes", "mean", "fields" -- each the bits its own call returns: numpy arrays, or the
+        contiguous float32 CUDA tensors given as probes_out / mean_out / fields_out, filled on the GPU."""
+        n = max(nsteps, 0)
+        av = np.empty(n, dtype=np.float32)
+        res = {"av_vels": av}
+        what = Observe()
+        if forces:
+            f = np.empty((n, getattr(self, "_nbodies", 0), 2), dtype=np.float32)
+            res["forces"] = f
+            what.forces = f.ctypes.data if f.size else av.ctypes.data    # (wanted, but nothing to write: any non-NULL pointer)
+        rows, nx = self._local_rows(), self.params.nx
+        if probes_every != 0 or probes_out is not None:
+            shape = (n // probes_every if probes_every > 0 else 0, getattr(self, "_nprobes", 0), 4)
+            res["probes"], ptr = self._output(probes_out, shape, "probes_out")
+            what.probes_out = ptr if ptr is not None else av.ctypes.data
+            what.probes_every = probes_every
+        if mean_every != 0 or mean_out is not None:
+            res["mean"], ptr = self._output(mean_out, (rows, nx, 4), "mean_out")
+            what.mean_out = ptr
+            what.mean_every = mean_every
+        if fields_every != 0 or fields_out is not None:
+            shape = (n // fields_every if fields_every > 0 else 0, rows, nx, 4)
+            res["fields"], ptr = self._output(fields_out, shape, "fields_out")
+            what.fields_out = ptr if ptr is not None else av.ctypes.data
+            what.fields_every = fields_every
+        _check(self._lib.lbm_run_observed(self._ctx, nsteps, av.ctypes.data if n else None, C.byref(what)))
+        return res
 
     def last_run_ms(self):
         g, w = C.c_double(0), C.c_double(0)

@@ -204,6 +204,10 @@ struct Slab {
   int* pslot = nullptr;
   uint32_t* pwords = nullptr;
   int pty = 0;
+  // lbm_run_observed, probes without forces in the kRegForce | kRegProbe flavour: a force slot table of fslot_none_n tiles
+  // that are all -1 (no tile counts anything)
+  int* fslot_none = nullptr;
+  int fslot_none_n = 0;
 };
 
 }  // namespace
@@ -245,6 +249,8 @@ struct lbm_ctx {
   int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
   int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
   int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
+  int observed_in_kernel = 0;  // the last lbm_run_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
+  int observed_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
   int nbodies = 0;             // lbm_set_bodies (0: none)
   int nprobes = 0;             // lbm_set_probes (0: none)
   // obstacle map of the local rows and one row either side (global rows keep_row0 .. keep_row0 + keep_rows - 1, taken
@@ -635,7 +641,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   const float a1 = c->p.density * c->p.accel / 9.f;   // d2q9-bgk.c:230-231
   const float a2 = c->p.density * c->p.accel / 36.f;
   const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour, else the one-step kernel, lbm_body_forces behind each step
-  if ((!fo || k.force_tiles) && regtile_is_next(c)) {
+  if (!k.no_tiles && (!fo || k.force_tiles) && regtile_is_next(c)) {
     bool done = false;
     int rr = run_regtile(c, nsteps, av_vels, &done, k);
     if (rr && c->engine == 0) {
@@ -652,9 +658,11 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
       else if (k.snap && k.mean) c->mean_in_kernel = 1;
       else if (k.snap) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
+      if (k.ran) *k.ran = true;
       return LBM_OK;
     }
   }
+  if (k.piece) return LBM_OK;   // (lbm_run_observed: nothing stepped; it runs the piece again off the tiles)
   if (c->engine >= 2 && !fo) return fail(LBM_EINVAL, "the register tiles cannot run here (%s), or this lattice has no register tiling (engine = %d)",
                                          c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
   if (k.snap) return LBM_OK;
@@ -1301,6 +1309,8 @@ static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, 
   return LBM_OK;
 }
 
+#include "lbm_host_observe.inc"
+
 extern "C" int lbm_av_velocity(lbm_ctx* c, float* out) {
   if (!c || !out) return fail(LBM_EINVAL, "NULL argument");
   double sp = 0.0;
@@ -1477,6 +1487,8 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
   if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
   if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "observed_pieces")) { *value = c->observed_pieces; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first
     *value = regtile_is_next(c) ? 3 : 1;
     return LBM_OK;

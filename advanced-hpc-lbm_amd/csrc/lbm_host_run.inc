@@ -19,6 +19,12 @@ struct SnapPlan {
 // probe (lbm_run_probes, with snap): as snap, but the kRegProbe flavour -- snap->at[i] is row 0 of the output slab i stores
 // into, stride[i] the floats from one sample's row to the next (4 x the probes of the whole set); the slabs' probe tables
 // (probe_tables) are in place.
+// piece (lbm_run_observed): a piece of a longer call -- ONLY the register tiles are tried, in their kRegForce | kRegProbe
+// flavour, which alone keeps the probes' phase (snap and probe: the first sample pfirst steps into the piece, 1 .. every)
+// and stores the last step's speed sums folded like any other step's (piece_mid, not the last piece of the call: those are the ones used).  Forces beside them
+// when nb > 0 and force_tiles; an observer that is not wanted gets the table of -1s (Slab::fslot_none: no tile counts or
+// stores anything).  *ran tells the caller whether the tiles ran the piece (false with LBM_OK: nothing stepped, nothing of
+// the piece's output is valid).  no_tiles: the register tiles are not tried.
 struct RunKind {
   const SnapPlan* snap = nullptr;
   bool mean = false;
@@ -26,6 +32,9 @@ struct RunKind {
   int nb = 0;
   long nval = 0;
   bool force_tiles = false;
+  bool piece = false, piece_mid = false, no_tiles = false;
+  int pfirst = 0;
+  bool* ran = nullptr;
 };
 
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the
@@ -296,6 +305,7 @@ auto regtile_kernel(int r, bool fast, bool async, int flavour) {
   if (flavour == lbm::kRegForce) return regtile_flavour<SLAB, lbm::kRegForce>(r, fast, async);
   if (flavour == lbm::kRegMean) return regtile_flavour<SLAB, lbm::kRegMean>(r, fast, async);
   if (flavour == lbm::kRegProbe) return regtile_flavour<SLAB, lbm::kRegProbe>(r, fast, async);
+  if (flavour == (lbm::kRegForce | lbm::kRegProbe)) return regtile_flavour<SLAB, lbm::kRegForce | lbm::kRegProbe>(r, fast, async);
   return regtile_flavour<SLAB, 0>(r, fast, async);
 }
 
@@ -382,14 +392,15 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const bool fk = k.nb > 0 && k.force_tiles;            // lbm_run_forces: the kRegForce flavour, with its larger LDS
   const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
   const bool pk = k.snap && k.probe;                    // lbm_run_probes: the kRegProbe flavour, with its larger LDS
-  const int flavour = fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : 0;
+  const bool fpk = k.piece;                             // lbm_run_observed: the kRegForce | kRegProbe flavour (forces counted when fk)
+  const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : 0;
   auto kernel = [&](int fl) {
     return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
                 : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
   };
   const dim3 block(64 * t.nw);
   const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const unsigned shm_run = fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : mk ? (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r)
+  const unsigned shm_run = fpk ? (unsigned)lbm::regtile_lds_bytes_force_probe(t.nw, t.r) : fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : mk ? (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r)
                                                                                     : pk ? (unsigned)lbm::regtile_lds_bytes_probe(t.nw, t.r) : shm;
   static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run
   const bool stats = lone && want_stats;
@@ -448,10 +459,10 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   // buffers: the mail areas, the per-step tile sums, the groups' abort words, the table of arguments
   for (auto& s : c->slabs) {
     if ((rc = regtile_mail_alloc(c, s))) return rc;
-    if (s.rpartials_cap < nsteps) {
+    if (s.rpartials_cap < nsteps + (fpk ? 1 : 0)) {               // (the force + probe flavour: one row more, see RegTileArgs::pfirst)
       HIPC(hipSetDevice(s.dev));
       long cap = std::max(1024L, s.rpartials_cap);
-      while (cap < nsteps) cap *= 2;
+      while (cap < nsteps + (fpk ? 1 : 0)) cap *= 2;
       if (s.rpartials) HIPC(hipFree(s.rpartials));
       s.rpartials = nullptr; s.rpartials_cap = 0;
       HIPC(hipMalloc((void**)&s.rpartials, sizeof(float) * (size_t)cap * ntiles));
@@ -508,7 +519,10 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       a.snap = k.snap ? k.snap->at[i] : nullptr; a.snap_stride = k.snap ? k.snap->stride[i] : 0; a.every = k.snap ? k.snap->every : 0;
       a.density = c->p.density;
       a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
-      if (pk) { a.fslot = s.pslot; a.fwords = s.pwords; a.fpart = nullptr; a.nslots = 0; }   // (the probe flavour's tables: same members)
+      if (pk && !fpk) { a.fslot = s.pslot; a.fwords = s.pwords; a.fpart = nullptr; a.nslots = 0; }   // (the probe flavour's tables: same members)
+      a.pfirst = k.pfirst; a.pslot = s.pslot; a.pwords = s.pwords;   // (the force + probe flavour's)
+      if (fpk && !pk) { a.pslot = s.fslot_none; a.pwords = nullptr; a.pfirst = 0x7fffffff; }   // (... with no probe wanted: no tile samples)
+      if (fpk && !fk) { a.fslot = s.fslot_none; a.fwords = nullptr; a.fpart = nullptr; a.nslots = 0; }   // (... with no force wanted: no tile counts)
       if (c->rank_mode && c->nranks > 1) {
         a.mail_s = s.tmail_nb[0]; a.mail_n = s.tmail_nb[1];
         a.mail_bytes_s = (unsigned)s.tmail_nb_bytes[0]; a.mail_bytes_n = (unsigned)s.tmail_nb_bytes[1];
@@ -547,6 +561,9 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
     for (int q = gstart[g]; q < gstart[g + 1]; ++q) {
       Slab& s = c->slabs[order[q]];
       if (q > gstart[g]) HIPC(hipStreamWaitEvent(s.sc, l.ev_rt, 0));
+      if (fpk && k.piece_mid)           // a piece, not the call's last: its last step's tile sums as the loop folds them
+        HIPC(hipMemcpyAsync(s.rpartials + (size_t)(nsteps - 1) * ntiles, s.rpartials + (size_t)nsteps * ntiles, sizeof(float) * ntiles,
+                            hipMemcpyDeviceToDevice, s.sc));
       hipLaunchKernelGGL(lbm::lbm_fold_steps, dim3(cdiv(nsteps, lbm::kBlock / 64)), dim3(lbm::kBlock), 0, s.sc,
                          s.rpartials, ntiles, nsteps, s.sums, l.rabort, s.err_host + 1);
       HIPC(hipGetLastError());

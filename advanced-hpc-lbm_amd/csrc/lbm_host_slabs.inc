@@ -361,6 +361,7 @@ void slab_free(Slab& s) {
   if (s.blocked) (void)hipFree(s.blocked);
   if (s.fcells) (void)hipFree(s.fcells);
   if (s.fslot) (void)hipFree(s.fslot);
+  if (s.fslot_none) (void)hipFree(s.fslot_none);
   if (s.fwords) (void)hipFree(s.fwords);
   if (s.pcells) (void)hipFree(s.pcells);
   if (s.pslot) (void)hipFree(s.pslot);

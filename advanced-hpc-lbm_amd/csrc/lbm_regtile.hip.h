@@ -132,6 +132,17 @@ struct RegTileArgs {
   // (snap_stride = 4 x the number of probes of the WHOLE set: the index is global, every slab stores into the same rows);
   // every, density as for snapshots; fpart, nslots unused
   const int* fslot; const uint32_t* fwords; float* fpart; int nslots;
+  // ---- forces AND probes in one launch (lbm_run_observed, flavour kRegForce | kRegProbe only): the force members above keep
+  // their meaning, the probes' tables are pslot / pwords (laid out as the probe flavour's fslot / fwords); snap, snap_stride,
+  // every, density as for the probe flavour; pfirst = steps to the first sample (1 .. every: a piece of a longer call that
+  // starts s0 steps into it passes every - s0 mod every; a piece without probes: a table of -1s and a pfirst beyond nsteps).
+  // This flavour also stores the tile's speed sum of the LAST step a second time, folded as the loop folds every other
+  // step's (wave_sum_dpp; the epilogue of a whole run folds with wave_sum: another order of additions, the last bit may
+  // differ), into partials[nsteps][tile] -- one row beyond the run's: the host moves it over row nsteps - 1 when the launch
+  // is a piece that is not the last of its call, so that av_vels of a call does not depend on where it is cut.
+  // At the END, so that every member above keeps its place.
+  int pfirst;
+  const int* pslot; const uint32_t* pwords;
 };
 
 // LDS bytes of a block of nw waves with r rows per wave (see the kernel)
@@ -145,6 +156,9 @@ __host__ __device__ constexpr int regtile_lds_bytes_mean(int nw, int r) { return
 
 // ... of the kRegProbe flavour: behind those, the cells' probe words [wave][R][64]
 __host__ __device__ constexpr int regtile_lds_bytes_probe(int nw, int r) { return regtile_lds_bytes(nw, r) + 4 * nw * r * 64; }
+
+// ... of the kRegForce | kRegProbe flavour: behind the force flavour's words and sums, the cells' probe words [wave][R][64]
+__host__ __device__ constexpr int regtile_lds_bytes_force_probe(int nw, int r) { return regtile_lds_bytes_force(nw, r) + 4 * nw * r * 64; }
 
 // bytes of one mailbox (one tile, one parity): Sin[64], Nin[64], Win[ty+2], Ein[ty+2] granules of 16 bytes
 __host__ __device__ constexpr int regtile_box(int ty) { return 16 * (2 * 64 + 2 * (ty + 2)); }
@@ -175,7 +189,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool FORCE = (MODE & kRegForce) != 0;
   constexpr bool MEAN = (MODE & kRegMean) != 0;
   constexpr bool PROBE = (MODE & kRegProbe) != 0;
-  static_assert(!(MEAN && (SNAP || FORCE)) && !(PROBE && (SNAP || FORCE || MEAN)), "one flavour per launch");
+  static_assert(!(MEAN && (SNAP || FORCE)) && !(PROBE && (SNAP || MEAN)), "one flavour per launch, or forces with probes");
   // The mail of the loop issued and waited for BY HAND (R > 1): see "the asynchronous loop" below
   constexpr bool ASYNC = (MODE & kRegAsync) != 0 && R > 1;
   static_assert(R == 1 || R == 2 || R == 4, "rows per wave");
@@ -299,16 +313,18 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     }
   };
   // probes (PROBE): the tile's slot (-1: no probe in it); the rows' words in LDS behind the tile's other LDS (pw, where the force
-  // flavour keeps its own); prow = bit r: row r of this wave holds a probe -- wave-uniform, so that on a sample step a row
+  // flavour keeps its own; with FORCE: behind the force words and sums, and the tables are pslot / pwords); prow = bit r: row r of this wave holds a probe -- wave-uniform, so that on a sample step a row
   // without one costs one scalar branch and a tile without one nothing but the `sample` test
-  uint32_t* pw = fw;
+  uint32_t* pw = FORCE ? reinterpret_cast<uint32_t*>(frc + 2 * nw_ * 8) : fw;
   uint32_t prow = 0u;
   if constexpr (PROBE) {
-    const int ps = __builtin_amdgcn_readfirstlane(a.fslot[tile]);
+    const int* ptile = FORCE ? a.pslot : a.fslot;
+    const uint32_t* pwords = FORCE ? a.pwords : a.fwords;
+    const int ps = __builtin_amdgcn_readfirstlane(ptile[tile]);
     if (ps >= 0) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const uint32_t wd = a.fwords[((long)ps * TY + rho0 + r) * 64 + lane];
+        const uint32_t wd = pwords[((long)ps * TY + rho0 + r) * 64 + lane];
         pw[(w * R + r) * 64 + lane] = wd;
         if (__any(wd != 0u)) prow |= 1u << r;
       }
@@ -639,6 +655,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         if constexpr (D > 1) afetch(std::integral_constant<int, UP ? 1 : R - 2>{}, pb0, slot[1]);
       }
       int snap_left = a.every;                       // (SNAP) steps to the next snapshot (never 0 again when every = 0)
+      if constexpr (FORCE && PROBE) snap_left = a.pfirst;   // (a piece of a longer call: its first sample keeps the call's phase)
       for (int s = 1; s <= a.nsteps; ++s) {
         int par = (s - 1) & 1;
         asm volatile("" : "+s"(par));
@@ -790,6 +807,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     }
     if (tid < 64) {
       float v = (lane < nw) ? red[(a.nsteps & 1) * 16 + lane] : 0.f;
+      if constexpr (FORCE && PROBE) { const float vd = wave_sum_dpp(v); if (tid == 0) a.partials[(long)a.nsteps * nt + tile] = vd; }   // (for a piece: see pfirst)
       v = wave_sum(v);
       if (tid == 0) a.partials[(long)(a.nsteps - 1) * nt + tile] = v;
       if (FORCE && fs >= 0) force_out(a.nsteps - 1, a.nsteps & 1);
@@ -807,6 +825,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
 
   bool aborted = false;
   int snap_left = a.every;                         // (SNAP) steps to the next snapshot (never 0 again when every = 0)
+  if constexpr (FORCE && PROBE) snap_left = a.pfirst;     // (a piece of a longer call: its first sample keeps the call's phase)
   for (int s = 1; s <= a.nsteps; ++s) {
     int par = (s - 1) & 1;                         // parity of the state being pulled
     asm volatile("" : "+s"(par));                  // (keeps both parities' addresses from being hoisted into registers)
@@ -951,6 +970,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   }
   if (tid < 64) {
     float v = (lane < nw) ? red[(a.nsteps & 1) * 16 + lane] : 0.f;
+    if constexpr (FORCE && PROBE) { const float vd = wave_sum_dpp(v); if (tid == 0) a.partials[(long)a.nsteps * nt + tile] = vd; }     // (for a piece: see pfirst)
     v = wave_sum(v);
     if (tid == 0) a.partials[(long)(a.nsteps - 1) * nt + tile] = v;
     if (FORCE && fs >= 0) force_out(a.nsteps - 1, a.nsteps & 1);

@@ -147,6 +147,7 @@ int lbm_run(lbm_ctx* ctx, int nsteps, float* av_vels);
  * copied to the host).  The register-tile engines write the snapshots from inside their kernels (info
  * "samples_in_kernel" = 1); the other engines run the steps in pieces with a derive after each.  LBM_ENOMEM /
  * LBM_EINVAL before anything runs when the device staging or the snapshots do not fit: the lattice is untouched.
+ * With forces, probes or means in one run: lbm_run_observed.
  */
 int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* fields_out);
 
@@ -167,7 +168,7 @@ int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* 
  * buffer (16 bytes per cell) does not fit; in both cases before anything runs: the lattice is untouched.
  * A window that starts late is lbm_run(ctx, skip, ...) followed by lbm_run_mean; the means of consecutive calls can be
  * combined by the caller in double (weights m).  Accuracy: a plain float sum of m terms carries at most (m - 1) 2^-24
- * relative to the sum of |X_j| per cell.  Not combined with snapshots or forces in one call.
+ * relative to the sum of |X_j| per cell.  With snapshots, forces or probes in one run: lbm_run_observed.
  */
 int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mean_out);
 
@@ -197,7 +198,8 @@ int lbm_set_bodies(lbm_ctx* ctx, const int* body, int nbodies);
    contexts: every rank gets the global forces (without RCCL: its own contribution), as with av_vels.  The register
    tiles take the sums inside their kernels (info "forces_in_kernel" = 1); every other engine runs the one-step kernel
    with a small force kernel behind each step (correct, not fast).  LBM_EINVAL with nothing queued and the lattice
-   untouched when no bodies are set or forces is NULL with nsteps > 0; LBM_ENOMEM likewise when the partials do not fit. */
+   untouched when no bodies are set or forces is NULL with nsteps > 0; LBM_ENOMEM likewise when the partials do not fit.
+   With snapshots, probes or means in one run: lbm_run_observed. */
 int lbm_run_forces(lbm_ctx* ctx, int nsteps, float* av_vels, float* forces);
 
 /*
@@ -230,8 +232,46 @@ int lbm_set_probes(lbm_ctx* ctx, const int* xy, int nprobes);
    LBM_EINVAL with nothing queued and the lattice untouched when no probes are set, every <= 0, nsteps < 0, m = 0 or
    probes_out is NULL; LBM_ENOMEM likewise when the device staging of host output (16 m nprobes bytes per slab that holds
    a probe) or the register tiles' tables do not fit.  Rank contexts agree on both before anything is queued.
-   Not combined with snapshots, forces or means in one call. */
+   With snapshots, forces or means in one run: lbm_run_observed. */
 int lbm_run_probes(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* probes_out);
+
+/*
+ * One run, any subset of the four observers: drag and lift per step (lbm_run_forces), time series at the probes
+ * (lbm_run_probes), time-averaged fields (lbm_run_mean) and snapshots (lbm_run_sampled) of the SAME steps.
+ * Layout (plain C, LP64): sizeof(lbm_observe) = 48; offsets forces 0, probes_out 8, mean_out 16, fields_out 24,
+ * probes_every 32, mean_every 36, fields_every 40 (4 bytes of padding at the end).
+ */
+typedef struct {
+  float* forces;       /* [nsteps][nbodies][2] as lbm_run_forces, or NULL: not wanted                       */
+  float* probes_out;   /* [nsteps / probes_every][nprobes][4] as lbm_run_probes, or NULL                     */
+  float* mean_out;     /* [rows][nx][4] as lbm_run_mean, or NULL                                             */
+  float* fields_out;   /* [nsteps / fields_every][rows][nx][4] as lbm_run_sampled, or NULL                   */
+  int probes_every, mean_every, fields_every;   /* read only where the pointer beside it is not NULL         */
+} lbm_observe;
+/* An observer is wanted exactly when its pointer is not NULL; what == NULL, or all four NULL: exactly lbm_run.
+   The three periods are independent (probes every step, means every 10, a snapshot every 500); sample steps count from
+   the start of the call, as in the single calls.
+   Each output is, bit for bit, what its own call (lbm_run_forces, lbm_run_probes, lbm_run_mean, lbm_run_sampled) writes
+   from the same state with the same options, bodies, probes and period: the rank-local conventions (rows of
+   lbm_final_state; probes of other ranks' rows read +0.0f; forces global through the run's all-reduce, or the rank's
+   contribution without RCCL), host or device memory per pointer, independently (forces: host memory), and the -0
+   handling of the mean included.
+   The lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels).  av_vels is bit-identical
+   to lbm_run's wherever the register tiles ran the call (info "engine_last" = 3), in one launch or in pieces; on the
+   streaming engines it is equal to lbm_run's within float rounding of the per-step sum, as for lbm_run_forces there.
+   How: forces with probes ride inside one register-tile launch (a kernel flavour of its own); means and snapshots -- and
+   probes where the register tiles do not run -- are taken behind pieces of the step loop that end on their sample steps
+   (each piece a launch of that flavour), by the small kernels the single calls fall back to (a 1024 x 1024 run with forces and mean_every = 100 stays on the
+   register tiles and pays their per-run fixed cost once per 100 steps).  One observer alone simply runs its own call.
+   Info "observed_in_kernel": bits 1 forces, 2 probes, 4 means, 8 snapshots -- what the last lbm_run_observed took inside
+   register-tile launches; "observed_pieces": the step-loop pieces it ran (1 = the whole call in one).  What the four
+   single calls' "*_in_kernel" keys read after lbm_run_observed is unspecified.  lbm_last_run_ms: the sums over the pieces.
+   LBM_EINVAL with nothing queued and the lattice untouched: nsteps < 0; forces wanted without bodies; probes wanted
+   without a probe set; probes or means wanted with every <= 0 or no sample step in nsteps; fields_every < 0 (0, or no
+   sample step: legal, nothing written); a device pointer on another device than the slabs'.  LBM_ENOMEM likewise when a
+   staging, table or partial buffer does not fit.  Rank contexts agree on room and on the path before anything is queued.
+   Overlapping observers of one kind with different periods: not offered. */
+int lbm_run_observed(lbm_ctx* ctx, int nsteps, float* av_vels, const lbm_observe* what);
 
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
@@ -290,7 +330,8 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
  * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
  * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles),
- * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles), "observed_in_kernel",
+ * "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */

@@ -7,7 +7,7 @@ that retires them (marked `; retire v[a:b] ...` in the asm text) sees -- or dest
 (cdna_hip_programming.md 5.7, item 1).  This walks the ISA of every lbm_regtile<R, MODE | kRegAsync> instantiation from each
 asm `buffer_load_dwordx4` along every path (branches followed both ways, loops once round) until the retiring statement, and
 reports every instruction outside asm statements that touches the destination registers on the way; also scratch use and
-AGPR traffic, and any asynchronous flavour the library selects (plain, kRegSnap, kRegForce, kRegMean, kRegProbe; alone and across slabs) that is
+AGPR traffic, and any asynchronous flavour the library selects (plain, kRegSnap, kRegForce, kRegMean, kRegProbe, kRegForce | kRegProbe; alone and across slabs) that is
 missing from the ISA.  Exit status 1 on any finding.
 
     python tools/audit_regtile_isa.py [file.s]      (default: compiles advanced-hpc-lbm_amd/csrc/lbm_api.hip -S for gfx950)
@@ -135,8 +135,10 @@ def main():
             i = j
         i += 1
     # the flavours the library selects must all be here: lbm_run's, the snapshots' (kRegSnap), the forces' (kRegForce), the
-    # means' (kRegMean) and the probes' (kRegProbe), alone and across slabs (kRegSlab), R = 2 and 4, with and without fast math
-    for flav, label in ((0, "plain"), (16384, "snapshot"), (32768, "force"), (65536, "mean"), (131072, "probe")):
+    # means' (kRegMean), the probes' (kRegProbe) and lbm_run_observed's forces with probes (kRegForce | kRegProbe), alone and
+    # across slabs (kRegSlab), R = 2 and 4, with and without fast math
+    for flav, label in ((0, "plain"), (16384, "snapshot"), (32768, "force"), (65536, "mean"), (131072, "probe"),
+                        (32768 | 131072, "force + probe")):
         for slab in (0, 8192):
             for r in (2, 4):
                 for fast in (0, 1):
