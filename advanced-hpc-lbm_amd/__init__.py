@@ -300,7 +300,10 @@ class Lattice:
 
     def run_forces(self, nsteps: int):
         """lbm_run that also returns the force of the fluid on every body at every step: (av_vels[nsteps],
-        forces[nsteps, nbodies, 2]) with (F_x, F_y) per body (definition: include/lbm_mi355x.h)."""
+        forces[nsteps, nbodies, 2]) with (F_x, F_y) per body (definition: include/lbm_mi355x.h).  The register tiles sum
+        them inside their kernels (info("forces_in_kernel") == 1); where lbm_wave runs they ride in its launches
+        (info("forces_in_wave") == 1: av_vels is run()'s bits, the forces are the one-step path's bits); elsewhere the
+        one-step kernel runs with a force kernel behind each step."""
         nb = getattr(self, "_nbodies", 0)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
         forces = np.empty((max(nsteps, 0), nb, 2), dtype=np.float32)

@@ -197,6 +197,12 @@ struct Slab {
   int fnslots = 0, fty = 0;
   float* fpart = nullptr;
   long fpart_cap = 0;              // floats
+  // lbm_wave's force flavour (a lattice alone; lbm_host_march.inc, wave_force_ready): the obstacle bytes with 2 on the cells
+  // of fcells, those cells' indices in fcells (dense, read at counted cells only), one group's contributions [K][fcells_n][2]
+  uint8_t* fmap = nullptr;
+  int* fidx = nullptr;
+  float* fcontrib = nullptr;
+  long fcontrib_cap = 0;           // floats
   // probes (lbm_set_probes): the slab's probes, {column, local row, index in the set}; on the device as {offset in a plane,
   // index} for lbm_probe_gather; the register tiles' tables (lbm_regtile.hip.h, kRegProbe) for tiles of pty rows (0: not built)
   std::vector<int4> pcells_host;
@@ -247,6 +253,7 @@ struct lbm_ctx {
   int engine_last = 0;         // what the last lbm_run used: 1 streaming, 3 resident in registers
   int samples_in_kernel = 0;   // 1: the snapshots of the last lbm_run_sampled came from the register tiles
   int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
+  int forces_in_wave = 0;      // 1: the last lbm_run_forces took its per-cell contributions inside lbm_wave launches
   int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
   int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
   int observed_in_kernel = 0;  // the last lbm_run_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
@@ -640,7 +647,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   const int nx = c->p.nx;
   const float a1 = c->p.density * c->p.accel / 9.f;   // d2q9-bgk.c:230-231
   const float a2 = c->p.density * c->p.accel / 36.f;
-  const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour, else the one-step kernel, lbm_body_forces behind each step
+  const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour; lbm_wave in its force flavour where lbm_run would
+                              // run it (fwave, below); else the one-step kernel, lbm_body_forces behind each step
   if (!k.no_tiles && (!fo || k.force_tiles) && regtile_is_next(c)) {
     bool done = false;
     int rr = run_regtile(c, nsteps, av_vels, &done, k);
@@ -669,8 +677,16 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels, k); }
   c->engine_last = 1;
   const bool ex = c->exchange != 0;
-  const bool pairs = !fo && t2_eligible(c) && nsteps >= 2;
   int rc;
+  // lbm_run_forces where lbm_run would run lbm_wave (a lattice alone): the groups of K steps in lbm_wave's force flavour.
+  // Decided before anything is queued; maps, contributions or partials that do not fit: the one-step path, the same bits.
+  bool fwave = false;
+  if (fo && !ex && march_eligible(c) && use_wave_kernel(c) && nsteps >= c->time_block) {
+    if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
+    fwave = (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap && wave_force_ready(c, c->time_block);
+  }
+  // (behind those groups the left-over steps go as lbm_run's do, in pairs where it takes pairs: av_vels is lbm_run's bits)
+  const bool pairs = (!fo || fwave) && t2_eligible(c) && nsteps >= 2;
 
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
@@ -770,11 +786,12 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
       if ((rc = prime_halos((li & 1) ^ 1))) return rc;
     }
   } else
-  if (!fo && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
+  if ((!fo || fwave) && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
     const int K = c->time_block, ngroups = nsteps / K;
     const bool wave = use_wave_kernel(c);
     for (int g = 0; g < ngroups; ++g, ++li, tt += K)
-      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+    if (fwave) c->forces_in_wave = 1;
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -783,8 +800,17 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   }
   if (pairs && nsteps - tt >= 2) {
     const int npairs = (nsteps - tt) / 2;
-    for (int j = 0; j < npairs; ++j, ++li, tt += 2)
+    for (int j = 0; j < npairs; ++j, ++li, tt += 2) {
+      if (fo) {
+        // (a forces run behind its lbm_wave groups, a lattice alone) the pair's first step alone into the destination
+        // lattice, for its forces -- its speed sums go unused -- then the pair from the same source over it
+        if ((rc = launch_single(c, li, tt, true, false, a1, a2))) return rc;
+        if ((rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
+        c->cur ^= 1;
+      }
       if ((rc = launch_pair(c, li, tt, tt + 2 < nsteps, j > 0, a1, a2))) return rc;
+      if (fo && (rc = launch_forces(c, tt + 1, li & 1, nsteps, k))) return rc;
+    }
     const int ql = (li - 1) & 1;
     for (auto& s : c->slabs) {  // fold the last pair's partials
       HIPC(hipSetDevice(s.dev));
@@ -951,6 +977,7 @@ extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
     HIPC(hipSetDevice(s.dev));
     if (s.fcells) HIPC(hipFree(s.fcells));
     s.fcells = nullptr; s.fcells_n = 0; s.fty = 0;
+    wave_force_free(s);                 // (lbm_wave's force maps follow the list: rebuilt by the next forces run that wants them)
     s.fcells_host.swap(lists[k]);
     if (s.fcells_host.empty()) continue;
     std::vector<int2> dev(s.fcells_host.size());
@@ -973,7 +1000,7 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
   if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
   if (c->nbodies == 0) return fail(LBM_EINVAL, "no bodies are set (lbm_set_bodies)");
   if (nsteps > 0 && !forces) return fail(LBM_EINVAL, "forces is NULL");
-  c->forces_in_kernel = 0;
+  c->forces_in_kernel = 0; c->forces_in_wave = 0;
   if (nsteps == 0) return run_steps(c, 0, av_vels);
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   const int nb = c->nbodies;
@@ -1485,6 +1512,7 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "engine_last")) { *value = c->engine_last; return LBM_OK; }
   if (!strcmp(key, "samples_in_kernel")) { *value = c->samples_in_kernel; return LBM_OK; }
   if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "forces_in_wave")) { *value = c->forces_in_wave; return LBM_OK; }
   if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
   if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
   if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }

@@ -518,6 +518,22 @@ wave_fn wave_kernel(int K, bool slab, int C, int flavour) {
   return wave_kernel_f<4, false, 1>(flavour);
 }
 
+// ... and their force flavour (lbm_run_forces): the lone-lattice forms only
+template <int K, int C>
+wave_fn wave_force_kernel_f(int flavour) {
+  switch (flavour & 3) {
+    case 0: return lbm::lbm_wave<K, 0, false, C, true>;
+    case 1: return lbm::lbm_wave<K, 1, false, C, true>;
+    case 2: return lbm::lbm_wave<K, 2, false, C, true>;
+    default: return lbm::lbm_wave<K, 3, false, C, true>;
+  }
+}
+wave_fn wave_force_kernel(int K, int C, int flavour) {
+  if (K == 8) return C == 2 ? wave_force_kernel_f<8, 2>(flavour) : wave_force_kernel_f<8, 1>(flavour);
+  if (K == 6) return wave_force_kernel_f<6, 1>(flavour);
+  return wave_force_kernel_f<4, 1>(flavour);
+}
+
 int wave_blocks_per_cu(int K, int C) {
   static int cache[16][3] = {};                 // (the answer does not change; lbm_set_option asks often)
   if (K < 16 && C < 3 && cache[K][C] > 0) return cache[K][C];
@@ -540,8 +556,43 @@ void wave_plan(lbm_ctx* c) {
   c->wave_rows = (K == 8) ? slab_wave_rows(c, c->p.ny, 8) : std::min(c->p.ny, K >= 6 ? 64 : 32);   // (K = 8: whole rounds of the chip's wave slots)
 }
 
-// One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li.
-int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev) {
+// The force flavour's buffers of the lone slab: the force map and the index map (built at the first forces run that wants
+// them, freed with fcells by lbm_set_bodies) and the contributions of one group of K steps (the stream orders the fold of
+// group g before launch g + 1: one buffer).  false: no room -- the run takes the one-step path, nothing has been queued.
+void wave_force_free(Slab& s) {
+  if (s.fmap) (void)hipFree(s.fmap);
+  if (s.fidx) (void)hipFree(s.fidx);
+  if (s.fcontrib) (void)hipFree(s.fcontrib);
+  s.fmap = nullptr; s.fidx = nullptr; s.fcontrib = nullptr; s.fcontrib_cap = 0;
+}
+bool wave_force_ready(lbm_ctx* c, int K) {
+  Slab& s = c->slabs[0];
+  const int n = s.fcells_n;
+  if (n == 0) return true;                       // (no counted cell: the plain kernel, and the fold writes the zeros)
+  if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (!s.fmap) {
+    bool ok = hipMalloc((void**)&s.fmap, (size_t)s.plane) == hipSuccess &&
+              hipMalloc((void**)&s.fidx, sizeof(int) * (size_t)s.nyl * s.pitch) == hipSuccess &&
+              hipMemcpyAsync(s.fmap, s.blocked, (size_t)s.plane, hipMemcpyDeviceToDevice, s.sc) == hipSuccess;
+    if (ok) {
+      hipLaunchKernelGGL(lbm::lbm_mark_counted, dim3(cdiv(n, 256)), dim3(256), 0, s.sc, s.fcells, n, s.fmap, s.fidx);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); (void)hipStreamSynchronize(s.sc); wave_force_free(s); return false; }
+  }
+  const long need = 2L * K * n;
+  if (need > s.fcontrib_cap) {
+    if (s.fcontrib) (void)hipFree(s.fcontrib);
+    s.fcontrib = nullptr; s.fcontrib_cap = 0;
+    if (hipMalloc((void**)&s.fcontrib, sizeof(float) * (size_t)need) != hipSuccess) { (void)hipGetLastError(); s.fcontrib = nullptr; return false; }
+    s.fcontrib_cap = need;
+  }
+  return true;
+}
+
+// One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li.  nb > 0 (lbm_run_forces, wave_force_ready
+// said yes): the force flavour, and behind it the fold of the group's forces into the run's sums (of nsteps steps).
+int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0) {
   Slab& s = c->slabs[0];
   HIPC(hipSetDevice(s.dev));
   const int K = c->time_block;
@@ -565,8 +616,19 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev) {
   // (development: LBM_WAVE_PAD_LDS = bytes of unused dynamic LDS per block, to hold fewer blocks on a CU than the registers
   // allow -- how the rate depends on the waves per SIMD: profiles/r03_wave_occupancy.log)
   static const int pad_lds = getenv("LBM_WAVE_PAD_LDS") ? atoi(getenv("LBM_WAVE_PAD_LDS")) : 0;
-  hipLaunchKernelGGL(wave_kernel(K, false, wave_C(c, K), (int)(c->variant & (lbm::kFastMath | lbm::kNtStore))), dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
+  const int flavour = (int)(c->variant & (lbm::kFastMath | lbm::kNtStore));
+  a.fidx = nullptr; a.fcells = nullptr; a.contrib = nullptr; a.fcells_n = 0;
+  if (nb_bodies > 0 && s.fcells_n > 0) {
+    a.blocked = s.fmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n;
+    hipLaunchKernelGGL(wave_force_kernel(K, wave_C(c, K), flavour), dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
+  } else
+    hipLaunchKernelGGL(wave_kernel(K, false, wave_C(c, K), flavour), dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
   HIPC(hipGetLastError());
+  if (nb_bodies > 0) {
+    hipLaunchKernelGGL(lbm::lbm_fold_wave_forces, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.fcontrib, s.fcells, s.fcells_n, nb_bodies,
+                       s.sums + nsteps + 1 + (long)tt * 2 * nb_bodies);
+    HIPC(hipGetLastError());
+  }
   c->cur ^= 1;
   return LBM_OK;
 }

@@ -73,6 +73,7 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   if (wm && (rc = output_on_device(c, what->mean_out, "mean_out", &m_dev))) return rc;
   if (ws && (rc = output_on_device(c, what->fields_out, "fields_out", &s_dev))) return rc;
   c->observed_in_kernel = 0; c->observed_pieces = 0;
+  if (wf) c->forces_in_wave = 0;                          // (set by any piece whose forces rode in lbm_wave launches)
   // ---- none, or one alone: the call itself
   const int wanted = (wf ? 1 : 0) + (wp ? 1 : 0) + (wm ? 1 : 0) + (ws ? 1 : 0);
   if (wanted <= 1) {

@@ -360,6 +360,9 @@ void slab_free(Slab& s) {
   }
   if (s.blocked) (void)hipFree(s.blocked);
   if (s.fcells) (void)hipFree(s.fcells);
+  if (s.fmap) (void)hipFree(s.fmap);
+  if (s.fidx) (void)hipFree(s.fidx);
+  if (s.fcontrib) (void)hipFree(s.fcontrib);
   if (s.fslot) (void)hipFree(s.fslot);
   if (s.fslot_none) (void)hipFree(s.fslot_none);
   if (s.fwords) (void)hipFree(s.fwords);

@@ -1101,18 +1101,28 @@ __device__ __forceinline__ void body_force_cell(const float (&p)[9], uint32_t m,
 // One step's forces from the stored lattice (lbm_run_forces on every engine but the register tiles; one block):
 // cells[j] = {offset of a blocked labelled cell in the slab's planes, its word: mask | label << 8}.  out[2 b + k] = 2 x the
 // sum of component k over the cells of label b + 1, b < nb (in double, fixed order).
-__global__ __launch_bounds__(kBlock) void lbm_body_forces(const float* lat, long plane, const int2* cells, int n, int nb,
-                                                          double* out) {
+// The body of lbm_body_forces, shared with lbm_fold_wave_forces so that both add the same floats in the same order: a
+// thread's running sums per body over cells j = tid, tid + kBlock, ... in float, then the block's sums per body in double.
+// STORED: a cell's contribution comes from the stored lattice (body_force_cell on its eight planes); else it is read from
+// contrib[j][2], where the lane of lbm_wave's force flavour that owned the cell stored what body_force_cell gave it.
+template <bool STORED>
+__device__ __forceinline__ void body_forces_block(const float* lat, long plane, const float* contrib, const int2* cells, int n, int nb,
+                                                  double* out) {
   __shared__ double red_d[kBlock / 64];
   float fx[4] = {0.f, 0.f, 0.f, 0.f}, fy[4] = {0.f, 0.f, 0.f, 0.f};
   for (int j = threadIdx.x; j < n; j += kBlock) {
     const int2 cw = cells[j];
-    float p[9];
-    p[0] = 0.f;
-#pragma unroll
-    for (int k = 1; k < 9; ++k) p[k] = lat[k * plane + cw.x];
     float gx, gy;
-    body_force_cell(p, (uint32_t)cw.y, gx, gy);
+    if constexpr (STORED) {
+      float p[9];
+      p[0] = 0.f;
+#pragma unroll
+      for (int k = 1; k < 9; ++k) p[k] = lat[k * plane + cw.x];
+      body_force_cell(p, (uint32_t)cw.y, gx, gy);
+    } else {
+      const float2 g = *reinterpret_cast<const float2*>(contrib + 2L * j);
+      gx = g.x; gy = g.y;
+    }
     const int b = ((uint32_t)cw.y >> 8) - 1;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -1125,6 +1135,28 @@ __global__ __launch_bounds__(kBlock) void lbm_body_forces(const float* lat, long
     __syncthreads();
     if (threadIdx.x == 0) { out[2 * i] = 2.0 * sx; out[2 * i + 1] = 2.0 * sy; }
   }
+}
+
+__global__ __launch_bounds__(kBlock) void lbm_body_forces(const float* lat, long plane, const int2* cells, int n, int nb,
+                                                          double* out) {
+  body_forces_block<true>(lat, plane, nullptr, cells, n, nb, out);
+}
+
+// The forces of the K steps of one lbm_wave launch in its force flavour (lbm_wave.hip.h, FORCE): contrib[l][j][2] = what
+// body_force_cell gave for cell j of `cells` at step l of the group.  One block per step; block l writes out[l * 2 nb ...]
+// exactly as lbm_body_forces would have from the lattice stored after that step (n = 0: the zeros).
+__global__ __launch_bounds__(kBlock) void lbm_fold_wave_forces(const float* contrib, const int2* cells, int n, int nb, double* out) {
+  body_forces_block<false>(nullptr, 0, contrib + (long)blockIdx.x * n * 2, cells, n, nb, out + (long)blockIdx.x * 2 * nb);
+}
+
+// The maps of lbm_wave's force flavour from the obstacle bytes (copied into `map` beforehand) and the slab's counted
+// cells: map = 2 at a counted cell, idx = its index in `cells` (idx is read at counted cells only, the rest stays unset).
+__global__ void lbm_mark_counted(const int2* cells, int n, uint8_t* map, int* idx) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int off = cells[j].x;
+  map[off] = 2;
+  idx[off] = j;
 }
 
 // Derived fields of write_values() (d2q9-bgk.c:2935-2976) and the speed sum of

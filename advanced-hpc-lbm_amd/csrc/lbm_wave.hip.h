@@ -54,6 +54,13 @@ struct WaveArgs {
   int ny_s, ny_n;
   const uint8_t* blocked_s; const uint8_t* blocked_n;
   int acc_rows[3];             // this slab's row indices of the lattice's accelerate row and of its periodic images
+  // ---- the force flavour (FORCE; a lattice alone, lbm_run_forces): `blocked` is then the slab's force map -- 0 fluid,
+  // 1 blocked, 2 blocked and counted (a cell of `fcells`: labelled, with a fluid source) -- and a counted cell's lane
+  // stores what body_force_cell gives for it at level l to contrib[l - 1][fidx[cell]][2] (lbm_fold_wave_forces adds them up)
+  const int* fidx;             // [ny][pitch]: a counted cell's index in fcells (read at counted cells only)
+  const int2* fcells;          // {offset in a plane, mask | label << 8}, as lbm_body_forces takes them
+  float* contrib;              // [K][fcells_n][2]
+  int fcells_n;
 };
 
 constexpr int kWaveBlock = 256;   // four independent waves per block (they only meet for the final sums)
@@ -78,13 +85,22 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // -- 112 of 128 at K = 8 instead of 48 of 64 -- and half of the east / west neighbours are the lane's own other
 // column: six DPP shifts per PAIR of cells instead of twelve.  Needs K and nx even (a lane's pair never straddles the
 // periodic wrap, and is delivered or dropped as a whole).
-template <int K, int MODE, bool SLAB = false, int C = 1>
+// FORCE (lbm_run_forces where lbm_wave runs; a lattice alone): after collide_cell at level l a blocked cell's p[] holds
+// the populations the stored lattice of step t + l would hold (accelerate_cell leaves blocked cells alone), so
+// body_force_cell on them gives, for EVERY step of the pass, the bits lbm_body_forces gets from the stored lattice.  The
+// lane that owns a counted cell (own_row && out_ok: each cell exactly once per step) stores its two floats to the cell's
+// slot; no accumulator, no atomic, no LDS.  "Counted" rides down the levels in a second bit field beside mreg, from the
+// same byte of the map that says "blocked": no extra traffic, and a row without counted cells costs one scalar branch.
+// Not offered, and left on the one-step path with lbm_body_forces behind each step: contexts where lbm_march would run,
+// slabs with neighbours (the SLAB kernels, band groups, peer-to-peer marching), runs shorter than K.
+template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
 void lbm_wave(const WaveArgs a) {
   constexpr bool FAST = (MODE & kFastMath) != 0, NTS = (MODE & kNtStore) != 0, NTL = (MODE & kNtLoad) != 0;
   constexpr int VW = 64 * C - 2 * K;
   static_assert(K >= 1 && K <= 12, "a wave must keep some columns");
   static_assert(C == 1 || (C == 2 && K % 2 == 0), "one or two columns per lane; pairs need an even K");
+  static_assert(!(FORCE && SLAB), "the force flavour is for a lattice alone");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -197,6 +213,9 @@ void lbm_wave(const WaveArgs a) {
     unsigned mreg[C];                            // bit l = obstacle flag of the row level l works on, per column
 #pragma unroll
     for (int c = 0; c < C; ++c) mreg[c] = 0u;
+    [[maybe_unused]] unsigned creg[C];           // FORCE: bit l = "counted" flag of the same cell
+#pragma unroll
+    for (int c = 0; c < C; ++c) creg[c] = 0u;
     float nxt[C][9]; unsigned nblk;
     load_row(nxt, nblk);
     // One iteration.  STEADY: past the 2K fill iterations of the chunk every level has its history, the "is this level
@@ -209,6 +228,7 @@ void lbm_wave(const WaveArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) cur[c][k] = nxt[c][k];
         mreg[c] = (mreg[c] << 1) | (((nblk >> (8 * c)) & 0xffu) != 0u ? 1u : 0u);
+        if constexpr (FORCE) creg[c] = (creg[c] << 1) | (((nblk >> (8 * c)) & 0xffu) == 2u ? 1u : 0u);
       }
       if (j + 1 < niter) load_row(nxt, nblk);    // next iteration's source row, in flight behind this one's arithmetic
 #pragma unroll
@@ -262,6 +282,24 @@ void lbm_wave(const WaveArgs a) {
             // kernel 12 % at K = 8 and 18 % at K = 6, more than the eight dwords the K = 8 loop spills without them)
 #pragma unroll
             for (int c = 0; c < C; ++c) sum[l - 1] += (out_ok && own_row) ? sp[c] : 0.f;
+          }
+          if constexpr (FORCE) {
+            if (own_row) {                       // (wave-uniform; the row is Y0 + j - l - K, its columns do not wrap)
+              bool cnt[C], any = false;
+#pragma unroll
+              for (int c = 0; c < C; ++c) { cnt[c] = out_ok && ((creg[c] >> l) & 1u) != 0u; any = any || cnt[c]; }
+              if (__any(any)) {
+                const int cell = (S0 + j - l) * a.pitch + (X0 - K + C * lane);
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                  if (cnt[c]) {
+                    const int jc = a.fidx[cell + c];
+                    float fx, fy;
+                    body_force_cell(p[c], (uint32_t)a.fcells[jc].y, fx, fy);
+                    *reinterpret_cast<float2*>(a.contrib + ((long)(l - 1) * a.fcells_n + jc) * 2) = make_float2(fx, fy);
+                  }
+              }
+            }
           }
         }
         if (l >= 2 && (STEADY || j >= 2 * (l - 1))) {   // the producer's row of this iteration becomes history for the next two

@@ -191,14 +191,23 @@ int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mea
    a blocked cell of this context's rows carries a label outside [0, nbodies]. */
 int lbm_set_bodies(lbm_ctx* ctx, const int* body, int nbodies);
 /* lbm_run that also writes forces[nsteps][nbodies][2] = (F_x, F_y) of each body at each step (definition above).
-   The lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels), and so is av_vels wherever
-   the same kernel runs (the register tiles; the one-step kernel).  Where lbm_run would take several steps per launch
-   (time_block > 1, two-step launches on slabs), the forces run takes one at a time and av_vels is the one-step kernel's:
-   equal to lbm_run's within float rounding of the per-step sum.  Rank
-   contexts: every rank gets the global forces (without RCCL: its own contribution), as with av_vels.  The register
-   tiles take the sums inside their kernels (info "forces_in_kernel" = 1); every other engine runs the one-step kernel
-   with a small force kernel behind each step (correct, not fast).  LBM_EINVAL with nothing queued and the lattice
-   untouched when no bodies are set or forces is NULL with nsteps > 0; LBM_ENOMEM likewise when the partials do not fit.
+   The lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels).
+   Which kernels take the forces:
+   - The register tiles take the sums inside their kernels (info "forces_in_kernel" = 1); av_vels is lbm_run's, bit for bit.
+   - Where lbm_wave runs (a lattice alone on its GPU with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block),
+     the forces ride in its launches (info "forces_in_wave" = 1, "forces_in_kernel" = 0): a force flavour of lbm_wave
+     stores every counted cell's contribution at every step of a pass and a small kernel behind each launch adds them up;
+     the steps left over behind the last full pass go as lbm_run's do, with a force kernel behind each.  There
+     av_vels is lbm_run's, bit for bit, and the forces are the bits of the one-step path (below), whichever steps fell
+     inside an lbm_wave launch.  If the force maps (5 bytes per cell) do not fit on the device, the run takes the one-step
+     path: the same forces, no error.
+   - The remaining engines are unchanged: contexts where lbm_march runs, slabs with neighbours, rank contexts and runs
+     shorter than time_block run the one-step kernel with a small force kernel behind each step (correct, not fast; both
+     keys read 0).  Where lbm_run would take several steps per launch there, av_vels is the one-step kernel's: equal to
+     lbm_run's within float rounding of the per-step sum.
+   Rank contexts: every rank gets the global forces (without RCCL: its own contribution), as with av_vels.
+   LBM_EINVAL with nothing queued and the lattice untouched when no bodies are set or forces is NULL with nsteps > 0;
+   LBM_ENOMEM likewise when the register tiles' partials do not fit.
    With snapshots, probes or means in one run: lbm_run_observed. */
 int lbm_run_forces(lbm_ctx* ctx, int nsteps, float* av_vels, float* forces);
 
@@ -329,6 +338,7 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * form of the speed sum, d2q9-bgk.c:1783-1811, 256 one-step kernel only), "vector_width", "t2_threads".
  * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
  * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
+ * "forces_in_wave" (1: the last lbm_run_forces took its per-cell contributions inside lbm_wave launches),
  * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles),
  * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles), "observed_in_kernel",
  * "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
