@@ -267,7 +267,10 @@ class Lattice:
         """lbm_run with the time series of the probes (set_probes): returns (av_vels[nsteps], probes) where probes is
         (nsteps // every, nprobes, 4) float32 -- u_x, u_y, |u|, pressure of each probe after steps every, 2 every, ...,
         the bits run_sampled has in those cells -- a numpy array, or `out`, a contiguous float32 torch tensor of that
-        shape on the context's GPU, filled there."""
+        shape on the context's GPU, filled there.  The register tiles take the values inside their kernels
+        (info("probes_in_kernel") == 1); where lbm_wave runs they ride in its launches (info("probes_in_wave") == 1:
+        av_vels is run()'s bits, the probes are the split path's bits); elsewhere the steps run in pieces of `every`
+        with a gather kernel behind each."""
         n = getattr(self, "_nprobes", 0)
         shape = (max(nsteps, 0) // every if every > 0 else 0, n, 4)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
@@ -328,7 +331,9 @@ class Lattice:
         """lbm_run with any subset of the observers in ONE run: forces=True (run_forces), probes_every > 0 (run_probes),
         mean_every > 0 (run_mean), fields_every > 0 (run_sampled).  Returns a dict with "av_vels" and one entry per wanted
         observer -- "forces", "probes", "mean", "fields" -- each the bits its own call returns: numpy arrays, or the
-        contiguous float32 CUDA tensors given as probes_out / mean_out / fields_out, filled on the GPU."""
+        contiguous float32 CUDA tensors given as probes_out / mean_out / fields_out, filled on the GPU.  Where lbm_wave
+        runs, forces and probes ride together in its launches and cut no piece (info("observed_in_wave"): bits 1 forces,
+        2 probes; info("observed_in_kernel") means the register tiles and reads 0 there)."""
         n = max(nsteps, 0)
         av = np.empty(n, dtype=np.float32)
         res = {"av_vels": av}

@@ -214,6 +214,12 @@ struct Slab {
   // that are all -1 (no tile counts anything)
   int* fslot_none = nullptr;
   int fslot_none_n = 0;
+  // lbm_wave's probe flavours (a lattice alone; lbm_host_march.inc, wave_probe_ready): the obstacle bytes with 4 added on the
+  // probes' cells (probes alone), the force map with the same (forces and probes: follows both sets), the probes' indices in
+  // the set (dense, read at probe cells only)
+  uint8_t* pmap = nullptr;
+  uint8_t* fpmap = nullptr;
+  int* pidx = nullptr;
 };
 
 }  // namespace
@@ -256,6 +262,8 @@ struct lbm_ctx {
   int forces_in_wave = 0;      // 1: the last lbm_run_forces took its per-cell contributions inside lbm_wave launches
   int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
   int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
+  int probes_in_wave = 0;      // 1: the last lbm_run_probes took its values inside lbm_wave launches
+  int observed_in_wave = 0;    // the last lbm_run_observed: bits 1 forces, 2 probes taken inside lbm_wave launches
   int observed_in_kernel = 0;  // the last lbm_run_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
   int observed_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
   int nbodies = 0;             // lbm_set_bodies (0: none)
@@ -638,6 +646,18 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 
 static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
 
+// May a probe run of this context take its values inside lbm_wave launches (with_forces: forces beside them)?  The
+// conditions of the forces (run_steps, fwave) on the context -- a lattice alone, no ranks, no exchange, lbm_wave the
+// engine of the groups of K steps, their partial sums fit -- and the maps in place.  Asked before anything is queued; no:
+// the caller keeps the split path.  (Whether a run is long enough for a group is the caller's question.)
+static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
+  if (c->rank_mode || c->exchange != 0 || !march_eligible(c) || !use_wave_kernel(c)) return false;
+  if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
+  if ((long)c->time_block * wave_blocks(c) > c->slabs[0].partial_cap) return false;
+  if (with_forces && !wave_force_ready(c, c->time_block)) return false;
+  return wave_probe_ready(c, with_forces);
+}
+
 // The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean; with k.probe: lbm_run_probes): ONLY the
 // register tiles are tried, with the snapshots (the sums, the probes) in the kernel; if they did not run (samples_in_kernel /
 // mean_in_kernel / probes_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
@@ -687,6 +707,26 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   }
   // (behind those groups the left-over steps go as lbm_run's do, in pairs where it takes pairs: av_vels is lbm_run's bits)
   const bool pairs = (!fo || fwave) && t2_eligible(c) && nsteps >= 2;
+  // probes on an admitted context (RunKind::wave_pout): is step s (1-based) of this run a sample step, and its output row
+  const bool pw = k.wave_pout != nullptr;
+  auto psample = [&](int s) { return pw && s >= k.pfirst && (s - k.pfirst) % k.wave_pevery == 0; };
+  auto prow = [&](int s) { return (s - k.pfirst) / k.wave_pevery; };
+  // ... a left-over step that is one: the probes' cells of the lattice just stored (stored WITHOUT the next step's
+  // accelerate phase, which `then_accelerate` applies behind the gather as the prologue does, to the same bits)
+  auto pgather = [&](int s, bool then_accelerate) -> int {
+    Slab& sl = c->slabs[0];
+    const int n_here = (int)sl.pcells_host.size();
+    HIPC(hipSetDevice(sl.dev));
+    hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane,
+                       sl.pcells, n_here, sl.blocked, c->p.density, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes);
+    HIPC(hipGetLastError());
+    if (then_accelerate && sl.accel_row >= 0) {
+      hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, sl.sc,
+                         sl.lat[c->cur], sl.plane, sl.pitch, nx, sl.accel_row, sl.blocked, a1, a2);
+      HIPC(hipGetLastError());
+    }
+    return LBM_OK;
+  };
 
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
@@ -789,9 +829,17 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   if ((!fo || fwave) && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
     const int K = c->time_block, ngroups = nsteps / K;
     const bool wave = use_wave_kernel(c);
-    for (int g = 0; g < ngroups; ++g, ++li, tt += K)
-      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+    for (int g = 0; g < ngroups; ++g, ++li, tt += K) {
+      WaveProbes wp;
+      if (pw && wave) {                                  // the group's sample levels and the first one's output row
+        wp.out = k.wave_pout; wp.nprobes = c->nprobes;
+        for (int l = K; l >= 1; --l)
+          if (psample(tt + l)) { wp.mask |= 1u << (l - 1); wp.row = prow(tt + l); }
+      }
+      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, wp) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+    }
     if (fwave) c->forces_in_wave = 1;
+    if (pw && wave) c->probes_in_wave = 1;
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -801,15 +849,19 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   if (pairs && nsteps - tt >= 2) {
     const int npairs = (nsteps - tt) / 2;
     for (int j = 0; j < npairs; ++j, ++li, tt += 2) {
-      if (fo) {
-        // (a forces run behind its lbm_wave groups, a lattice alone) the pair's first step alone into the destination
-        // lattice, for its forces -- its speed sums go unused -- then the pair from the same source over it
+      const bool p1 = psample(tt + 1), p2 = psample(tt + 2);
+      if (fo || p1) {
+        // (a forces run behind its lbm_wave groups, a lattice alone; a probe run whose sample step this is) the pair's first
+        // step alone into the destination lattice, for its forces and probes -- its speed sums go unused -- then the pair
+        // from the same source over it
         if ((rc = launch_single(c, li, tt, true, false, a1, a2))) return rc;
-        if ((rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
+        if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
+        if (p1 && (rc = pgather(tt + 1, false))) return rc;
         c->cur ^= 1;
       }
-      if ((rc = launch_pair(c, li, tt, tt + 2 < nsteps, j > 0, a1, a2))) return rc;
+      if ((rc = launch_pair(c, li, tt, tt + 2 < nsteps && !p2, j > 0, a1, a2))) return rc;
       if (fo && (rc = launch_forces(c, tt + 1, li & 1, nsteps, k))) return rc;
+      if (p2 && (rc = pgather(tt + 2, tt + 2 < nsteps))) return rc;
     }
     const int ql = (li - 1) & 1;
     for (auto& s : c->slabs) {  // fold the last pair's partials
@@ -822,8 +874,10 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   }
   const int first_single = tt;
   for (; tt < nsteps; ++tt, ++li) {
-    if ((rc = launch_single(c, li, tt, tt == nsteps - 1, tt > first_single, a1, a2))) return rc;
+    const bool ps = psample(tt + 1);
+    if ((rc = launch_single(c, li, tt, tt == nsteps - 1 || ps, tt > first_single, a1, a2))) return rc;
     if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
+    if (ps && (rc = pgather(tt + 1, tt + 1 < nsteps))) return rc;
   }
 
   // ---- epilogue: fold the last single step's partials, collect the per-step sums
@@ -978,6 +1032,7 @@ extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
     if (s.fcells) HIPC(hipFree(s.fcells));
     s.fcells = nullptr; s.fcells_n = 0; s.fty = 0;
     wave_force_free(s);                 // (lbm_wave's force maps follow the list: rebuilt by the next forces run that wants them)
+    wave_probe_free(s, false);          // (... and so does the force-and-probe map)
     s.fcells_host.swap(lists[k]);
     if (s.fcells_host.empty()) continue;
     std::vector<int2> dev(s.fcells_host.size());
@@ -1163,6 +1218,7 @@ extern "C" int lbm_set_probes(lbm_ctx* c, const int* xy, int nprobes) {
     s.pcells = (int2*)fresh[k].p; fresh[k].p = nullptr;
     s.pcells_host.swap(lists[k]);
     s.pty = 0;                      // (the register tiles' tables: rebuilt by the next lbm_run_probes)
+    wave_probe_free(s, true);       // (lbm_wave's probe maps likewise)
   }
   c->nprobes = nprobes;
   return LBM_OK;
@@ -1176,7 +1232,7 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
   const int m = nsteps / every;
   if (m == 0) return fail(LBM_EINVAL, "nothing to record: no sample step in nsteps = %d step(s) at every = %d", nsteps, every);
   if (!probes_out) return fail(LBM_EINVAL, "probes_out is NULL");
-  c->probes_in_kernel = 0;
+  c->probes_in_kernel = 0; c->probes_in_wave = 0;
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   const int np = c->nprobes;
@@ -1244,6 +1300,15 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     if (c->probes_in_kernel) return to_host();
     // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run and store every value again)
+  }
+  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps in lbm_wave's probe flavour, which
+  // stores the probes of every sample step of a pass; lbm_probe_gather behind the left-over steps that are sample steps.
+  // Decided here, before anything is queued; maps or partials that do not fit: the pieces below, the same bits.
+  if (nsteps >= c->time_block && wave_probes_admit(c, false)) {
+    RunKind k;
+    k.no_tiles = true; k.wave_pout = out_of(0); k.wave_pevery = every; k.pfirst = every;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    return to_host();
   }
   // ---- the step loop split at the sample steps: each piece a complete run, then the probes' cells of the stored lattice
   // gathered into row j.  Correct, not fast.
@@ -1515,6 +1580,8 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "forces_in_wave")) { *value = c->forces_in_wave; return LBM_OK; }
   if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
   if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "probes_in_wave")) { *value = c->probes_in_wave; return LBM_OK; }
+  if (!strcmp(key, "observed_in_wave")) { *value = c->observed_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }
   if (!strcmp(key, "observed_pieces")) { *value = c->observed_pieces; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first

@@ -534,6 +534,23 @@ wave_fn wave_force_kernel(int K, int C, int flavour) {
   return wave_force_kernel_f<4, 1>(flavour);
 }
 
+// ... and their probe flavours (lbm_run_probes; with forces: lbm_run_observed's forces and probes)
+template <int K, int C, bool FORCE>
+wave_fn wave_probe_kernel_f(int flavour) {
+  switch (flavour & 3) {
+    case 0: return lbm::lbm_wave<K, 0, false, C, FORCE, true>;
+    case 1: return lbm::lbm_wave<K, 1, false, C, FORCE, true>;
+    case 2: return lbm::lbm_wave<K, 2, false, C, FORCE, true>;
+    default: return lbm::lbm_wave<K, 3, false, C, FORCE, true>;
+  }
+}
+template <bool FORCE>
+wave_fn wave_probe_kernel(int K, int C, int flavour) {
+  if (K == 8) return C == 2 ? wave_probe_kernel_f<8, 2, FORCE>(flavour) : wave_probe_kernel_f<8, 1, FORCE>(flavour);
+  if (K == 6) return wave_probe_kernel_f<6, 1, FORCE>(flavour);
+  return wave_probe_kernel_f<4, 1, FORCE>(flavour);
+}
+
 int wave_blocks_per_cu(int K, int C) {
   static int cache[16][3] = {};                 // (the answer does not change; lbm_set_option asks often)
   if (K < 16 && C < 3 && cache[K][C] > 0) return cache[K][C];
@@ -590,9 +607,53 @@ bool wave_force_ready(lbm_ctx* c, int K) {
   return true;
 }
 
+// The probe flavours' maps of the lone slab, built at the first probe run that wants them: the probe map and the index map
+// (freed by lbm_set_probes), and -- with_forces, where a cell is counted -- the force-and-probe map from the force map
+// (freed by lbm_set_probes and by lbm_set_bodies: it follows both sets).  false: no room, nothing has been queued.
+void wave_probe_free(Slab& s, bool all) {
+  if (s.fpmap) (void)hipFree(s.fpmap);
+  s.fpmap = nullptr;
+  if (!all) return;
+  if (s.pmap) (void)hipFree(s.pmap);
+  if (s.pidx) (void)hipFree(s.pidx);
+  s.pmap = nullptr; s.pidx = nullptr;
+}
+bool wave_probe_ready(lbm_ctx* c, bool with_forces) {
+  Slab& s = c->slabs[0];
+  const int n = (int)s.pcells_host.size();
+  if (n == 0 || !s.pcells) return false;
+  if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+  auto build = [&](uint8_t*& map, const uint8_t* from) {
+    bool ok = hipMalloc((void**)&map, (size_t)s.plane) == hipSuccess &&
+              (s.pidx || hipMalloc((void**)&s.pidx, sizeof(int) * (size_t)s.nyl * s.pitch) == hipSuccess) &&
+              hipMemcpyAsync(map, from, (size_t)s.plane, hipMemcpyDeviceToDevice, s.sc) == hipSuccess;
+    if (ok) {
+      hipLaunchKernelGGL(lbm::lbm_mark_probes, dim3(cdiv(n, 256)), dim3(256), 0, s.sc, s.pcells, n, map, s.pidx);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); (void)hipStreamSynchronize(s.sc); wave_probe_free(s, true); }
+    return ok;
+  };
+  if (with_forces && s.fcells_n > 0) {           // (no counted cell: the probe flavour alone, and the fold writes the zeros)
+    if (!s.fmap) return false;                   // (wave_force_ready comes first)
+    return s.fpmap || build(s.fpmap, s.fmap);
+  }
+  return s.pmap || build(s.pmap, s.blocked);
+}
+
+// What a launch of the probe flavours is told (RunKind::wave_pout; nullptr: no probes): the sample levels of its K steps
+// (bit l - 1: step tt + l), the output row of the first of them, row 0 of the output, the probes in the set.
+struct WaveProbes {
+  float* out = nullptr;
+  unsigned mask = 0u;
+  int row = 0, nprobes = 0;
+};
+
 // One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li.  nb > 0 (lbm_run_forces, wave_force_ready
 // said yes): the force flavour, and behind it the fold of the group's forces into the run's sums (of nsteps steps).
-int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0) {
+// wp.out (wave_probe_ready said yes): the probe flavour, or the force-and-probe flavour; a group without a sample step
+// runs what it would run without probes.
+int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0, WaveProbes wp = WaveProbes()) {
   Slab& s = c->slabs[0];
   HIPC(hipSetDevice(s.dev));
   const int K = c->time_block;
@@ -618,6 +679,16 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   static const int pad_lds = getenv("LBM_WAVE_PAD_LDS") ? atoi(getenv("LBM_WAVE_PAD_LDS")) : 0;
   const int flavour = (int)(c->variant & (lbm::kFastMath | lbm::kNtStore));
   a.fidx = nullptr; a.fcells = nullptr; a.contrib = nullptr; a.fcells_n = 0;
+  a.pidx = nullptr; a.pout = nullptr; a.nprobes = 0; a.pmask = 0u; a.prow = 0; a.density = c->p.density;
+  const bool probes = wp.out != nullptr && wp.mask != 0u;
+  if (probes) { a.pidx = s.pidx; a.pout = wp.out; a.nprobes = wp.nprobes; a.pmask = wp.mask; a.prow = wp.row; }
+  if (probes && nb_bodies > 0 && s.fcells_n > 0) {
+    a.blocked = s.fpmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n;
+    hipLaunchKernelGGL(wave_probe_kernel<true>(K, wave_C(c, K), flavour), dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
+  } else if (probes) {
+    a.blocked = s.pmap;
+    hipLaunchKernelGGL(wave_probe_kernel<false>(K, wave_C(c, K), flavour), dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
+  } else
   if (nb_bodies > 0 && s.fcells_n > 0) {
     a.blocked = s.fmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n;
     hipLaunchKernelGGL(wave_force_kernel(K, wave_C(c, K), flavour), dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);

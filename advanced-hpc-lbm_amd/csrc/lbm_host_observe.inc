@@ -72,19 +72,19 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   if (wp && (rc = output_on_device(c, what->probes_out, "probes_out", &p_dev))) return rc;
   if (wm && (rc = output_on_device(c, what->mean_out, "mean_out", &m_dev))) return rc;
   if (ws && (rc = output_on_device(c, what->fields_out, "fields_out", &s_dev))) return rc;
-  c->observed_in_kernel = 0; c->observed_pieces = 0;
+  c->observed_in_kernel = 0; c->observed_in_wave = 0; c->observed_pieces = 0;
   if (wf) c->forces_in_wave = 0;                          // (set by any piece whose forces rode in lbm_wave launches)
   // ---- none, or one alone: the call itself
   const int wanted = (wf ? 1 : 0) + (wp ? 1 : 0) + (wm ? 1 : 0) + (ws ? 1 : 0);
   if (wanted <= 1) {
-    if (wf) { rc = lbm_run_forces(c, nsteps, av_vels, what->forces); if (!rc && c->forces_in_kernel) c->observed_in_kernel = 1; }
-    else if (wp) { rc = lbm_run_probes(c, nsteps, av_vels, pe, what->probes_out); if (!rc && c->probes_in_kernel) c->observed_in_kernel = 2; }
+    if (wf) { rc = lbm_run_forces(c, nsteps, av_vels, what->forces); if (!rc && c->forces_in_kernel) c->observed_in_kernel = 1; if (!rc && c->forces_in_wave) c->observed_in_wave = 1; }
+    else if (wp) { rc = lbm_run_probes(c, nsteps, av_vels, pe, what->probes_out); if (!rc && c->probes_in_kernel) c->observed_in_kernel = 2; if (!rc && c->probes_in_wave) c->observed_in_wave = 2; }
     else if (wm) { rc = lbm_run_mean(c, nsteps, av_vels, me, what->mean_out); if (!rc && c->mean_in_kernel) c->observed_in_kernel = 4; }
     else if (ws) { rc = lbm_run_sampled(c, nsteps, av_vels, se, what->fields_out); if (!rc && c->samples_in_kernel) c->observed_in_kernel = 8; }
     else rc = lbm_run(c, nsteps, av_vels);
     if (!rc) {
       const int m = wp ? mp : wm ? mm : ws ? msn : 0, ev = wp ? pe : wm ? me : se;
-      c->observed_pieces = (wanted == 0 || wf || c->observed_in_kernel != 0) ? 1 : m + (nsteps > m * ev ? 1 : 0);
+      c->observed_pieces = (wanted == 0 || wf || c->observed_in_kernel != 0 || c->observed_in_wave != 0) ? 1 : m + (nsteps > m * ev ? 1 : 0);
     }
     return rc;
   }
@@ -126,6 +126,10 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     }
   }
   if ((rc = ranks_agree(c, rc, &tiles, "the observers' buffers"))) return rc;
+  // probes where lbm_run would run lbm_wave (a lattice alone): they ride in its launches, beside the forces if those are
+  // wanted, and cut no piece; decided here, before anything is queued (no: lbm_probe_gather behind pieces cut at their steps)
+  const bool pwave = wp && !rc && !tiles && wave_probes_admit(c, wf);
+  int wbits = 0;
   // the probes of other ranks' rows read +0.0f
   if (wp && plocal < (size_t)np) {
     if (p_dev) {
@@ -151,7 +155,7 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     int next = nsteps;
     if (wm) next = std::min<long>(next, ((long)done / me + 1) * me);
     if (ws) next = std::min<long>(next, ((long)done / se + 1) * se);
-    if (wp && !on_tiles) next = std::min<long>(next, ((long)done / pe + 1) * pe);
+    if (wp && !on_tiles && !pwave) next = std::min<long>(next, ((long)done / pe + 1) * pe);
     const int n = next - done;
     const long nval = wf ? 2L * nb * n : 0;
     const int jp = wp ? done / pe : 0;                    // the probes' samples taken before this piece
@@ -174,8 +178,15 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
       bits |= (wf ? 1 : 0) | (wp ? 2 : 0);
     } else {
       k.no_tiles = true;
+      if (pwave) {
+        // (the probes' phase runs on from the start of the call: the first sample of this piece, and its row of the output)
+        k.wave_pevery = pe; k.pfirst = pe - done % pe; k.wave_pout = probes_of(0) + 4 * (size_t)jp * (size_t)np;
+        c->probes_in_wave = 0;
+      }
       if ((rc = run_steps(c, n, av, k))) return rc;
-      if (wp && (done + n) % pe == 0)
+      if (pwave && c->probes_in_wave) wbits |= 2;
+      if (wf && c->forces_in_wave) wbits |= 1;
+      if (wp && !pwave && (done + n) % pe == 0)
         for (size_t i = 0; i < ns; ++i) {
           Slab& s = c->slabs[i];
           const int n_here = (int)s.pcells_host.size();
@@ -238,6 +249,6 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     }
   }
   c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
-  c->observed_in_kernel = bits; c->observed_pieces = pieces;
+  c->observed_in_kernel = bits; c->observed_in_wave = wbits; c->observed_pieces = pieces;
   return LBM_OK;
 }

@@ -35,6 +35,12 @@ struct RunKind {
   bool piece = false, piece_mid = false, no_tiles = false;
   int pfirst = 0;
   bool* ran = nullptr;
+  // wave_pout (lbm_run_probes / lbm_run_observed on a context wave_probes_admit said yes to; a lattice alone, the register
+  // tiles kept off): the probes' sample steps are pfirst, pfirst + wave_pevery, ... steps into this run, wave_pout is the
+  // output row of the first of them (rows of 4 x nprobes floats).  The groups of K steps take them inside lbm_wave's probe
+  // flavours; behind a left-over step that is a sample step, lbm_probe_gather.
+  float* wave_pout = nullptr;
+  int wave_pevery = 0;
 };
 
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the

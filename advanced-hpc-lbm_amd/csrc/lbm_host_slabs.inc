@@ -363,6 +363,9 @@ void slab_free(Slab& s) {
   if (s.fmap) (void)hipFree(s.fmap);
   if (s.fidx) (void)hipFree(s.fidx);
   if (s.fcontrib) (void)hipFree(s.fcontrib);
+  if (s.pmap) (void)hipFree(s.pmap);
+  if (s.fpmap) (void)hipFree(s.fpmap);
+  if (s.pidx) (void)hipFree(s.pidx);
   if (s.fslot) (void)hipFree(s.fslot);
   if (s.fslot_none) (void)hipFree(s.fslot_none);
   if (s.fwords) (void)hipFree(s.fwords);

@@ -1159,6 +1159,17 @@ __global__ void lbm_mark_counted(const int2* cells, int n, uint8_t* map, int* id
   idx[off] = j;
 }
 
+// The maps of lbm_wave's probe flavours from a byte map (the obstacle bytes, or the force map: copied into `map` beforehand)
+// and the slab's probes, cells[j] = {offset in a plane, index in the set}: map += 4 at a probe's cell (probes are distinct
+// cells: one thread per byte), idx = the probe's index (idx is read at probe cells only, the rest stays unset).
+__global__ void lbm_mark_probes(const int2* cells, int n, uint8_t* map, int* idx) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int2 cw = cells[j];
+  map[cw.x] = (uint8_t)(map[cw.x] | 4u);
+  idx[cw.x] = cw.y;
+}
+
 // Derived fields of write_values() (d2q9-bgk.c:2935-2976) and the speed sum of
 // av_velocity() (d2q9-bgk.c:2665-2714) in one pass.  out4 may be nullptr.
 __global__ __launch_bounds__(kBlock) void lbm_derive(const float* lat, long plane, int pitch, int nx,

@@ -61,6 +61,16 @@ struct WaveArgs {
   const int2* fcells;          // {offset in a plane, mask | label << 8}, as lbm_body_forces takes them
   float* contrib;              // [K][fcells_n][2]
   int fcells_n;
+  // ---- the probe flavours (PROBE, alone or with FORCE; a lattice alone, lbm_run_probes / lbm_run_observed): `blocked` is
+  // then the slab's probe map -- the low two bits as above (0 fluid, 1 blocked, 2 blocked and counted), plus 4 on a probe's
+  // cell, blocked or not -- and at the sample levels of the pass a probe's lane stores what derive_cell gives for the cell
+  // to pout + 4 * (row * nprobes + pidx[cell]): one 16-byte store, nothing to fold
+  const int* pidx;             // [ny][pitch]: a probe cell's index in the set (read at probe cells only)
+  float* pout;                 // [samples][nprobes][4]
+  int nprobes;
+  unsigned pmask;              // bit l - 1: step t + l of this pass is a sample step
+  int prow;                    // the output row of the pass's first sample; a later one's: + the sample levels below it
+  float density;               // what derive_cell gives a blocked cell's pressure from
 };
 
 constexpr int kWaveBlock = 256;   // four independent waves per block (they only meet for the final sums)
@@ -93,7 +103,14 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // same byte of the map that says "blocked": no extra traffic, and a row without counted cells costs one scalar branch.
 // Not offered, and left on the one-step path with lbm_body_forces behind each step: contexts where lbm_march would run,
 // slabs with neighbours (the SLAB kernels, band groups, peer-to-peer marching), runs shorter than K.
-template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false>
+// PROBE (lbm_run_probes, with FORCE lbm_run_observed's forces and probes, where lbm_wave runs; a lattice alone): after
+// collide_cell at level l and BEFORE accelerate_cell, p[] of any cell, fluid or blocked, holds the populations the stored
+// lattice of step t + l would hold at the end of a run -- what lbm_probe_gather hands to derive_cell.  (Behind
+// accelerate_cell a fluid cell of row ny - 2 would carry the next step's accelerate phase, which a run's last lattice
+// never does.)  At a sample level -- wave-uniform, a bit of pmask: a level that samples nothing costs one scalar test --
+// the lane that owns a probe's cell (own_row && out_ok) stores the four floats into the probe's place of the sample's
+// output row.  "Probe" rides down the levels in a third bit field, from the same map byte.
+template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
 void lbm_wave(const WaveArgs a) {
   constexpr bool FAST = (MODE & kFastMath) != 0, NTS = (MODE & kNtStore) != 0, NTL = (MODE & kNtLoad) != 0;
@@ -101,6 +118,7 @@ void lbm_wave(const WaveArgs a) {
   static_assert(K >= 1 && K <= 12, "a wave must keep some columns");
   static_assert(C == 1 || (C == 2 && K % 2 == 0), "one or two columns per lane; pairs need an even K");
   static_assert(!(FORCE && SLAB), "the force flavour is for a lattice alone");
+  static_assert(!(PROBE && SLAB), "the probe flavours are for a lattice alone");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -216,6 +234,29 @@ void lbm_wave(const WaveArgs a) {
     [[maybe_unused]] unsigned creg[C];           // FORCE: bit l = "counted" flag of the same cell
 #pragma unroll
     for (int c = 0; c < C; ++c) creg[c] = 0u;
+    [[maybe_unused]] unsigned preg[C];           // PROBE: bit l = "a probe sits here" flag of the same cell
+#pragma unroll
+    for (int c = 0; c < C; ++c) preg[c] = 0u;
+    // PROBE, at a sample level behind collide_cell(s): the probes of the level's row, straight to their places
+    // (l is a constant once the level loop is unrolled)
+    [[maybe_unused]] auto store_probes = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
+      if (own_row && ((a.pmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
+        bool pr[C], any = false;
+#pragma unroll
+        for (int c = 0; c < C; ++c) { pr[c] = out_ok && ((preg[c] >> l) & 1u) != 0u; any = any || pr[c]; }
+        if (__any(any)) {
+          const int cell = (S0 + j - l) * a.pitch + (X0 - K + C * lane);
+          const long row = a.prow + __builtin_popcount(a.pmask & ((1u << (l - 1)) - 1u));
+#pragma unroll
+          for (int c = 0; c < C; ++c)
+            if (pr[c]) {
+              float rho;
+              const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
+              *reinterpret_cast<f4a*>(a.pout + 4 * (row * a.nprobes + a.pidx[cell + c])) = v;
+            }
+        }
+      }
+    };
     float nxt[C][9]; unsigned nblk;
     load_row(nxt, nblk);
     // One iteration.  STEADY: past the 2K fill iterations of the chunk every level has its history, the "is this level
@@ -227,8 +268,14 @@ void lbm_wave(const WaveArgs a) {
       for (int c = 0; c < C; ++c) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) cur[c][k] = nxt[c][k];
-        mreg[c] = (mreg[c] << 1) | (((nblk >> (8 * c)) & 0xffu) != 0u ? 1u : 0u);
-        if constexpr (FORCE) creg[c] = (creg[c] << 1) | (((nblk >> (8 * c)) & 0xffu) == 2u ? 1u : 0u);
+        if constexpr (PROBE) {                   // (the probe map: blocked / counted in the low two bits, 4 = a probe)
+          mreg[c] = (mreg[c] << 1) | (((nblk >> (8 * c)) & 3u) != 0u ? 1u : 0u);
+          if constexpr (FORCE) creg[c] = (creg[c] << 1) | (((nblk >> (8 * c)) & 3u) == 2u ? 1u : 0u);
+          preg[c] = (preg[c] << 1) | ((nblk >> (8 * c + 2)) & 1u);
+        } else {
+          mreg[c] = (mreg[c] << 1) | (((nblk >> (8 * c)) & 0xffu) != 0u ? 1u : 0u);
+          if constexpr (FORCE) creg[c] = (creg[c] << 1) | (((nblk >> (8 * c)) & 0xffu) == 2u ? 1u : 0u);
+        }
       }
       if (j + 1 < niter) load_row(nxt, nblk);    // next iteration's source row, in flight behind this one's arithmetic
 #pragma unroll
@@ -267,6 +314,7 @@ void lbm_wave(const WaveArgs a) {
           if constexpr (C == 1) {
             const bool blk = ((mreg[0] >> l) & 1u) != 0u;
             const float sp = collide_cell<FAST>(p[0], blk, a.omega);
+            if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if (acc) accelerate_cell(p[0], blk, a.a1, a.a2);
             sum[l - 1] += (out_ok && own_row) ? sp : 0.f;
           } else {
@@ -275,6 +323,7 @@ void lbm_wave(const WaveArgs a) {
 #pragma unroll
             for (int c = 0; c < C; ++c) blk[c] = ((mreg[c] >> l) & 1u) != 0u;
             collide_cells<FAST, C>(p, blk, a.omega, sp);      // the lane's cells statement by statement: independent chains
+            if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
 #pragma unroll
             for (int c = 0; c < C; ++c)
               if (acc) accelerate_cell(p[c], blk[c], a.a1, a.a2);

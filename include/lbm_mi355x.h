@@ -227,17 +227,27 @@ int lbm_set_probes(lbm_ctx* ctx, const int* xy, int nprobes);
    every, 2 every, ..., m every (m = nsteps / every).
    Definition, bit for bit: probes_out[j][p][:] equals fields_out[j][jj_p][ii_p][:] of
    lbm_run_sampled(ctx, nsteps, av_vels, every, fields_out) from the same state; a blocked cell reads the constant
-   0, 0, 0, density / 3.  Probes keep the order in which they were given.  av_vels, the lattice and everything after the
-   call are bit-identical to lbm_run(ctx, nsteps, av_vels) (where the streaming engines run in pieces, av_vels as for
-   lbm_run_sampled / lbm_run_mean on those engines).  probes_out: host memory, or device memory of the device that holds
+   0, 0, 0, density / 3.  Probes keep the order in which they were given.  The lattice and everything after the
+   call are bit-identical to lbm_run(ctx, nsteps, av_vels).  probes_out: host memory, or device memory of the device that holds
    every slab of the context (then nothing is copied to the host).
    Rank contexts: xy is global on every rank; each rank fills the entries of the probes that lie in its own rows
    (lbm_slab_rows) and writes +0.0f to the others; no communication is added.  Combining the ranks' arrays is the caller's
    business: a float sum turns a probe's -0.0f into +0.0f, so selecting each entry from the rank that owns its row is the
    bit-exact way.
-   The register-tile engines take the values inside their kernels (info "probes_in_kernel" = 1): a sample step moves 16
-   bytes per probe and nothing else.  The other engines run the steps in pieces of `every` with a small gather kernel
-   behind each (correct, not fast; the same bits).
+   Which kernels take the probes:
+   - The register-tile engines take the values inside their kernels (info "probes_in_kernel" = 1): a sample step moves 16
+     bytes per probe and nothing else; av_vels is lbm_run's, bit for bit.
+   - Where lbm_wave runs (a lattice alone on its GPU with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block),
+     the probes ride in its launches (info "probes_in_wave" = 1, "probes_in_kernel" = 0): a probe flavour of lbm_wave
+     stores a probe's four floats at every sample step of a pass, read between the collision and the next step's
+     accelerate phase -- the values the stored lattice of that step would hold; the steps left over behind the last full
+     pass go as lbm_run's do, with the gather kernel behind those that are sample steps.  There av_vels is lbm_run's, bit
+     for bit, and the probes are the bits of the split path (below), whichever steps fell inside an lbm_wave launch.  If
+     the probe maps (5 bytes per cell) do not fit on the device, the run takes the split path: the same probes, no error.
+   - The remaining engines are unchanged: contexts where lbm_march runs, slabs with neighbours, rank contexts and runs
+     shorter than time_block run the steps in pieces of `every` with a small gather kernel behind each (correct, not fast;
+     the same bits; both keys read 0).  There av_vels is as for lbm_run_sampled / lbm_run_mean on those engines: equal
+     to lbm_run's within float rounding of the per-step sum.
    LBM_EINVAL with nothing queued and the lattice untouched when no probes are set, every <= 0, nsteps < 0, m = 0 or
    probes_out is NULL; LBM_ENOMEM likewise when the device staging of host output (16 m nprobes bytes per slab that holds
    a probe) or the register tiles' tables do not fit.  Rank contexts agree on both before anything is queued.
@@ -268,12 +278,16 @@ typedef struct {
    The lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels).  av_vels is bit-identical
    to lbm_run's wherever the register tiles ran the call (info "engine_last" = 3), in one launch or in pieces; on the
    streaming engines it is equal to lbm_run's within float rounding of the per-step sum, as for lbm_run_forces there.
-   How: forces with probes ride inside one register-tile launch (a kernel flavour of its own); means and snapshots -- and
-   probes where the register tiles do not run -- are taken behind pieces of the step loop that end on their sample steps
+   How: forces with probes ride inside one register-tile launch (a kernel flavour of its own); where lbm_wave runs (a
+   lattice alone, as for lbm_run_probes) forces and probes ride together in its launches, in a force-and-probe flavour,
+   and cut no piece: with those two alone the call is one piece and av_vels is lbm_run's, bit for bit; inside the pieces
+   that means and snapshots cut, the probes' sample steps keep counting from the start of the call.  Means and snapshots
+   -- and probes where neither the register tiles nor lbm_wave run -- are taken behind pieces of the step loop that end on their sample steps
    (each piece a launch of that flavour), by the small kernels the single calls fall back to (a 1024 x 1024 run with forces and mean_every = 100 stays on the
    register tiles and pays their per-run fixed cost once per 100 steps).  One observer alone simply runs its own call.
    Info "observed_in_kernel": bits 1 forces, 2 probes, 4 means, 8 snapshots -- what the last lbm_run_observed took inside
-   register-tile launches; "observed_pieces": the step-loop pieces it ran (1 = the whole call in one).  What the four
+   register-tile launches; "observed_in_wave": bits 1 forces, 2 probes -- what it took inside lbm_wave launches (then
+   "observed_in_kernel" reads 0); "observed_pieces": the step-loop pieces it ran (1 = the whole call in one).  What the four
    single calls' "*_in_kernel" keys read after lbm_run_observed is unspecified.  lbm_last_run_ms: the sums over the pieces.
    LBM_EINVAL with nothing queued and the lattice untouched: nsteps < 0; forces wanted without bodies; probes wanted
    without a probe set; probes or means wanted with every <= 0 or no sample step in nsteps; fields_every < 0 (0, or no
@@ -340,8 +354,9 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
  * "forces_in_wave" (1: the last lbm_run_forces took its per-cell contributions inside lbm_wave launches),
  * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles),
- * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles), "observed_in_kernel",
- * "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles),
+ * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches), "observed_in_kernel",
+ * "observed_in_wave", "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */
