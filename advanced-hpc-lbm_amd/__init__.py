@@ -211,7 +211,10 @@ class Lattice:
     def run_sampled(self, nsteps: int, every: int, out=None):
         """lbm_run with snapshots after steps every, 2 every, ...: returns (av_vels[nsteps], fields) where fields is
         (m, rows, nx, 4) float32 (u_x, u_y, |u|, pressure; m = nsteps // every; as final_state), a numpy array -- or
-        `out`, a contiguous float32 torch tensor of that shape on the context's GPU, filled there."""
+        `out`, a contiguous float32 torch tensor of that shape on the context's GPU, filled there.  The register tiles
+        write the snapshots inside their kernels (info("samples_in_kernel") == 1); where lbm_wave runs they ride in its
+        launches (info("samples_in_wave") == 1: av_vels is run()'s bits, the fields are the split path's bits); elsewhere
+        the steps run in pieces of `every` with a derive kernel behind each."""
         m = nsteps // every if every > 0 else 0
         shape = (m, self._local_rows(), self.params.nx, 4)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
@@ -233,7 +236,10 @@ class Lattice:
         """lbm_run with the time-averaged fields over the sample steps every, 2 every, ...: returns (av_vels[nsteps], mean)
         where mean is (rows, nx, 4) float32 (u_x, u_y, |u|, pressure; the float sum of run_sampled's snapshots in step
         order, divided by their number), a numpy array -- or `out`, a contiguous float32 torch tensor of that shape on
-        the context's GPU, filled there."""
+        the context's GPU, filled there.  The register tiles keep the sums inside their kernels
+        (info("mean_in_kernel") == 1); where lbm_wave runs they ride in its launches (info("mean_in_wave") == 1: av_vels is
+        run()'s bits, the mean is the split path's bits); elsewhere the steps run in pieces of `every` with an add kernel
+        behind each."""
         shape = (self._local_rows(), self.params.nx, 4)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
         if out is None:

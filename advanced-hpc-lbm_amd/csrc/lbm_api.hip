@@ -261,6 +261,9 @@ struct lbm_ctx {
   int forces_in_kernel = 0;    // 1: the last lbm_run_forces took its sums inside the register tiles
   int forces_in_wave = 0;      // 1: the last lbm_run_forces took its per-cell contributions inside lbm_wave launches
   int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
+  int samples_in_wave = 0;     // 1: the last lbm_run_sampled took its snapshots inside lbm_wave launches
+  int mean_in_wave = 0;        // 1: the last lbm_run_mean took its sums inside lbm_wave launches
+  long wave_launches = 0;      // lbm_wave kernels this context has launched so far, every flavour (launch_wave counts them)
   int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
   int probes_in_wave = 0;      // 1: the last lbm_run_probes took its values inside lbm_wave launches
   int observed_in_wave = 0;    // the last lbm_run_observed: bits 1 forces, 2 probes taken inside lbm_wave launches
@@ -658,6 +661,15 @@ static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
   return wave_probe_ready(c, with_forces);
 }
 
+// May a snapshot or mean run of this context take its fields inside lbm_wave launches?  wave_probes_admit's conditions on
+// the context, without the maps: the field flavour reads the plain obstacle bytes.  Asked before anything is queued; no: the
+// caller keeps the split path.  (Whether a run is long enough for a group is the caller's question.)
+static bool wave_fields_admit(lbm_ctx* c) {
+  if (c->rank_mode || c->exchange != 0 || !march_eligible(c) || !use_wave_kernel(c)) return false;
+  if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
+  return (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap;
+}
+
 // The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean; with k.probe: lbm_run_probes): ONLY the
 // register tiles are tried, with the snapshots (the sums, the probes) in the kernel; if they did not run (samples_in_kernel /
 // mean_in_kernel / probes_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
@@ -711,15 +723,35 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   const bool pw = k.wave_pout != nullptr;
   auto psample = [&](int s) { return pw && s >= k.pfirst && (s - k.pfirst) % k.wave_pevery == 0; };
   auto prow = [&](int s) { return (s - k.pfirst) / k.wave_pevery; };
-  // ... a left-over step that is one: the probes' cells of the lattice just stored (stored WITHOUT the next step's
-  // accelerate phase, which `then_accelerate` applies behind the gather as the prologue does, to the same bits)
+  // fields on an admitted context (RunKind::wave_fout): is step s (1-based) of this run a sample step, and its field
+  const bool fw = k.wave_fout != nullptr;
+  // (the field flavour is a flavour of its own: refused before anything is queued, launch_wave would refuse it mid-run)
+  if (fw && (pw || fo)) return fail(LBM_EINVAL, "run_steps: fields inside lbm_wave run beside neither probes nor forces");
+  auto fsample = [&](int s) { return fw && s % k.wave_fevery == 0; };
+  auto fslot = [&](int s) { return k.wave_fout + (size_t)(s / k.wave_fevery - 1) * (size_t)k.wave_fstride; };
+  // ... a left-over step that is a sample step: the probes' cells of the lattice just stored (stored WITHOUT the next step's
+  // accelerate phase, which `then_accelerate` applies behind the gather as the prologue does, to the same bits); for fields
+  // likewise, the stored lattice through the kernels of the split path, lbm_derive into the sample's slot or lbm_mean_add
+  // into the sums
   auto pgather = [&](int s, bool then_accelerate) -> int {
     Slab& sl = c->slabs[0];
-    const int n_here = (int)sl.pcells_host.size();
     HIPC(hipSetDevice(sl.dev));
-    hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane,
-                       sl.pcells, n_here, sl.blocked, c->p.density, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes);
-    HIPC(hipGetLastError());
+    if (psample(s)) {
+      const int n_here = (int)sl.pcells_host.size();
+      hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane,
+                         sl.pcells, n_here, sl.blocked, c->p.density, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes);
+      HIPC(hipGetLastError());
+    }
+    if (fsample(s)) {
+      const long ncell = (long)sl.nyl * nx;
+      if (k.wave_fadd)
+        hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
+                           nx, ncell, sl.blocked, c->p.density, k.wave_fout);
+      else
+        hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
+                           nx, ncell, sl.blocked, c->p.density, fslot(s), k.wave_fpart, k.wave_fmass);
+      HIPC(hipGetLastError());
+    }
     if (then_accelerate && sl.accel_row >= 0) {
       hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, sl.sc,
                          sl.lat[c->cur], sl.plane, sl.pitch, nx, sl.accel_row, sl.blocked, a1, a2);
@@ -836,10 +868,17 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
         for (int l = K; l >= 1; --l)
           if (psample(tt + l)) { wp.mask |= 1u << (l - 1); wp.row = prow(tt + l); }
       }
-      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, wp) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+      WaveFields wf;
+      if (fw && wave) {                                  // likewise: the first sample's field
+        wf.stride = k.wave_fstride; wf.add = k.wave_fadd;
+        for (int l = K; l >= 1; --l)
+          if (fsample(tt + l)) { wf.mask |= 1u << (l - 1); wf.out = fslot(tt + l); }
+      }
+      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, wp, wf) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
     }
     if (fwave) c->forces_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
+    if (fw && wave) { if (k.wave_fadd) c->mean_in_wave = 1; else c->samples_in_wave = 1; }
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -849,11 +888,11 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   if (pairs && nsteps - tt >= 2) {
     const int npairs = (nsteps - tt) / 2;
     for (int j = 0; j < npairs; ++j, ++li, tt += 2) {
-      const bool p1 = psample(tt + 1), p2 = psample(tt + 2);
+      const bool p1 = psample(tt + 1) || fsample(tt + 1), p2 = psample(tt + 2) || fsample(tt + 2);
       if (fo || p1) {
-        // (a forces run behind its lbm_wave groups, a lattice alone; a probe run whose sample step this is) the pair's first
-        // step alone into the destination lattice, for its forces and probes -- its speed sums go unused -- then the pair
-        // from the same source over it
+        // (a forces run behind its lbm_wave groups, a lattice alone; a probe, snapshot or mean run whose sample step this is)
+        // the pair's first step alone into the destination lattice, for its forces, probes and fields -- its speed sums go
+        // unused -- then the pair from the same source over it
         if ((rc = launch_single(c, li, tt, true, false, a1, a2))) return rc;
         if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
         if (p1 && (rc = pgather(tt + 1, false))) return rc;
@@ -874,7 +913,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   }
   const int first_single = tt;
   for (; tt < nsteps; ++tt, ++li) {
-    const bool ps = psample(tt + 1);
+    const bool ps = psample(tt + 1) || fsample(tt + 1);
     if ((rc = launch_single(c, li, tt, tt == nsteps - 1 || ps, tt > first_single, a1, a2))) return rc;
     if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
     if (ps && (rc = pgather(tt + 1, tt + 1 < nsteps))) return rc;
@@ -937,7 +976,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
   if (every < 0) return fail(LBM_EINVAL, "every < 0");
   const int m = every > 0 ? nsteps / every : 0;
   if (m > 0 && !fields_out) return fail(LBM_EINVAL, "fields_out is NULL but %d snapshot(s) are due", m);
-  c->samples_in_kernel = 0;
+  c->samples_in_kernel = 0; c->samples_in_wave = 0;
   if (m == 0) return run_steps(c, nsteps, av_vels);
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
@@ -983,6 +1022,29 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
       return LBM_OK;
     }
     // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run)
+  }
+  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps that hold a sample step in
+  // lbm_wave's field flavour, which stores every delivered cell's fields at the sample levels of a pass; lbm_derive behind
+  // the left-over steps that are sample steps.  Device output is written in place, host output goes through one staging of
+  // the m snapshots.  Decided here, before anything is queued; a staging that does not fit: the pieces below, the same bits.
+  if (nsteps >= c->time_block && wave_fields_admit(c)) {
+    Slab& s = c->slabs[0];
+    HIPC(hipSetDevice(s.dev));
+    DeviceTemp stage, part;
+    bool room = true;
+    if (!on_dev && hipMalloc(&stage.p, sizeof(float) * (size_t)m * (size_t)slot) != hipSuccess) { stage.p = nullptr; room = false; }
+    // (lbm_derive leaves a float and a double per block, unused here; the partial-sum buffers are busy during a run)
+    const size_t nblk = (size_t)cdiv((long)s.nyl * nx, lbm::kBlock);
+    if (room && hipMalloc(&part.p, (sizeof(double) + sizeof(float)) * nblk) != hipSuccess) { part.p = nullptr; room = false; }
+    if (!room) (void)hipGetLastError();
+    else {
+      RunKind k;
+      k.no_tiles = true; k.wave_fout = on_dev ? fields_out : (float*)stage.p; k.wave_fevery = every; k.wave_fstride = slot;
+      k.wave_fmass = (double*)part.p; k.wave_fpart = (float*)(k.wave_fmass + nblk);
+      if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+      if (!on_dev) HIPC(hipMemcpy(fields_out, stage.p, sizeof(float) * (size_t)m * (size_t)slot, hipMemcpyDeviceToHost));
+      return LBM_OK;
+    }
   }
   // ---- the step loop split at the sample steps: each piece a complete run, then lbm_final_state's derive into its slot
   double gpu_ms = 0.0, wall_ms = 0.0;
@@ -1090,7 +1152,7 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
   const int m = nsteps / every;
   if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
   if (!mean_out) return fail(LBM_EINVAL, "mean_out is NULL");
-  c->mean_in_kernel = 0;
+  c->mean_in_kernel = 0; c->mean_in_wave = 0;
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   const int nx = c->p.nx;
@@ -1133,6 +1195,24 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     if (c->mean_in_kernel) return to_host();
     // (the register tiles did not run, or gave up with the lattice untouched and nothing stored: the pieces below repeat the run)
+  }
+  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps that hold a sample step in
+  // lbm_wave's field flavour, which adds every delivered cell's fields to the slab's sums at the sample levels of a pass, in
+  // the order of the steps; lbm_mean_add behind the left-over steps that are sample steps.  The same adds in the same order
+  // as below.
+  if (nsteps >= c->time_block && wave_fields_admit(c)) {
+    Slab& s = c->slabs[0];
+    HIPC(hipSetDevice(s.dev));
+    const long ncell = (long)s.nyl * nx;
+    HIPC(hipMemsetAsync(acc[0].p, 0, sizeof(float) * 4 * (size_t)ncell, s.sc));
+    RunKind k;
+    k.no_tiles = true; k.wave_fout = (float*)acc[0].p; k.wave_fevery = every; k.wave_fstride = 0; k.wave_fadd = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, (const float*)acc[0].p, ncell,
+                       (float)m, out_of(0));
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s.sc));
+    return to_host();
   }
   // ---- the step loop split at the sample steps: each piece a complete run, then the fields of the stored lattice added to
   // the slab's sums (no snapshot, no host round trip per sample); the same adds in the same order as in the register tiles.
@@ -1579,6 +1659,9 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
   if (!strcmp(key, "forces_in_wave")) { *value = c->forces_in_wave; return LBM_OK; }
   if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "samples_in_wave")) { *value = c->samples_in_wave; return LBM_OK; }
+  if (!strcmp(key, "mean_in_wave")) { *value = c->mean_in_wave; return LBM_OK; }
+  if (!strcmp(key, "wave_launches")) { *value = (double)c->wave_launches; return LBM_OK; }
   if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
   if (!strcmp(key, "probes_in_wave")) { *value = c->probes_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_wave")) { *value = c->observed_in_wave; return LBM_OK; }

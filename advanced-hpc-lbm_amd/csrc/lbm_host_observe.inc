@@ -84,7 +84,9 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     else rc = lbm_run(c, nsteps, av_vels);
     if (!rc) {
       const int m = wp ? mp : wm ? mm : ws ? msn : 0, ev = wp ? pe : wm ? me : se;
-      c->observed_pieces = (wanted == 0 || wf || c->observed_in_kernel != 0 || c->observed_in_wave != 0) ? 1 : m + (nsteps > m * ev ? 1 : 0);
+      // (a lone mean or snapshot series that rode in lbm_wave launches ran in one piece too; observed_in_wave keeps its two bits)
+      const bool fields_in_wave = (wm && c->mean_in_wave) || (ws && c->samples_in_wave);
+      c->observed_pieces = (wanted == 0 || wf || c->observed_in_kernel != 0 || c->observed_in_wave != 0 || fields_in_wave) ? 1 : m + (nsteps > m * ev ? 1 : 0);
     }
     return rc;
   }

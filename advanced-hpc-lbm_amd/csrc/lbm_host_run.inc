@@ -41,6 +41,18 @@ struct RunKind {
   // flavours; behind a left-over step that is a sample step, lbm_probe_gather.
   float* wave_pout = nullptr;
   int wave_pevery = 0;
+  // wave_fout (lbm_run_sampled / lbm_run_mean on a context wave_fields_admit said yes to; a lattice alone, the register
+  // tiles kept off): the sample steps are wave_fevery, 2 wave_fevery, ... steps into this run; wave_fout is the first
+  // sample's field, [ny][nx][4] floats on the slab's device, wave_fstride the floats from one sample's field to the next;
+  // wave_fadd: the samples are added into ONE field (wave_fstride = 0), the sums of a mean.  The groups of K steps take them
+  // inside lbm_wave's field flavour; behind a left-over step that is a sample step, lbm_derive into the slot (its sums go to
+  // wave_fpart / wave_fmass, one float / double per block of the kernel, and are not used) or lbm_mean_add into the sums.
+  float* wave_fout = nullptr;
+  int wave_fevery = 0;
+  long wave_fstride = 0;
+  bool wave_fadd = false;
+  float* wave_fpart = nullptr;
+  double* wave_fmass = nullptr;
 };
 
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the

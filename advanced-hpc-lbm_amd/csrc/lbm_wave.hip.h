@@ -71,6 +71,13 @@ struct WaveArgs {
   unsigned pmask;              // bit l - 1: step t + l of this pass is a sample step
   int prow;                    // the output row of the pass's first sample; a later one's: + the sample levels below it
   float density;               // what derive_cell gives a blocked cell's pressure from
+  // ---- the field flavour (FIELD; a lattice alone, lbm_run_sampled / lbm_run_mean): `blocked` stays the obstacle bytes, and
+  // at the sample levels of the pass EVERY delivered cell's lane takes what derive_cell gives for the cell to its place of a
+  // field in lbm_derive's layout, [ny][nx][4] -- nx, not pitch
+  unsigned fmask;              // bit l - 1: step t + l of this pass is a sample step
+  float* fout;                 // the output base of the pass's first sample
+  long fstride;                // floats between consecutive samples' outputs (snapshots: one field; sums: 0)
+  int fadd;                    // 0: stored (snapshots); 1: added to what is there (the sums of lbm_run_mean)
 };
 
 constexpr int kWaveBlock = 256;   // four independent waves per block (they only meet for the final sums)
@@ -110,7 +117,17 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // never does.)  At a sample level -- wave-uniform, a bit of pmask: a level that samples nothing costs one scalar test --
 // the lane that owns a probe's cell (own_row && out_ok) stores the four floats into the probe's place of the sample's
 // output row.  "Probe" rides down the levels in a third bit field, from the same map byte.
-template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false>
+// FIELD (lbm_run_sampled / lbm_run_mean where lbm_wave runs; a lattice alone, a flavour of its own): at the same point, at a
+// sample level (a bit of fmask, wave-uniform: a level that samples nothing costs one scalar test), every lane that delivers
+// cells (own_row && out_ok) hands each of them to derive_cell -- the plain obstacle bit of mreg serves, no map of its own --
+// and stores the four floats at 4 * (row * nx + column) of the sample's field: a snapshot (fadd = 0; one 16-byte store per
+// cell, a lane's two cells 32 contiguous bytes), or an add into the sums of a mean (fadd = 1; fstride = 0: load the four
+// sums, four float adds, store them back -- no contraction, lbm_mean_add's arithmetic).
+// Why the adds come in the order of the steps, as lbm_mean_add's do: own_row and out_ok do not depend on the level, so ONE
+// lane of ONE wave owns a cell at every level of a pass; it reaches levels l and l + 1 of a row in consecutive iterations,
+// in program order; so the adds of one pass into a cell's sums are same-thread accesses to one address (plain loads and
+// stores, not the nontemporal helpers), and the adds of different passes are ordered by the stream.
+template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
 void lbm_wave(const WaveArgs a) {
   constexpr bool FAST = (MODE & kFastMath) != 0, NTS = (MODE & kNtStore) != 0, NTL = (MODE & kNtLoad) != 0;
@@ -119,6 +136,7 @@ void lbm_wave(const WaveArgs a) {
   static_assert(C == 1 || (C == 2 && K % 2 == 0), "one or two columns per lane; pairs need an even K");
   static_assert(!(FORCE && SLAB), "the force flavour is for a lattice alone");
   static_assert(!(PROBE && SLAB), "the probe flavours are for a lattice alone");
+  static_assert(!(FIELD && (SLAB || FORCE || PROBE)), "the field flavour is for a lattice alone, and a flavour of its own");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -257,6 +275,29 @@ void lbm_wave(const WaveArgs a) {
         }
       }
     };
+    // FIELD, at a sample level behind collide_cell(s): every delivered cell of the level's row into the sample's field
+    [[maybe_unused]] auto store_fields = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
+      if (own_row && ((a.fmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
+        if (out_ok) {                            // (row S0 + j - l in [Y0, Y0 + hy), columns X0 - K + C lane + c in [X0, X0 + wx))
+#pragma clang fp contract(off)
+          float* o = a.fout + (long)__builtin_popcount(a.fmask & ((1u << (l - 1)) - 1u)) * a.fstride +
+                     4 * ((long)(S0 + j - l) * a.nx + (X0 - K + C * lane));
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            float rho;
+            const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
+            f4a* at = reinterpret_cast<f4a*>(o + 4 * c);
+            if (a.fadd != 0) {                   // (wave-uniform) the sums of a mean: one rounding per add, the order of the steps
+              f4a s = *at;
+              s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+              *at = s;
+            } else {
+              *at = v;
+            }
+          }
+        }
+      }
+    };
     float nxt[C][9]; unsigned nblk;
     load_row(nxt, nblk);
     // One iteration.  STEADY: past the 2K fill iterations of the chunk every level has its history, the "is this level
@@ -315,6 +356,7 @@ void lbm_wave(const WaveArgs a) {
             const bool blk = ((mreg[0] >> l) & 1u) != 0u;
             const float sp = collide_cell<FAST>(p[0], blk, a.omega);
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
+            if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
             if (acc) accelerate_cell(p[0], blk, a.a1, a.a2);
             sum[l - 1] += (out_ok && own_row) ? sp : 0.f;
           } else {
@@ -324,6 +366,7 @@ void lbm_wave(const WaveArgs a) {
             for (int c = 0; c < C; ++c) blk[c] = ((mreg[c] >> l) & 1u) != 0u;
             collide_cells<FAST, C>(p, blk, a.omega, sp);      // the lane's cells statement by statement: independent chains
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
+            if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
 #pragma unroll
             for (int c = 0; c < C; ++c)
               if (acc) accelerate_cell(p[c], blk[c], a.a1, a.a2);

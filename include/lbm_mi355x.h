@@ -147,6 +147,20 @@ int lbm_run(lbm_ctx* ctx, int nsteps, float* av_vels);
  * copied to the host).  The register-tile engines write the snapshots from inside their kernels (info
  * "samples_in_kernel" = 1); the other engines run the steps in pieces with a derive after each.  LBM_ENOMEM /
  * LBM_EINVAL before anything runs when the device staging or the snapshots do not fit: the lattice is untouched.
+ * Which kernels take the snapshots:
+ * - The register-tile engines write them from inside their kernels ("samples_in_kernel" = 1); av_vels is lbm_run's, bit
+ *   for bit.
+ * - Where lbm_wave runs (a lattice alone on its GPU with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block),
+ *   the snapshots ride in its launches (info "samples_in_wave" = 1, "samples_in_kernel" = 0): a field flavour of lbm_wave
+ *   stores every cell's four floats at every sample step of a pass, read between the collision and the next step's
+ *   accelerate phase -- the values the stored lattice of that step would hold; passes without a sample step run the plain
+ *   kernel, and the steps left over behind the last full pass go as lbm_run's do, with the derive kernel behind those that
+ *   are sample steps.  In lbm_wave, av_vels is lbm_run's, bit for bit; the fields are the bits of the split path (below).
+ *   Device output is written in place; host output goes through one device staging of the m snapshots, and if that
+ *   staging has no room the run falls back to the split path: the same fields, no error.
+ * - The remaining engines are unchanged: contexts where lbm_march runs, slabs with neighbours, rank contexts and runs
+ *   shorter than time_block run the steps in pieces of `every` with a derive after each (the split path; correct, not
+ *   fast; both keys read 0).
  * With forces, probes or means in one run: lbm_run_observed.
  */
 int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* fields_out);
@@ -168,7 +182,20 @@ int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* 
  * buffer (16 bytes per cell) does not fit; in both cases before anything runs: the lattice is untouched.
  * A window that starts late is lbm_run(ctx, skip, ...) followed by lbm_run_mean; the means of consecutive calls can be
  * combined by the caller in double (weights m).  Accuracy: a plain float sum of m terms carries at most (m - 1) 2^-24
- * relative to the sum of |X_j| per cell.  With snapshots, forces or probes in one run: lbm_run_observed.
+ * relative to the sum of |X_j| per cell.
+ * Which kernels take the sums:
+ * - The register-tile engines keep them inside their kernels ("mean_in_kernel" = 1); av_vels is lbm_run's, bit for bit.
+ * - Where lbm_wave runs (a lattice alone on its GPU with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block),
+ *   the sums ride in its launches (info "mean_in_wave" = 1, "mean_in_kernel" = 0): at every sample step of a pass the
+ *   field flavour of lbm_wave adds every cell's four floats into the per-slab buffer (one lane owns a cell through all
+ *   steps of a pass and passes follow each other on one stream: the adds keep the order of the steps); the steps left
+ *   over behind the last full pass go as lbm_run's do, with the add kernel behind those that are sample steps.  In
+ *   lbm_wave, av_vels is lbm_run's, bit for bit; the fields are the bits of the split path (below).  The buffer is the one
+ *   every path allocates: where it has no room the call fails as before, and a context that cannot run lbm_wave falls
+ *   back to the split path.
+ * - The remaining engines are unchanged: contexts where lbm_march runs, slabs with neighbours, rank contexts and runs
+ *   shorter than time_block keep the split path (pieces of `every` steps, the add kernel behind each; both keys read 0).
+ * With snapshots, forces or probes in one run: lbm_run_observed.
  */
 int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mean_out);
 
@@ -354,6 +381,9 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
  * "forces_in_wave" (1: the last lbm_run_forces took its per-cell contributions inside lbm_wave launches),
  * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles),
+ * "samples_in_wave" (1: the last lbm_run_sampled took its snapshots inside lbm_wave launches),
+ * "mean_in_wave" (1: the last lbm_run_mean took its sums inside lbm_wave launches),
+ * "wave_launches" (the lbm_wave kernels this context has launched on a lattice alone, every flavour: one per pass of K steps),
  * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles),
  * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches), "observed_in_kernel",
  * "observed_in_wave", "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
