@@ -232,6 +232,91 @@ def run_band(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, j0: int, j
     return a[K:K + (j1 - j0)].copy()
 
 
+def run_band_steps(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, j0: int, j1: int, nsteps: int,
+                   dtype=np.float64):
+    """run_band after EVERY step: yields (t, rows [j0, j1) after step t) for t = 1 .. nsteps, each (j1 - j0, nx, 9) in
+    `dtype` and the caller's own (a copy), each what run_band(..., K = t, ...) returns, from ONE run of rows
+    j0 - nsteps .. j1 + nsteps - 1 (the same wrap, accelerate row and whole-lattice fall-back as run_band): after step t
+    the band's own wrap has spoilt t rows at either end, never rows [j0, j1).  So a series over the steps -- forces,
+    probes -- costs one band run, not nsteps of them."""
+    ny = prm.ny
+    if not (0 <= j0 < ny and j0 < j1 <= j0 + ny and nsteps >= 0):
+        raise ValueError(f"band [{j0}, {j1}) of {nsteps} steps on {ny} rows")
+    orc = _oracle_for(dtype)
+    if 2 * nsteps + (j1 - j0) >= ny:
+        out_rows = np.arange(j0, j1) % ny
+        a = np.ascontiguousarray(cells, dtype=dtype).copy()
+        ob = np.ascontiguousarray(obstacles, dtype=np.int32)
+        for t in range(1, nsteps + 1):
+            orc.run(prm, a, ob, 1)
+            yield t, a[out_rows]
+        return
+    rows = band_rows(ny, j0, j1, nsteps)
+    a = np.ascontiguousarray(cells[rows], dtype=dtype)
+    b = np.empty_like(a)
+    ob = np.ascontiguousarray(obstacles[rows], dtype=np.int32)
+    bp = band_param(prm, len(rows))
+    acc = np.nonzero(rows == ny - 2)[0]
+    for t in range(1, nsteps + 1):
+        for r in acc:
+            orc.accelerate_row(bp, a, ob, int(r))
+        orc.sweep_rows(bp, a, b, ob, 0, len(rows))
+        a, b = b, a
+        yield t, a[nsteps:nsteps + (j1 - j0)].copy()
+
+
+# directions 1..8: E N W S NE NW SW SE (index 0: rest), and the direction opposite to each
+CX = np.array([0, 1, 0, -1, 0, 1, -1, -1, 1])
+CY = np.array([0, 0, 1, 0, -1, 1, 1, -1, -1])
+OPP = np.array([0, 3, 4, 1, 2, 7, 8, 5, 6])
+
+
+def band_forces(rows: np.ndarray, obstacles_ext: np.ndarray, body: np.ndarray, nbodies: int) -> dict:
+    """The force definition of include/lbm_mi355x.h on a window of rows, in plain numpy float64:
+        F_b = 2 sum over the blocked cells B of label b, over the directions i whose source cell B - c_i is fluid, of
+              c_i f_opp(i)(B)
+    rows: the stored lattice in the window (h, nx, 9), any float type; obstacles_ext: the obstacle rows of the window
+    AND one row either side (h + 2, nx) -- whether B - c_i is fluid is asked of the row below and the row above;
+    body: the labels in the window (h, nx), 0 = not counted (labels on fluid cells are ignored).  Columns wrap.  The
+    whole lattice is the window [0, ny) with obstacles_ext = obstacles[arange(-1, ny + 1) % ny].  Returns, per body b
+    (index b - 1) and where it applies per component k (x, y):
+      F[nb, 2]        the force;
+      A[nb, 2]        2 sum |c_ik| |f_opp(i)(B)| over the counted links: the scale of any float32 evaluation's rounding;
+      links[nb, 2]    sum |c_ik| over the counted links (how far an error of every population can move F / 2);
+      cells[nb]       the counted cells: labelled b, blocked, with at least one fluid source;
+      min_link[nb]    the smallest |2 f_opp(i)(B)| of any counted link (inf where there is none)."""
+    lat = np.asarray(rows)
+    h, nx = lat.shape[:2]
+    blocked = np.asarray(obstacles_ext) != 0
+    if blocked.shape != (h + 2, nx) or np.shape(body) != (h, nx):
+        raise ValueError("obstacles_ext must hold the window's rows and one row either side; body the window's rows")
+    label = np.where(blocked[1:-1], np.asarray(body), 0).astype(np.int64)
+    if label.min(initial=0) < 0 or label.max(initial=0) > nbodies:
+        raise ValueError("labels must lie in [0, nbodies]")
+    F, A, links = (np.zeros((nbodies, 2)) for _ in range(3))
+    min_link = np.full(nbodies, np.inf)
+    counted = np.zeros((h, nx), bool)
+    for i in range(1, 9):
+        src_fluid = np.roll(~blocked[1 - CY[i]:1 - CY[i] + h], CX[i], axis=1)      # [y, x] = fluid at (x - cx, y - cy)
+        lab = np.where(src_fluid, label, 0).ravel()
+        counted |= (lab > 0).reshape(h, nx)
+        v = lat[..., OPP[i]].astype(np.float64).ravel()
+        c = np.array([CX[i], CY[i]], dtype=np.float64)
+        s = np.bincount(lab, weights=v, minlength=nbodies + 1)[1:nbodies + 1]
+        a = np.bincount(lab, weights=np.abs(v), minlength=nbodies + 1)[1:nbodies + 1]
+        n = np.bincount(lab, minlength=nbodies + 1)[1:nbodies + 1]
+        F += 2.0 * s[:, None] * c
+        A += 2.0 * a[:, None] * np.abs(c)
+        links += n[:, None] * np.abs(c)
+        on = lab > 0
+        if on.any():
+            m = np.full(nbodies + 1, np.inf)
+            np.minimum.at(m, lab[on], 2.0 * np.abs(v[on]))
+            min_link = np.minimum(min_link, m[1:])
+    cells = np.bincount(label[counted], minlength=nbodies + 1)[1:nbodies + 1]
+    return dict(F=F, A=A, links=links, cells=cells, min_link=min_link)
+
+
 def step_chunks(prm: OrcParam, cells: np.ndarray, obstacles: np.ndarray, rows_per_chunk: int, dtype=np.float64):
     """One whole-lattice step (accelerate + sweep) of the strict oracle in `dtype`, chunk by chunk: yields
     (r0, r1, new rows [r0, r1) as (r1 - r0, nx, 9) in dtype, speed sum of the chunk, fluid cells of the chunk).  Each
