@@ -218,17 +218,7 @@ class Lattice:
         m = nsteps // every if every > 0 else 0
         shape = (m, self._local_rows(), self.params.nx, 4)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
-        if out is None:
-            fields = np.empty(shape, dtype=np.float32)
-            ptr = fields.ctypes.data if m > 0 else None
-        else:
-            import torch
-            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
-                    or not out.is_contiguous() or tuple(out.shape) != shape):
-                raise LbmError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
-            fields = out
-            ptr = out.data_ptr() if m > 0 else None
-            torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        fields, ptr = self._output(out, shape, "out")
         _check(self._lib.lbm_run_sampled(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, fields
 
@@ -242,17 +232,7 @@ class Lattice:
         behind each."""
         shape = (self._local_rows(), self.params.nx, 4)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
-        if out is None:
-            mean = np.empty(shape, dtype=np.float32)
-            ptr = mean.ctypes.data
-        else:
-            import torch
-            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
-                    or not out.is_contiguous() or tuple(out.shape) != shape):
-                raise LbmError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
-            mean = out
-            ptr = out.data_ptr()
-            torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        mean, ptr = self._output(out, shape, "out")
         _check(self._lib.lbm_run_mean(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, mean
 
@@ -280,17 +260,7 @@ class Lattice:
         n = getattr(self, "_nprobes", 0)
         shape = (max(nsteps, 0) // every if every > 0 else 0, n, 4)
         av = np.empty(max(nsteps, 0), dtype=np.float32)
-        if out is None:
-            probes = np.empty(shape, dtype=np.float32)
-            ptr = probes.ctypes.data if probes.size else None
-        else:
-            import torch
-            if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda
-                    or not out.is_contiguous() or tuple(out.shape) != shape):
-                raise LbmError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
-            probes = out
-            ptr = out.data_ptr()
-            torch.cuda.synchronize(out.device)      # (the library's streams do not follow torch's)
+        probes, ptr = self._output(out, shape, "out")
         _check(self._lib.lbm_run_probes(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, probes
 
@@ -320,8 +290,8 @@ class Lattice:
         return av, forces
 
     def _output(self, out, shape, name):
-        """(array or tensor, pointer) of one output of run_observed: a fresh numpy array, or `out`, validated as the single
-        calls validate theirs."""
+        """(array or tensor, pointer) of one output of a run_* call: a fresh numpy array, or `out`, a contiguous float32
+        CUDA tensor of that shape, waited for.  The pointer is None where there is nothing to write."""
         if out is None:
             arr = np.empty(shape, dtype=np.float32)
             return arr, (arr.ctypes.data if arr.size else None)

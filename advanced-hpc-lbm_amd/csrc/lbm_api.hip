@@ -648,32 +648,30 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 #include "lbm_host_run.inc"
 
 static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
+static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind());
 
-// May a probe run of this context take its values inside lbm_wave launches (with_forces: forces beside them)?  The
-// conditions of the forces (run_steps, fwave) on the context -- a lattice alone, no ranks, no exchange, lbm_wave the
-// engine of the groups of K steps, their partial sums fit -- and the maps in place.  Asked before anything is queued; no:
-// the caller keeps the split path.  (Whether a run is long enough for a group is the caller's question.)
-static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
-  if (c->rank_mode || c->exchange != 0 || !march_eligible(c) || !use_wave_kernel(c)) return false;
-  if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
-  if ((long)c->time_block * wave_blocks(c) > c->slabs[0].partial_cap) return false;
-  if (with_forces && !wave_force_ready(c, c->time_block)) return false;
-  return wave_probe_ready(c, with_forces);
-}
-
-// May a snapshot or mean run of this context take its fields inside lbm_wave launches?  wave_probes_admit's conditions on
-// the context, without the maps: the field flavour reads the plain obstacle bytes.  Asked before anything is queued; no: the
-// caller keeps the split path.  (Whether a run is long enough for a group is the caller's question.)
-static bool wave_fields_admit(lbm_ctx* c) {
+// May an observer run of this context take its values inside lbm_wave launches?  A lattice alone, no ranks, no exchange,
+// lbm_wave the engine of the groups of K steps, their partial sums fit.  Asked before anything is queued; no: the caller
+// keeps the split path.  (Whether a run is long enough for a group is the caller's question.)  Snapshots and means need no
+// more: the field flavour reads the plain obstacle bytes.  (run_steps' fwave states the same terms but rank_mode: a rank
+// context of one rank that trades no halos takes its forces inside lbm_wave, and keeps doing so.)
+static bool wave_admit(lbm_ctx* c) {
   if (c->rank_mode || c->exchange != 0 || !march_eligible(c) || !use_wave_kernel(c)) return false;
   if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
   return (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap;
 }
 
+// ... and probes (with_forces: forces beside them): the maps in place as well.
+static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
+  return wave_admit(c) && (!with_forces || wave_force_ready(c, c->time_block)) && wave_probe_ready(c, with_forces);
+}
+
+#include "lbm_host_observe.inc"
+
 // The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean; with k.probe: lbm_run_probes): ONLY the
 // register tiles are tried, with the snapshots (the sums, the probes) in the kernel; if they did not run (samples_in_kernel /
 // mean_in_kernel / probes_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
-static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind()) {
+static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   const int nx = c->p.nx;
@@ -736,20 +734,13 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
   auto pgather = [&](int s, bool then_accelerate) -> int {
     Slab& sl = c->slabs[0];
     HIPC(hipSetDevice(sl.dev));
-    if (psample(s)) {
-      const int n_here = (int)sl.pcells_host.size();
-      hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane,
-                         sl.pcells, n_here, sl.blocked, c->p.density, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes);
-      HIPC(hipGetLastError());
-    }
-    if (fsample(s)) {
+    int rc;
+    if (psample(s) && (rc = launch_probe_gather(c, sl, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes))) return rc;
+    if (fsample(s) && k.wave_fadd && (rc = launch_mean_add(c, sl, k.wave_fout))) return rc;
+    if (fsample(s) && !k.wave_fadd) {
       const long ncell = (long)sl.nyl * nx;
-      if (k.wave_fadd)
-        hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
-                           nx, ncell, sl.blocked, c->p.density, k.wave_fout);
-      else
-        hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
-                           nx, ncell, sl.blocked, c->p.density, fslot(s), k.wave_fpart, k.wave_fmass);
+      hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
+                         nx, ncell, sl.blocked, c->p.density, fslot(s), k.wave_fpart, k.wave_fmass);
       HIPC(hipGetLastError());
     }
     if (then_accelerate && sl.accel_row >= 0) {
@@ -937,488 +928,6 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind
 
 extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) { return lbm_run_sampled(c, nsteps, av_vels, 0, nullptr); }
 
-// Output of lbm_run_sampled / lbm_run_mean (`what`: the argument's name): host memory, or device memory -- then of the device
-// that holds every slab, written in place.
-static int output_on_device(const lbm_ctx* c, const void* out, const char* what, bool* on_dev) {
-  *on_dev = false;
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeDevice) {
-    *on_dev = true;
-    for (auto& s : c->slabs)
-      if (s.dev != attr.device)
-        return fail(LBM_EINVAL, "%s is memory of device %d: device output needs every slab on that device (slab on %d)", what, attr.device, s.dev);
-  }
-  (void)hipGetLastError();      // (host memory unknown to HIP: an error the runtime remembers)
-  return LBM_OK;
-}
-
-// Before lbm_run_forces / lbm_run_mean queue anything: a rank context's ranks take the same path and fail together.  rc: this
-// rank's allocation result (`what` it was for); *in_kernel: would this rank use the register tiles -- on return, would every rank.
-// Returns what the call must return now, or LBM_OK.
-static int ranks_agree(lbm_ctx* c, int rc, bool* in_kernel, const char* what) {
-  if (!(c->rank_mode && c->slabs[0].comm != nullptr)) return rc;
-  // [0] ranks short of room, [1] ranks that would not use the tiles
-  Slab& s = c->slabs[0];
-  double v[2] = {rc ? 1.0 : 0.0, *in_kernel ? 0.0 : 1.0};
-  HIPC(hipSetDevice(s.dev));
-  HIPC(hipMemcpy(s.scratch_d, v, sizeof(v), hipMemcpyHostToDevice));
-  NCCLC(rccl::AllReduce(s.scratch_d, s.scratch_d, 2, rccl::kFloat64, rccl::kSum, s.comm, s.sc));
-  HIPC(hipStreamSynchronize(s.sc));
-  HIPC(hipMemcpy(v, s.scratch_d, sizeof(v), hipMemcpyDeviceToHost));
-  if (v[0] > 0.0) return rc ? rc : fail(LBM_ENOMEM, "another rank has no room for %s", what);
-  *in_kernel = *in_kernel && v[1] == 0.0;
-  return LBM_OK;
-}
-
-extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every, float* fields_out) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
-  if (every < 0) return fail(LBM_EINVAL, "every < 0");
-  const int m = every > 0 ? nsteps / every : 0;
-  if (m > 0 && !fields_out) return fail(LBM_EINVAL, "fields_out is NULL but %d snapshot(s) are due", m);
-  c->samples_in_kernel = 0; c->samples_in_wave = 0;
-  if (m == 0) return run_steps(c, nsteps, av_vels);
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
-  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
-  const int nx = c->p.nx;
-  const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
-  long rows = 0;
-  for (auto& s : c->slabs) rows += s.nyl;
-  const long slot = rows * nx * 4;                          // floats per snapshot
-  if ((unsigned long long)m > (unsigned long long)(PTRDIFF_MAX / 4) / (unsigned long long)slot)
-    return fail(LBM_EINVAL, "%d snapshots of %ld floats do not fit the address space", m, slot);
-  bool on_dev = false;
-  int rc;
-  if ((rc = output_on_device(c, fields_out, "fields_out", &on_dev))) return rc;
-  if (regtile_is_next(c)) {
-    // ---- in the kernel: straight into device output, or into one staging buffer per slab copied out after the run
-    SnapPlan sp;
-    sp.every = every;
-    std::vector<DeviceTemp> stage(c->slabs.size());
-    for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      if (on_dev) { sp.at.push_back(fields_out + 4L * (s.row0 - base_row) * nx); sp.stride.push_back(slot); continue; }
-      HIPC(hipSetDevice(s.dev));
-      const size_t bytes = sizeof(float) * 4 * (size_t)m * (size_t)s.nyl * (size_t)nx;
-      if (hipMalloc(&stage[i].p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        stage[i].p = nullptr;
-        return fail(LBM_ENOMEM, "no room on device %d for %d snapshot(s) of slab %zu (%zu bytes)", s.dev, m, i, bytes);
-      }
-      sp.at.push_back((float*)stage[i].p); sp.stride.push_back((long)s.nyl * nx * 4);
-    }
-    RunKind k;
-    k.snap = &sp;
-    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-    if (c->samples_in_kernel) {
-      if (!on_dev)
-        for (size_t i = 0; i < c->slabs.size(); ++i) {
-          Slab& s = c->slabs[i];
-          HIPC(hipSetDevice(s.dev));
-          const size_t w = sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx;
-          HIPC(hipMemcpy2D(fields_out + 4L * (s.row0 - base_row) * nx, sizeof(float) * (size_t)slot, stage[i].p, w, w, (size_t)m,
-                           hipMemcpyDeviceToHost));
-        }
-      return LBM_OK;
-    }
-    // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run)
-  }
-  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps that hold a sample step in
-  // lbm_wave's field flavour, which stores every delivered cell's fields at the sample levels of a pass; lbm_derive behind
-  // the left-over steps that are sample steps.  Device output is written in place, host output goes through one staging of
-  // the m snapshots.  Decided here, before anything is queued; a staging that does not fit: the pieces below, the same bits.
-  if (nsteps >= c->time_block && wave_fields_admit(c)) {
-    Slab& s = c->slabs[0];
-    HIPC(hipSetDevice(s.dev));
-    DeviceTemp stage, part;
-    bool room = true;
-    if (!on_dev && hipMalloc(&stage.p, sizeof(float) * (size_t)m * (size_t)slot) != hipSuccess) { stage.p = nullptr; room = false; }
-    // (lbm_derive leaves a float and a double per block, unused here; the partial-sum buffers are busy during a run)
-    const size_t nblk = (size_t)cdiv((long)s.nyl * nx, lbm::kBlock);
-    if (room && hipMalloc(&part.p, (sizeof(double) + sizeof(float)) * nblk) != hipSuccess) { part.p = nullptr; room = false; }
-    if (!room) (void)hipGetLastError();
-    else {
-      RunKind k;
-      k.no_tiles = true; k.wave_fout = on_dev ? fields_out : (float*)stage.p; k.wave_fevery = every; k.wave_fstride = slot;
-      k.wave_fmass = (double*)part.p; k.wave_fpart = (float*)(k.wave_fmass + nblk);
-      if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-      if (!on_dev) HIPC(hipMemcpy(fields_out, stage.p, sizeof(float) * (size_t)m * (size_t)slot, hipMemcpyDeviceToHost));
-      return LBM_OK;
-    }
-  }
-  // ---- the step loop split at the sample steps: each piece a complete run, then lbm_final_state's derive into its slot
-  double gpu_ms = 0.0, wall_ms = 0.0;
-  int done = 0;
-  for (int j = 0; j <= m; ++j) {
-    const int n = (j < m) ? every : nsteps - done;
-    if (n == 0) break;
-    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
-    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
-    done += n;
-    if (j < m && (rc = derive_all(c, fields_out + (size_t)j * (size_t)slot, nullptr, nullptr, on_dev))) return rc;
-  }
-  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
-  return LBM_OK;
-}
-
-extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nbodies < 0 || nbodies > LBM_MAX_BODIES) return fail(LBM_EINVAL, "nbodies must be in [0, %d] (got %d)", LBM_MAX_BODIES, nbodies);
-  if (nbodies > 0 && !body) return fail(LBM_EINVAL, "body is NULL");
-  const int nx = c->p.nx, ny = c->p.ny;
-  // c_i of directions 1..8 (E N W S NE NW SW SE)
-  static const int cx[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1}, cy[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
-  std::vector<std::vector<int4>> lists(c->slabs.size());
-  for (size_t k = 0; k < c->slabs.size() && nbodies > 0; ++k) {
-    const Slab& s = c->slabs[k];
-    for (int y = 0; y < s.nyl; ++y) {
-      const int gy = s.row0 + y, ky = gy - c->keep_row0;       // (row of obst_keep)
-      for (int x = 0; x < nx; ++x) {
-        if (!c->obst_keep[(size_t)ky * nx + x]) continue;       // (labels on fluid cells are ignored)
-        const int lab = body[(long)gy * nx + x];
-        if (lab < 0 || lab > nbodies) return fail(LBM_EINVAL, "label %d of blocked cell (%d, %d) is outside [0, %d]", lab, x, gy, nbodies);
-        if (lab == 0) continue;
-        unsigned m = 0u;
-        for (int i = 1; i <= 8; ++i) {
-          const int sx = ((x - cx[i]) % nx + nx) % nx, sy = ky - cy[i];   // the source cell B - c_i (wraps in x; rows: kept)
-          if (!c->obst_keep[(size_t)sy * nx + sx]) m |= 1u << (i - 1);
-        }
-        if (m) lists[k].push_back(int4{x, y, (int)(m | ((unsigned)lab << 8)), 0});
-      }
-    }
-  }
-  (void)ny;
-  for (size_t k = 0; k < c->slabs.size(); ++k) {
-    Slab& s = c->slabs[k];
-    HIPC(hipSetDevice(s.dev));
-    if (s.fcells) HIPC(hipFree(s.fcells));
-    s.fcells = nullptr; s.fcells_n = 0; s.fty = 0;
-    wave_force_free(s);                 // (lbm_wave's force maps follow the list: rebuilt by the next forces run that wants them)
-    wave_probe_free(s, false);          // (... and so does the force-and-probe map)
-    s.fcells_host.swap(lists[k]);
-    if (s.fcells_host.empty()) continue;
-    std::vector<int2> dev(s.fcells_host.size());
-    for (size_t j = 0; j < dev.size(); ++j)
-      dev[j] = int2{s.fcells_host[j].y * s.pitch + s.fcells_host[j].x, s.fcells_host[j].z};
-    if (hipMalloc((void**)&s.fcells, sizeof(int2) * dev.size()) != hipSuccess) {
-      (void)hipGetLastError();
-      s.fcells = nullptr; s.fcells_host.clear(); c->nbodies = 0;
-      return fail(LBM_ENOMEM, "no room on device %d for %zu body cells", s.dev, dev.size());
-    }
-    HIPC(hipMemcpy(s.fcells, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
-    s.fcells_n = (int)dev.size();
-  }
-  c->nbodies = nbodies;
-  return LBM_OK;
-}
-
-extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* forces) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
-  if (c->nbodies == 0) return fail(LBM_EINVAL, "no bodies are set (lbm_set_bodies)");
-  if (nsteps > 0 && !forces) return fail(LBM_EINVAL, "forces is NULL");
-  c->forces_in_kernel = 0; c->forces_in_wave = 0;
-  if (nsteps == 0) return run_steps(c, 0, av_vels);
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
-  const int nb = c->nbodies;
-  const long nval = 2L * nb * nsteps;
-  if (nval + nsteps + 1 > (1L << 30)) return fail(LBM_EINVAL, "a forces run of %d steps is too long (split it)", nsteps);
-  // ---- everything that can fail for want of room is decided here, before anything is queued
-  int rc = LBM_OK;
-  for (auto& s : c->slabs)
-    if (ensure_sums(s, (int)(nsteps + 1 + nval))) { (void)hipGetLastError(); return fail(LBM_ENOMEM, "no room for the sums of %d steps and their forces", nsteps); }
-  bool in_kernel = regtile_is_next(c);
-  if (in_kernel) {
-    for (auto& s : c->slabs)
-      if ((rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps))) break;
-  }
-  if ((rc = ranks_agree(c, rc, &in_kernel, "the force partials"))) return rc;
-  RunKind k;
-  k.nb = nb; k.nval = nval; k.force_tiles = in_kernel;
-  if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-  // the local slabs' sums (a rank: everybody's, through the all-reduce that ended the run)
-  for (long k = 0; k < nval; ++k) {
-    double acc = 0.0;
-    for (auto& s : c->slabs) acc += s.sums_host[nsteps + 1 + k];
-    forces[k] = (float)acc;
-  }
-  return LBM_OK;
-}
-
-extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, float* mean_out) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
-  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
-  const int m = nsteps / every;
-  if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
-  if (!mean_out) return fail(LBM_EINVAL, "mean_out is NULL");
-  c->mean_in_kernel = 0; c->mean_in_wave = 0;
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
-  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
-  const int nx = c->p.nx;
-  const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
-  bool on_dev = false;
-  int rc;
-  if ((rc = output_on_device(c, mean_out, "mean_out", &on_dev))) return rc;
-  // one float4 per cell and slab: the sums of the split path, and the staging of host output on either path
-  const size_t ns = c->slabs.size();
-  std::vector<DeviceTemp> acc(ns);
-  for (size_t i = 0; i < ns && !rc; ++i) {
-    Slab& s = c->slabs[i];
-    HIPC(hipSetDevice(s.dev));
-    const size_t bytes = sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx;
-    if (hipMalloc(&acc[i].p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      acc[i].p = nullptr;
-      rc = fail(LBM_ENOMEM, "no room on device %d for the sums of slab %zu (%zu bytes)", s.dev, i, bytes);
-    }
-  }
-  bool in_kernel = regtile_is_next(c);
-  if ((rc = ranks_agree(c, rc, &in_kernel, "the sums"))) return rc;
-  auto out_of = [&](size_t i) { return on_dev ? mean_out + 4L * (c->slabs[i].row0 - base_row) * nx : (float*)acc[i].p; };
-  auto to_host = [&]() -> int {
-    if (on_dev) return LBM_OK;
-    for (size_t i = 0; i < ns; ++i) {
-      Slab& s = c->slabs[i];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemcpy(mean_out + 4L * (s.row0 - base_row) * nx, acc[i].p, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx, hipMemcpyDeviceToHost));
-    }
-    return LBM_OK;
-  };
-  if (in_kernel) {
-    // ---- in the kernel: the means straight into device output, or into the slab's buffer copied out after the run
-    SnapPlan sp;
-    sp.every = every;
-    for (size_t i = 0; i < ns; ++i) { sp.at.push_back(out_of(i)); sp.stride.push_back(0); }
-    RunKind k;
-    k.snap = &sp; k.mean = true;
-    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-    if (c->mean_in_kernel) return to_host();
-    // (the register tiles did not run, or gave up with the lattice untouched and nothing stored: the pieces below repeat the run)
-  }
-  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps that hold a sample step in
-  // lbm_wave's field flavour, which adds every delivered cell's fields to the slab's sums at the sample levels of a pass, in
-  // the order of the steps; lbm_mean_add behind the left-over steps that are sample steps.  The same adds in the same order
-  // as below.
-  if (nsteps >= c->time_block && wave_fields_admit(c)) {
-    Slab& s = c->slabs[0];
-    HIPC(hipSetDevice(s.dev));
-    const long ncell = (long)s.nyl * nx;
-    HIPC(hipMemsetAsync(acc[0].p, 0, sizeof(float) * 4 * (size_t)ncell, s.sc));
-    RunKind k;
-    k.no_tiles = true; k.wave_fout = (float*)acc[0].p; k.wave_fevery = every; k.wave_fstride = 0; k.wave_fadd = true;
-    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-    hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, (const float*)acc[0].p, ncell,
-                       (float)m, out_of(0));
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(s.sc));
-    return to_host();
-  }
-  // ---- the step loop split at the sample steps: each piece a complete run, then the fields of the stored lattice added to
-  // the slab's sums (no snapshot, no host round trip per sample); the same adds in the same order as in the register tiles.
-  // Correct, not fast.
-  for (size_t i = 0; i < ns; ++i) {
-    Slab& s = c->slabs[i];
-    HIPC(hipSetDevice(s.dev));
-    HIPC(hipMemsetAsync(acc[i].p, 0, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx, s.sc));
-  }
-  double gpu_ms = 0.0, wall_ms = 0.0;
-  int done = 0;
-  for (int j = 0; j <= m; ++j) {
-    const int n = (j < m) ? every : nsteps - done;
-    if (n == 0) break;
-    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
-    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
-    done += n;
-    if (j < m)
-      for (size_t i = 0; i < ns; ++i) {
-        Slab& s = c->slabs[i];
-        HIPC(hipSetDevice(s.dev));
-        const long ncell = (long)s.nyl * nx;
-        hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
-                           nx, ncell, s.blocked, c->p.density, (float*)acc[i].p);
-        HIPC(hipGetLastError());
-      }
-  }
-  for (size_t i = 0; i < ns; ++i) {
-    Slab& s = c->slabs[i];
-    HIPC(hipSetDevice(s.dev));
-    const long ncell = (long)s.nyl * nx;
-    hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, (const float*)acc[i].p, ncell,
-                       (float)m, out_of(i));
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(s.sc));
-  }
-  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
-  return to_host();
-}
-
-extern "C" int lbm_set_probes(lbm_ctx* c, const int* xy, int nprobes) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nprobes < 0 || nprobes > LBM_MAX_PROBES) return fail(LBM_EINVAL, "nprobes must be in [0, %d] (got %d)", LBM_MAX_PROBES, nprobes);
-  if (nprobes > 0 && !xy) return fail(LBM_EINVAL, "xy is NULL");
-  const int nx = c->p.nx, ny = c->p.ny;
-  // ---- the whole set is checked, and the slabs' new lists are on their devices, before anything of the earlier set goes
-  std::vector<std::pair<long, int>> seen((size_t)nprobes);
-  for (int i = 0; i < nprobes; ++i) {
-    const int x = xy[2 * i], y = xy[2 * i + 1];
-    if (x < 0 || x >= nx || y < 0 || y >= ny)
-      return fail(LBM_EINVAL, "xy[%d] = (%d, %d) is outside the %d x %d lattice", i, x, y, nx, ny);
-    seen[i] = {(long)y * nx + x, i};
-  }
-  std::sort(seen.begin(), seen.end());
-  for (int i = 1; i < nprobes; ++i)
-    if (seen[i].first == seen[i - 1].first)
-      return fail(LBM_EINVAL, "xy[%d] and xy[%d] are the same cell (%d, %d)", seen[i - 1].second, seen[i].second,
-                  (int)(seen[i].first % nx), (int)(seen[i].first / nx));
-  const size_t ns = c->slabs.size();
-  std::vector<std::vector<int4>> lists(ns);
-  std::vector<DeviceTemp> fresh(ns);
-  for (size_t k = 0; k < ns; ++k) {
-    Slab& s = c->slabs[k];
-    for (int i = 0; i < nprobes; ++i) {
-      const int y = xy[2 * i + 1] - s.row0;
-      if (y >= 0 && y < s.nyl) lists[k].push_back(int4{xy[2 * i], y, i, 0});
-    }
-    if (lists[k].empty()) continue;
-    std::vector<int2> dev(lists[k].size());
-    for (size_t j = 0; j < dev.size(); ++j) dev[j] = int2{lists[k][j].y * s.pitch + lists[k][j].x, lists[k][j].z};
-    HIPC(hipSetDevice(s.dev));
-    if (hipMalloc(&fresh[k].p, sizeof(int2) * dev.size()) != hipSuccess) {
-      (void)hipGetLastError();
-      fresh[k].p = nullptr;
-      return fail(LBM_ENOMEM, "no room on device %d for %zu probe cells", s.dev, dev.size());
-    }
-    HIPC(hipMemcpy(fresh[k].p, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
-  }
-  for (size_t k = 0; k < ns; ++k) {
-    Slab& s = c->slabs[k];
-    HIPC(hipSetDevice(s.dev));
-    if (s.pcells) HIPC(hipFree(s.pcells));
-    s.pcells = (int2*)fresh[k].p; fresh[k].p = nullptr;
-    s.pcells_host.swap(lists[k]);
-    s.pty = 0;                      // (the register tiles' tables: rebuilt by the next lbm_run_probes)
-    wave_probe_free(s, true);       // (lbm_wave's probe maps likewise)
-  }
-  c->nprobes = nprobes;
-  return LBM_OK;
-}
-
-extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every, float* probes_out) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (c->nprobes == 0) return fail(LBM_EINVAL, "no probes are set (lbm_set_probes)");
-  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
-  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
-  const int m = nsteps / every;
-  if (m == 0) return fail(LBM_EINVAL, "nothing to record: no sample step in nsteps = %d step(s) at every = %d", nsteps, every);
-  if (!probes_out) return fail(LBM_EINVAL, "probes_out is NULL");
-  c->probes_in_kernel = 0; c->probes_in_wave = 0;
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
-  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
-  const int np = c->nprobes;
-  const size_t ns = c->slabs.size();
-  const size_t nfloat = 4 * (size_t)m * (size_t)np;
-  bool on_dev = false;
-  int rc;
-  if ((rc = output_on_device(c, probes_out, "probes_out", &on_dev))) return rc;
-  bool in_kernel = regtile_is_next(c);
-  // host output: one staging buffer [m][nprobes][4] per slab that holds a probe (a slab stores into its probes' places only)
-  std::vector<DeviceTemp> stage(ns);
-  size_t local = 0;
-  for (size_t i = 0; i < ns && !rc; ++i) {
-    Slab& s = c->slabs[i];
-    local += s.pcells_host.size();
-    if (!on_dev && !s.pcells_host.empty()) {
-      HIPC(hipSetDevice(s.dev));
-      if (hipMalloc(&stage[i].p, sizeof(float) * nfloat) != hipSuccess) {
-        (void)hipGetLastError();
-        stage[i].p = nullptr;
-        rc = fail(LBM_ENOMEM, "no room on device %d for %d sample(s) of %d probe(s) of slab %zu (%zu bytes)", s.dev, m, np, i, sizeof(float) * nfloat);
-      }
-    }
-    if (!rc && in_kernel) rc = probe_tables(c, s, c->tplan.ty, c->tplan.ntx);
-  }
-  if ((rc = ranks_agree(c, rc, &in_kernel, "the probes"))) return rc;
-  // the probes of other ranks' rows read +0.0f
-  if (local < (size_t)np) {
-    if (on_dev) {
-      Slab& s = c->slabs[0];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(probes_out, 0, sizeof(float) * nfloat, s.sc));
-      HIPC(hipStreamSynchronize(s.sc));
-    } else memset(probes_out, 0, sizeof(float) * nfloat);
-  }
-  auto out_of = [&](size_t i) { return on_dev ? probes_out : (float*)stage[i].p; };
-  auto to_host = [&]() -> int {
-    if (on_dev) return LBM_OK;
-    std::vector<float> tmp;
-    for (size_t i = 0; i < ns; ++i) {
-      Slab& s = c->slabs[i];
-      if (s.pcells_host.empty()) continue;
-      HIPC(hipSetDevice(s.dev));
-      if (s.pcells_host.size() == (size_t)np) {          // (every probe is this slab's)
-        HIPC(hipMemcpy(probes_out, stage[i].p, sizeof(float) * nfloat, hipMemcpyDeviceToHost));
-        continue;
-      }
-      tmp.resize(nfloat);
-      HIPC(hipMemcpy(tmp.data(), stage[i].p, sizeof(float) * nfloat, hipMemcpyDeviceToHost));
-      for (int j = 0; j < m; ++j)
-        for (const int4& q : s.pcells_host) {
-          const size_t o = 4 * ((size_t)j * np + (size_t)q.z);
-          memcpy(probes_out + o, tmp.data() + o, 4 * sizeof(float));
-        }
-    }
-    return LBM_OK;
-  };
-  if (in_kernel) {
-    // ---- in the kernel: every slab's tiles store their probes straight into their places of device output / of the slab's staging
-    SnapPlan sp;
-    sp.every = every;
-    for (size_t i = 0; i < ns; ++i) { sp.at.push_back(out_of(i)); sp.stride.push_back(4L * np); }
-    RunKind k;
-    k.snap = &sp; k.probe = true;
-    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-    if (c->probes_in_kernel) return to_host();
-    // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run and store every value again)
-  }
-  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps in lbm_wave's probe flavour, which
-  // stores the probes of every sample step of a pass; lbm_probe_gather behind the left-over steps that are sample steps.
-  // Decided here, before anything is queued; maps or partials that do not fit: the pieces below, the same bits.
-  if (nsteps >= c->time_block && wave_probes_admit(c, false)) {
-    RunKind k;
-    k.no_tiles = true; k.wave_pout = out_of(0); k.wave_pevery = every; k.pfirst = every;
-    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
-    return to_host();
-  }
-  // ---- the step loop split at the sample steps: each piece a complete run, then the probes' cells of the stored lattice
-  // gathered into row j.  Correct, not fast.
-  double gpu_ms = 0.0, wall_ms = 0.0;
-  int done = 0;
-  for (int j = 0; j <= m; ++j) {
-    const int n = (j < m) ? every : nsteps - done;
-    if (n == 0) break;
-    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
-    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
-    done += n;
-    if (j < m)
-      for (size_t i = 0; i < ns; ++i) {
-        Slab& s = c->slabs[i];
-        const int n_here = (int)s.pcells_host.size();
-        if (n_here == 0) continue;
-        HIPC(hipSetDevice(s.dev));
-        hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane,
-                           s.pcells, n_here, s.blocked, c->p.density, out_of(i) + 4 * (size_t)j * (size_t)np);
-        HIPC(hipGetLastError());
-      }
-  }
-  for (auto& s : c->slabs) {
-    HIPC(hipSetDevice(s.dev));
-    HIPC(hipStreamSynchronize(s.sc));
-  }
-  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
-  return to_host();
-}
-
 extern "C" int lbm_last_run_ms(const lbm_ctx* c, double* gpu_ms, double* wall_ms) {
   if (!c) return fail(LBM_EINVAL, "ctx is NULL");
   if (gpu_ms) *gpu_ms = c->gpu_ms;
@@ -1480,8 +989,6 @@ static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, 
   if (mass) *mass = tot[1];
   return LBM_OK;
 }
-
-#include "lbm_host_observe.inc"
 
 extern "C" int lbm_av_velocity(lbm_ctx* c, float* out) {
   if (!c || !out) return fail(LBM_EINVAL, "NULL argument");

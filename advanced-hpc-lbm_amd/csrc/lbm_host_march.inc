@@ -677,7 +677,7 @@ struct WaveFields {
 // One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li.  nb > 0 (lbm_run_forces, wave_force_ready
 // said yes): the force flavour, and behind it the fold of the group's forces into the run's sums (of nsteps steps).
 // wp.out (wave_probe_ready said yes): the probe flavour, or the force-and-probe flavour; a group without a sample step
-// runs what it would run without probes.  wf.out (wave_fields_admit said yes; no forces, no probes beside it): the field
+// runs what it would run without probes.  wf.out (wave_admit said yes; no forces, no probes beside it): the field
 // flavour for a group that holds a sample step, the plain kernel for one that holds none.
 int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0, WaveProbes wp = WaveProbes(),
                 WaveFields wf = WaveFields()) {

@@ -1,5 +1,15 @@
-// lbm_host_observe.inc -- part of lbm_api.hip (included there): lbm_run_observed, one run with any subset of the four
-// observers (forces, probes, means, snapshots).  DESIGN.md 3.11.
+// lbm_host_observe.inc -- part of lbm_api.hip (included there, in front of run_steps): the observer calls -- lbm_run_sampled,
+// lbm_run_forces, lbm_run_mean, lbm_run_probes with lbm_set_bodies / lbm_set_probes, and lbm_run_observed -- and the one
+// copy of what they share:
+//   output_on_device, ranks_agree          where an output lies; a rank context's ranks take the same path and fail together
+//   launch_probe_gather / _mean_add / _mean_div   the one launch site of each small kernel (run_steps' pgather uses them too)
+//   fetch_forces                           a run's forces from behind its per-step sums
+//   ProbeOut, MeanOut                      where one call's probe values / means go: device output in place, host output
+//                                          through per-slab staging (snapshots keep derive_all and their two staging shapes)
+//   run_split                              the step loop cut at the sample steps, plain run_steps pieces (the single calls)
+// Each call keeps its own refusals, the order in which it decides things before anything is queued, and its choice of path.
+//
+// lbm_run_observed, one run with any subset of the four observers (forces, probes, means, snapshots).  DESIGN.md 3.11.
 //
 // One observer alone IS its own call.  Two or more: the step loop is cut into pieces at the sample steps of the observers that
 // are not taken inside a launch -- means and snapshots always; probes where the register tiles do not run -- and each piece is
@@ -17,15 +27,240 @@
 // A register-tile piece that gives up (or whose flavour is not resident) has stepped nothing: run_steps says so (RunKind::ran),
 // and the loop repeats THAT piece from the same `done` off the tiles (RunKind::no_tiles, for the rest of the call) -- cut at
 // the probes' sample steps, every row of the piece gathered again, the forces of its steps stored again.
+
+// Output of lbm_run_sampled / lbm_run_mean (`what`: the argument's name): host memory, or device memory -- then of the device
+// that holds every slab, written in place.
+static int output_on_device(const lbm_ctx* c, const void* out, const char* what, bool* on_dev) {
+  *on_dev = false;
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeDevice) {
+    *on_dev = true;
+    for (auto& s : c->slabs)
+      if (s.dev != attr.device)
+        return fail(LBM_EINVAL, "%s is memory of device %d: device output needs every slab on that device (slab on %d)", what, attr.device, s.dev);
+  }
+  (void)hipGetLastError();      // (host memory unknown to HIP: an error the runtime remembers)
+  return LBM_OK;
+}
+
+// Before lbm_run_forces / lbm_run_mean queue anything: a rank context's ranks take the same path and fail together.  rc: this
+// rank's allocation result (`what` it was for); *in_kernel: would this rank use the register tiles -- on return, would every rank.
+// Returns what the call must return now, or LBM_OK.
+static int ranks_agree(lbm_ctx* c, int rc, bool* in_kernel, const char* what) {
+  if (!(c->rank_mode && c->slabs[0].comm != nullptr)) return rc;
+  // [0] ranks short of room, [1] ranks that would not use the tiles
+  Slab& s = c->slabs[0];
+  double v[2] = {rc ? 1.0 : 0.0, *in_kernel ? 0.0 : 1.0};
+  HIPC(hipSetDevice(s.dev));
+  HIPC(hipMemcpy(s.scratch_d, v, sizeof(v), hipMemcpyHostToDevice));
+  NCCLC(rccl::AllReduce(s.scratch_d, s.scratch_d, 2, rccl::kFloat64, rccl::kSum, s.comm, s.sc));
+  HIPC(hipStreamSynchronize(s.sc));
+  HIPC(hipMemcpy(v, s.scratch_d, sizeof(v), hipMemcpyDeviceToHost));
+  if (v[0] > 0.0) return rc ? rc : fail(LBM_ENOMEM, "another rank has no room for %s", what);
+  *in_kernel = *in_kernel && v[1] == 0.0;
+  return LBM_OK;
+}
+
 namespace {
 
-// a piece's forces: the local slabs' sums behind its per-step sums (a rank: everybody's, through the all-reduce that ended it)
-void observed_forces(const lbm_ctx* c, int n, long nval, float* out) {
+// ---- the small kernels behind a stored lattice, each launched from here alone (on the slab's stream)
+
+// the slab's probes' cells of the stored lattice into their places of out_row, one sample's row of 4 x nprobes floats
+int launch_probe_gather(const lbm_ctx* c, Slab& s, float* out_row) {
+  const int n_here = (int)s.pcells_host.size();
+  HIPC(hipSetDevice(s.dev));
+  hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane,
+                     s.pcells, n_here, s.blocked, c->p.density, out_row);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// the fields of the slab's stored lattice added to its sums, one float4 per cell
+int launch_mean_add(const lbm_ctx* c, Slab& s, float* acc) {
+  const int nx = c->p.nx;
+  const long ncell = (long)s.nyl * nx;
+  HIPC(hipSetDevice(s.dev));
+  hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
+                     nx, ncell, s.blocked, c->p.density, acc);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// the slab's sums of m samples divided into out (which may be the sums themselves)
+int launch_mean_div(const lbm_ctx* c, Slab& s, const float* acc, int m, float* out) {
+  const long ncell = (long)s.nyl * c->p.nx;
+  HIPC(hipSetDevice(s.dev));
+  hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, acc, ncell, (float)m, out);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// a run's forces: the local slabs' sums behind its n per-step sums (a rank: everybody's, through the all-reduce that ended it)
+void fetch_forces(const lbm_ctx* c, int n, long nval, float* out) {
   for (long k = 0; k < nval; ++k) {
     double acc = 0.0;
     for (auto& s : c->slabs) acc += s.sums_host[n + 1 + k];
     out[k] = (float)acc;
   }
+}
+
+// Where one call's probe values go, [m][nprobes][4] floats.  Device output is written in place; host output goes through one
+// staging buffer of that shape per slab that holds a probe (a slab stores into its probes' places only), copied out by to_host.
+struct ProbeOut {
+  lbm_ctx* c;
+  float* out = nullptr;
+  bool on_dev = false;
+  int m = 0, np = 0;
+  size_t nfloat = 0, local = 0;            // floats of the output; probes that the slabs of this context hold
+  std::vector<DeviceTemp> stage;
+
+  explicit ProbeOut(lbm_ctx* ctx) : c(ctx) {}
+  int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
+  // the staging of m_ samples (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
+  int prepare(int m_) {
+    m = m_; np = c->nprobes; nfloat = 4 * (size_t)m * (size_t)np;
+    stage.resize(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      local += s.pcells_host.size();
+      if (on_dev || s.pcells_host.empty()) continue;
+      HIPC(hipSetDevice(s.dev));
+      if (hipMalloc(&stage[i].p, sizeof(float) * nfloat) != hipSuccess) {
+        (void)hipGetLastError();
+        stage[i].p = nullptr;
+        return fail(LBM_ENOMEM, "no room on device %d for %d sample(s) of %d probe(s) of slab %zu (%zu bytes)", s.dev, m, np, i, sizeof(float) * nfloat);
+      }
+    }
+    return LBM_OK;
+  }
+  // the probes of other ranks' rows read +0.0f
+  int zero_foreign() {
+    if (local >= (size_t)np) return LBM_OK;
+    if (on_dev) {
+      Slab& s = c->slabs[0];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemsetAsync(out, 0, sizeof(float) * nfloat, s.sc));
+      HIPC(hipStreamSynchronize(s.sc));
+    } else memset(out, 0, sizeof(float) * nfloat);
+    return LBM_OK;
+  }
+  // row `row` of what slab i stores into (a slab without a probe stores nothing: NULL)
+  float* at(size_t i, int row) const {
+    float* base = on_dev ? out : (float*)stage[i].p;
+    return base ? base + 4 * (size_t)row * (size_t)np : nullptr;
+  }
+  // the probes' cells of the stored lattice into row `row`, on every slab that holds a probe
+  int gather(int row) {
+    int rc;
+    for (size_t i = 0; i < c->slabs.size(); ++i)
+      if (!c->slabs[i].pcells_host.empty() && (rc = launch_probe_gather(c, c->slabs[i], at(i, row)))) return rc;
+    return LBM_OK;
+  }
+  // what was staged, into the caller's array (the slabs' streams have been waited for)
+  int to_host() {
+    if (on_dev) return LBM_OK;
+    std::vector<float> tmp;
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (s.pcells_host.empty()) continue;
+      HIPC(hipSetDevice(s.dev));
+      if (s.pcells_host.size() == (size_t)np) {          // (every probe is this slab's)
+        HIPC(hipMemcpy(out, stage[i].p, sizeof(float) * nfloat, hipMemcpyDeviceToHost));
+        continue;
+      }
+      tmp.resize(nfloat);
+      HIPC(hipMemcpy(tmp.data(), stage[i].p, sizeof(float) * nfloat, hipMemcpyDeviceToHost));
+      for (int j = 0; j < m; ++j)
+        for (const int4& q : s.pcells_host) {
+          const size_t o = 4 * ((size_t)j * np + (size_t)q.z);
+          memcpy(out + o, tmp.data() + o, 4 * sizeof(float));
+        }
+    }
+    return LBM_OK;
+  }
+};
+
+// Where one call's means go, [rows][nx][4] floats: one float4 per cell and slab -- the sums of every path but the register
+// tiles', and the staging of host output on every path.  Device output is written in place.
+struct MeanOut {
+  lbm_ctx* c;
+  float* out = nullptr;
+  bool on_dev = false;
+  std::vector<DeviceTemp> acc;
+
+  explicit MeanOut(lbm_ctx* ctx) : c(ctx) {}
+  int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
+  size_t bytes(const Slab& s) const { return sizeof(float) * 4 * (size_t)s.nyl * (size_t)c->p.nx; }
+  float* host_rows(const Slab& s) const { return out + 4L * (s.row0 - (c->rank_mode ? c->slabs[0].row0 : 0)) * c->p.nx; }
+  // the slabs' buffers (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
+  int prepare() {
+    acc.resize(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      HIPC(hipSetDevice(s.dev));
+      if (hipMalloc(&acc[i].p, bytes(s)) != hipSuccess) {
+        (void)hipGetLastError();
+        acc[i].p = nullptr;
+        return fail(LBM_ENOMEM, "no room on device %d for the sums of slab %zu (%zu bytes)", s.dev, i, bytes(s));
+      }
+    }
+    return LBM_OK;
+  }
+  int clear() {
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemsetAsync(acc[i].p, 0, bytes(s), s.sc));
+    }
+    return LBM_OK;
+  }
+  float* sums(size_t i) const { return (float*)acc[i].p; }
+  // where slab i's means go
+  float* at(size_t i) const { return on_dev ? host_rows(c->slabs[i]) : sums(i); }
+  // the fields of the stored lattice added to the sums, on every slab
+  int add() {
+    int rc;
+    for (size_t i = 0; i < c->slabs.size(); ++i)
+      if ((rc = launch_mean_add(c, c->slabs[i], sums(i)))) return rc;
+    return LBM_OK;
+  }
+  int to_host() {
+    if (on_dev) return LBM_OK;
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemcpy(host_rows(s), acc[i].p, bytes(s), hipMemcpyDeviceToHost));
+    }
+    return LBM_OK;
+  }
+  // the sums of m samples divided into their place, every slab's stream waited for, host output copied out
+  int finish(int m) {
+    int rc;
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if ((rc = launch_mean_div(c, s, sums(i), m, at(i)))) return rc;
+      HIPC(hipStreamSynchronize(s.sc));
+    }
+    return to_host();
+  }
+};
+
+// The step loop split at the sample steps every, 2 every, ... m every: each piece a complete plain run_steps (the register
+// tiles may run it), after_sample(j) behind piece j < m on the stored lattice, then the tail.  Correct, not fast.
+template <class F>
+int run_split(lbm_ctx* c, int nsteps, float* av_vels, int every, int m, F after_sample) {
+  double gpu_ms = 0.0, wall_ms = 0.0;
+  int done = 0, rc;
+  for (int j = 0; j <= m; ++j) {
+    const int n = (j < m) ? every : nsteps - done;
+    if (n == 0) break;
+    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
+    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
+    done += n;
+    if (j < m && (rc = after_sample(j))) return rc;
+  }
+  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  return LBM_OK;
 }
 
 // the table of -1s of a slab for the current tiling (LBM_ENOMEM: nothing queued)
@@ -45,6 +280,310 @@ int observed_no_force_table(Slab& s, int ntiles) {
 }
 
 }  // namespace
+
+extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every, float* fields_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every < 0) return fail(LBM_EINVAL, "every < 0");
+  const int m = every > 0 ? nsteps / every : 0;
+  if (m > 0 && !fields_out) return fail(LBM_EINVAL, "fields_out is NULL but %d snapshot(s) are due", m);
+  c->samples_in_kernel = 0; c->samples_in_wave = 0;
+  if (m == 0) return run_steps(c, nsteps, av_vels);
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  const int nx = c->p.nx;
+  const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
+  long rows = 0;
+  for (auto& s : c->slabs) rows += s.nyl;
+  const long slot = rows * nx * 4;                          // floats per snapshot
+  if ((unsigned long long)m > (unsigned long long)(PTRDIFF_MAX / 4) / (unsigned long long)slot)
+    return fail(LBM_EINVAL, "%d snapshots of %ld floats do not fit the address space", m, slot);
+  bool on_dev = false;
+  int rc;
+  if ((rc = output_on_device(c, fields_out, "fields_out", &on_dev))) return rc;
+  if (regtile_is_next(c)) {
+    // ---- in the kernel: straight into device output, or into one staging buffer per slab copied out after the run
+    SnapPlan sp;
+    sp.every = every;
+    std::vector<DeviceTemp> stage(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (on_dev) { sp.at.push_back(fields_out + 4L * (s.row0 - base_row) * nx); sp.stride.push_back(slot); continue; }
+      HIPC(hipSetDevice(s.dev));
+      const size_t bytes = sizeof(float) * 4 * (size_t)m * (size_t)s.nyl * (size_t)nx;
+      if (hipMalloc(&stage[i].p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        stage[i].p = nullptr;
+        return fail(LBM_ENOMEM, "no room on device %d for %d snapshot(s) of slab %zu (%zu bytes)", s.dev, m, i, bytes);
+      }
+      sp.at.push_back((float*)stage[i].p); sp.stride.push_back((long)s.nyl * nx * 4);
+    }
+    RunKind k;
+    k.snap = &sp;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->samples_in_kernel) {
+      if (!on_dev)
+        for (size_t i = 0; i < c->slabs.size(); ++i) {
+          Slab& s = c->slabs[i];
+          HIPC(hipSetDevice(s.dev));
+          const size_t w = sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx;
+          HIPC(hipMemcpy2D(fields_out + 4L * (s.row0 - base_row) * nx, sizeof(float) * (size_t)slot, stage[i].p, w, w, (size_t)m,
+                           hipMemcpyDeviceToHost));
+        }
+      return LBM_OK;
+    }
+    // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run)
+  }
+  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps that hold a sample step in
+  // lbm_wave's field flavour, which stores every delivered cell's fields at the sample levels of a pass; lbm_derive behind
+  // the left-over steps that are sample steps.  Device output is written in place, host output goes through one staging of
+  // the m snapshots.  Decided here, before anything is queued; a staging that does not fit: the pieces below, the same bits.
+  if (nsteps >= c->time_block && wave_admit(c)) {
+    Slab& s = c->slabs[0];
+    HIPC(hipSetDevice(s.dev));
+    DeviceTemp stage, part;
+    bool room = true;
+    if (!on_dev && hipMalloc(&stage.p, sizeof(float) * (size_t)m * (size_t)slot) != hipSuccess) { stage.p = nullptr; room = false; }
+    // (lbm_derive leaves a float and a double per block, unused here; the partial-sum buffers are busy during a run)
+    const size_t nblk = (size_t)cdiv((long)s.nyl * nx, lbm::kBlock);
+    if (room && hipMalloc(&part.p, (sizeof(double) + sizeof(float)) * nblk) != hipSuccess) { part.p = nullptr; room = false; }
+    if (!room) (void)hipGetLastError();
+    else {
+      RunKind k;
+      k.no_tiles = true; k.wave_fout = on_dev ? fields_out : (float*)stage.p; k.wave_fevery = every; k.wave_fstride = slot;
+      k.wave_fmass = (double*)part.p; k.wave_fpart = (float*)(k.wave_fmass + nblk);
+      if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+      if (!on_dev) HIPC(hipMemcpy(fields_out, stage.p, sizeof(float) * (size_t)m * (size_t)slot, hipMemcpyDeviceToHost));
+      return LBM_OK;
+    }
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then lbm_final_state's derive into its slot
+  return run_split(c, nsteps, av_vels, every, m,
+                   [&](int j) { return derive_all(c, fields_out + (size_t)j * (size_t)slot, nullptr, nullptr, on_dev); });
+}
+
+extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nbodies < 0 || nbodies > LBM_MAX_BODIES) return fail(LBM_EINVAL, "nbodies must be in [0, %d] (got %d)", LBM_MAX_BODIES, nbodies);
+  if (nbodies > 0 && !body) return fail(LBM_EINVAL, "body is NULL");
+  const int nx = c->p.nx, ny = c->p.ny;
+  // c_i of directions 1..8 (E N W S NE NW SW SE)
+  static const int cx[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1}, cy[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
+  std::vector<std::vector<int4>> lists(c->slabs.size());
+  for (size_t k = 0; k < c->slabs.size() && nbodies > 0; ++k) {
+    const Slab& s = c->slabs[k];
+    for (int y = 0; y < s.nyl; ++y) {
+      const int gy = s.row0 + y, ky = gy - c->keep_row0;       // (row of obst_keep)
+      for (int x = 0; x < nx; ++x) {
+        if (!c->obst_keep[(size_t)ky * nx + x]) continue;       // (labels on fluid cells are ignored)
+        const int lab = body[(long)gy * nx + x];
+        if (lab < 0 || lab > nbodies) return fail(LBM_EINVAL, "label %d of blocked cell (%d, %d) is outside [0, %d]", lab, x, gy, nbodies);
+        if (lab == 0) continue;
+        unsigned m = 0u;
+        for (int i = 1; i <= 8; ++i) {
+          const int sx = ((x - cx[i]) % nx + nx) % nx, sy = ky - cy[i];   // the source cell B - c_i (wraps in x; rows: kept)
+          if (!c->obst_keep[(size_t)sy * nx + sx]) m |= 1u << (i - 1);
+        }
+        if (m) lists[k].push_back(int4{x, y, (int)(m | ((unsigned)lab << 8)), 0});
+      }
+    }
+  }
+  (void)ny;
+  for (size_t k = 0; k < c->slabs.size(); ++k) {
+    Slab& s = c->slabs[k];
+    HIPC(hipSetDevice(s.dev));
+    if (s.fcells) HIPC(hipFree(s.fcells));
+    s.fcells = nullptr; s.fcells_n = 0; s.fty = 0;
+    wave_force_free(s);                 // (lbm_wave's force maps follow the list: rebuilt by the next forces run that wants them)
+    wave_probe_free(s, false);          // (... and so does the force-and-probe map)
+    s.fcells_host.swap(lists[k]);
+    if (s.fcells_host.empty()) continue;
+    std::vector<int2> dev(s.fcells_host.size());
+    for (size_t j = 0; j < dev.size(); ++j)
+      dev[j] = int2{s.fcells_host[j].y * s.pitch + s.fcells_host[j].x, s.fcells_host[j].z};
+    if (hipMalloc((void**)&s.fcells, sizeof(int2) * dev.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      s.fcells = nullptr; s.fcells_host.clear(); c->nbodies = 0;
+      return fail(LBM_ENOMEM, "no room on device %d for %zu body cells", s.dev, dev.size());
+    }
+    HIPC(hipMemcpy(s.fcells, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
+    s.fcells_n = (int)dev.size();
+  }
+  c->nbodies = nbodies;
+  return LBM_OK;
+}
+
+extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* forces) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (c->nbodies == 0) return fail(LBM_EINVAL, "no bodies are set (lbm_set_bodies)");
+  if (nsteps > 0 && !forces) return fail(LBM_EINVAL, "forces is NULL");
+  c->forces_in_kernel = 0; c->forces_in_wave = 0;
+  if (nsteps == 0) return run_steps(c, 0, av_vels);
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  const int nb = c->nbodies;
+  const long nval = 2L * nb * nsteps;
+  if (nval + nsteps + 1 > (1L << 30)) return fail(LBM_EINVAL, "a forces run of %d steps is too long (split it)", nsteps);
+  // ---- everything that can fail for want of room is decided here, before anything is queued
+  int rc = LBM_OK;
+  for (auto& s : c->slabs)
+    if (ensure_sums(s, (int)(nsteps + 1 + nval))) { (void)hipGetLastError(); return fail(LBM_ENOMEM, "no room for the sums of %d steps and their forces", nsteps); }
+  bool in_kernel = regtile_is_next(c);
+  if (in_kernel) {
+    for (auto& s : c->slabs)
+      if ((rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps))) break;
+  }
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the force partials"))) return rc;
+  RunKind k;
+  k.nb = nb; k.nval = nval; k.force_tiles = in_kernel;
+  if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+  fetch_forces(c, nsteps, nval, forces);
+  return LBM_OK;
+}
+
+extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, float* mean_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
+  const int m = nsteps / every;
+  if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
+  if (!mean_out) return fail(LBM_EINVAL, "mean_out is NULL");
+  c->mean_in_kernel = 0; c->mean_in_wave = 0;
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  MeanOut mo(c);
+  int rc;
+  if ((rc = mo.locate(mean_out, "mean_out"))) return rc;
+  rc = mo.prepare();
+  bool in_kernel = regtile_is_next(c);
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the sums"))) return rc;
+  if (in_kernel) {
+    // ---- in the kernel: the means straight into device output, or into the slab's buffer copied out after the run
+    SnapPlan sp;
+    sp.every = every;
+    for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(mo.at(i)); sp.stride.push_back(0); }
+    RunKind k;
+    k.snap = &sp; k.mean = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->mean_in_kernel) return mo.to_host();
+    // (the register tiles did not run, or gave up with the lattice untouched and nothing stored: the pieces below repeat the run)
+  }
+  if ((rc = mo.clear())) return rc;
+  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps that hold a sample step in
+  // lbm_wave's field flavour, which adds every delivered cell's fields to the slab's sums at the sample levels of a pass, in
+  // the order of the steps; lbm_mean_add behind the left-over steps that are sample steps.  The same adds in the same order
+  // as below.
+  if (nsteps >= c->time_block && wave_admit(c)) {
+    RunKind k;
+    k.no_tiles = true; k.wave_fout = mo.sums(0); k.wave_fevery = every; k.wave_fstride = 0; k.wave_fadd = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    return mo.finish(m);
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then the fields of the stored lattice added to
+  // the slab's sums (no snapshot, no host round trip per sample); the same adds in the same order as in the register tiles.
+  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int) { return mo.add(); }))) return rc;
+  return mo.finish(m);
+}
+
+extern "C" int lbm_set_probes(lbm_ctx* c, const int* xy, int nprobes) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nprobes < 0 || nprobes > LBM_MAX_PROBES) return fail(LBM_EINVAL, "nprobes must be in [0, %d] (got %d)", LBM_MAX_PROBES, nprobes);
+  if (nprobes > 0 && !xy) return fail(LBM_EINVAL, "xy is NULL");
+  const int nx = c->p.nx, ny = c->p.ny;
+  // ---- the whole set is checked, and the slabs' new lists are on their devices, before anything of the earlier set goes
+  std::vector<std::pair<long, int>> seen((size_t)nprobes);
+  for (int i = 0; i < nprobes; ++i) {
+    const int x = xy[2 * i], y = xy[2 * i + 1];
+    if (x < 0 || x >= nx || y < 0 || y >= ny)
+      return fail(LBM_EINVAL, "xy[%d] = (%d, %d) is outside the %d x %d lattice", i, x, y, nx, ny);
+    seen[i] = {(long)y * nx + x, i};
+  }
+  std::sort(seen.begin(), seen.end());
+  for (int i = 1; i < nprobes; ++i)
+    if (seen[i].first == seen[i - 1].first)
+      return fail(LBM_EINVAL, "xy[%d] and xy[%d] are the same cell (%d, %d)", seen[i - 1].second, seen[i].second,
+                  (int)(seen[i].first % nx), (int)(seen[i].first / nx));
+  const size_t ns = c->slabs.size();
+  std::vector<std::vector<int4>> lists(ns);
+  std::vector<DeviceTemp> fresh(ns);
+  for (size_t k = 0; k < ns; ++k) {
+    Slab& s = c->slabs[k];
+    for (int i = 0; i < nprobes; ++i) {
+      const int y = xy[2 * i + 1] - s.row0;
+      if (y >= 0 && y < s.nyl) lists[k].push_back(int4{xy[2 * i], y, i, 0});
+    }
+    if (lists[k].empty()) continue;
+    std::vector<int2> dev(lists[k].size());
+    for (size_t j = 0; j < dev.size(); ++j) dev[j] = int2{lists[k][j].y * s.pitch + lists[k][j].x, lists[k][j].z};
+    HIPC(hipSetDevice(s.dev));
+    if (hipMalloc(&fresh[k].p, sizeof(int2) * dev.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      fresh[k].p = nullptr;
+      return fail(LBM_ENOMEM, "no room on device %d for %zu probe cells", s.dev, dev.size());
+    }
+    HIPC(hipMemcpy(fresh[k].p, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
+  }
+  for (size_t k = 0; k < ns; ++k) {
+    Slab& s = c->slabs[k];
+    HIPC(hipSetDevice(s.dev));
+    if (s.pcells) HIPC(hipFree(s.pcells));
+    s.pcells = (int2*)fresh[k].p; fresh[k].p = nullptr;
+    s.pcells_host.swap(lists[k]);
+    s.pty = 0;                      // (the register tiles' tables: rebuilt by the next lbm_run_probes)
+    wave_probe_free(s, true);       // (lbm_wave's probe maps likewise)
+  }
+  c->nprobes = nprobes;
+  return LBM_OK;
+}
+
+extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every, float* probes_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (c->nprobes == 0) return fail(LBM_EINVAL, "no probes are set (lbm_set_probes)");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
+  const int m = nsteps / every;
+  if (m == 0) return fail(LBM_EINVAL, "nothing to record: no sample step in nsteps = %d step(s) at every = %d", nsteps, every);
+  if (!probes_out) return fail(LBM_EINVAL, "probes_out is NULL");
+  c->probes_in_kernel = 0; c->probes_in_wave = 0;
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  ProbeOut po(c);
+  int rc;
+  if ((rc = po.locate(probes_out, "probes_out"))) return rc;
+  bool in_kernel = regtile_is_next(c);
+  rc = po.prepare(m);
+  for (size_t i = 0; i < c->slabs.size() && !rc && in_kernel; ++i) rc = probe_tables(c, c->slabs[i], c->tplan.ty, c->tplan.ntx);
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the probes"))) return rc;
+  if ((rc = po.zero_foreign())) return rc;
+  if (in_kernel) {
+    // ---- in the kernel: every slab's tiles store their probes straight into their places of device output / of the slab's staging
+    SnapPlan sp;
+    sp.every = every;
+    for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(po.at(i, 0)); sp.stride.push_back(4L * po.np); }
+    RunKind k;
+    k.snap = &sp; k.probe = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->probes_in_kernel) return po.to_host();
+    // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run and store every value again)
+  }
+  // ---- where lbm_run would run lbm_wave (a lattice alone): ONE run, the groups of K steps in lbm_wave's probe flavour, which
+  // stores the probes of every sample step of a pass; lbm_probe_gather behind the left-over steps that are sample steps.
+  // Decided here, before anything is queued; maps or partials that do not fit: the pieces below, the same bits.
+  if (nsteps >= c->time_block && wave_probes_admit(c, false)) {
+    RunKind k;
+    k.no_tiles = true; k.wave_pout = po.at(0, 0); k.wave_pevery = every; k.pfirst = every;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    return po.to_host();
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then the probes' cells of the stored lattice
+  // gathered into row j
+  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int j) { return po.gather(j); }))) return rc;
+  for (auto& s : c->slabs) {
+    HIPC(hipSetDevice(s.dev));
+    HIPC(hipStreamSynchronize(s.sc));
+  }
+  return po.to_host();
+}
 
 static_assert(sizeof(lbm_observe) == 48 && offsetof(lbm_observe, forces) == 0 && offsetof(lbm_observe, probes_out) == 8 &&
               offsetof(lbm_observe, mean_out) == 16 && offsetof(lbm_observe, fields_out) == 24 && offsetof(lbm_observe, probes_every) == 32 &&
@@ -67,10 +606,12 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   const int mp = wp ? nsteps / pe : 0, mm = wm ? nsteps / me : 0, msn = (ws && se > 0) ? nsteps / se : 0;
   if (msn == 0) ws = false;                               // (no snapshot is due: legal, nothing written, as lbm_run_sampled)
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
-  bool p_dev = false, m_dev = false, s_dev = false;
+  ProbeOut po(c);
+  MeanOut mo(c);
+  bool s_dev = false;
   int rc;
-  if (wp && (rc = output_on_device(c, what->probes_out, "probes_out", &p_dev))) return rc;
-  if (wm && (rc = output_on_device(c, what->mean_out, "mean_out", &m_dev))) return rc;
+  if (wp && (rc = po.locate(what->probes_out, "probes_out"))) return rc;
+  if (wm && (rc = mo.locate(what->mean_out, "mean_out"))) return rc;
   if (ws && (rc = output_on_device(c, what->fields_out, "fields_out", &s_dev))) return rc;
   c->observed_in_kernel = 0; c->observed_in_wave = 0; c->observed_pieces = 0;
   if (wf) c->forces_in_wave = 0;                          // (set by any piece whose forces rode in lbm_wave launches)
@@ -93,7 +634,6 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   // ---- two or more.  Everything that can fail for want of room is decided here, before anything is queued.
   const int nx = c->p.nx, nb = c->nbodies, np = c->nprobes;
   const size_t ns = c->slabs.size();
-  const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
   long rows = 0;
   for (auto& s : c->slabs) rows += s.nyl;
   const long slot = rows * nx * 4;                        // floats per snapshot
@@ -101,9 +641,6 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     return fail(LBM_EINVAL, "%d snapshots of %ld floats do not fit the address space", msn, slot);
   if (wf && 2L * nb * nsteps + nsteps + 1 > (1L << 30)) return fail(LBM_EINVAL, "a forces run of %d steps is too long (split it)", nsteps);
   bool tiles = regtile_is_next(c);
-  const size_t pfloat = 4 * (size_t)mp * (size_t)np;
-  std::vector<DeviceTemp> pstage(ns), macc(ns);
-  size_t plocal = 0;
   rc = LBM_OK;
   for (size_t i = 0; i < ns && !rc; ++i) {
     Slab& s = c->slabs[i];
@@ -114,41 +651,17 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     }
     if (!rc && tiles && !(wf && wp)) rc = observed_no_force_table(s, c->tplan.ntx * c->tplan.nty);
     if (!rc && wf && tiles) rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps);
-    if (wp) plocal += s.pcells_host.size();
-    if (!rc && wp && !p_dev && !s.pcells_host.empty() && hipMalloc(&pstage[i].p, sizeof(float) * pfloat) != hipSuccess) {
-      (void)hipGetLastError();
-      pstage[i].p = nullptr;
-      rc = fail(LBM_ENOMEM, "no room on device %d for %d sample(s) of %d probe(s) of slab %zu (%zu bytes)", s.dev, mp, np, i, sizeof(float) * pfloat);
-    }
     if (!rc && wp && tiles) rc = probe_tables(c, s, c->tplan.ty, c->tplan.ntx);
-    if (!rc && wm && hipMalloc(&macc[i].p, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx) != hipSuccess) {
-      (void)hipGetLastError();
-      macc[i].p = nullptr;
-      rc = fail(LBM_ENOMEM, "no room on device %d for the sums of slab %zu (%zu bytes)", s.dev, i, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx);
-    }
   }
+  if (!rc && wp) rc = po.prepare(mp);
+  if (!rc && wm) rc = mo.prepare();
   if ((rc = ranks_agree(c, rc, &tiles, "the observers' buffers"))) return rc;
   // probes where lbm_run would run lbm_wave (a lattice alone): they ride in its launches, beside the forces if those are
   // wanted, and cut no piece; decided here, before anything is queued (no: lbm_probe_gather behind pieces cut at their steps)
   const bool pwave = wp && !rc && !tiles && wave_probes_admit(c, wf);
   int wbits = 0;
-  // the probes of other ranks' rows read +0.0f
-  if (wp && plocal < (size_t)np) {
-    if (p_dev) {
-      Slab& s = c->slabs[0];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(what->probes_out, 0, sizeof(float) * pfloat, s.sc));
-      HIPC(hipStreamSynchronize(s.sc));
-    } else memset(what->probes_out, 0, sizeof(float) * pfloat);
-  }
-  auto probes_of = [&](size_t i) { return p_dev ? what->probes_out : (float*)pstage[i].p; };
-  auto mean_of = [&](size_t i) { return m_dev ? what->mean_out + 4L * (c->slabs[i].row0 - base_row) * nx : (float*)macc[i].p; };
-  if (wm)
-    for (size_t i = 0; i < ns; ++i) {
-      Slab& s = c->slabs[i];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(macc[i].p, 0, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx, s.sc));
-    }
+  if (wp && (rc = po.zero_foreign())) return rc;
+  if (wm && (rc = mo.clear())) return rc;
   // ---- the pieces
   double gpu_ms = 0.0, wall_ms = 0.0;
   int done = 0, pieces = 0, bits = 0, jsnap = 0;
@@ -167,11 +680,7 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     if (on_tiles) {
       SnapPlan sp;
       sp.every = pe;
-      for (size_t i = 0; wp && i < ns; ++i) {
-        float* at = probes_of(i);
-        sp.at.push_back(at ? at + 4 * (size_t)jp * (size_t)np : nullptr);   // (a slab without a probe stores nothing)
-        sp.stride.push_back(4L * np);
-      }
+      for (size_t i = 0; wp && i < ns; ++i) { sp.at.push_back(po.at(i, jp)); sp.stride.push_back(4L * np); }
       bool ran = false;
       if (wp) { k.snap = &sp; k.probe = true; k.pfirst = pe - done % pe; }
       k.piece = true; k.piece_mid = next < nsteps; k.ran = &ran;
@@ -182,74 +691,32 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
       k.no_tiles = true;
       if (pwave) {
         // (the probes' phase runs on from the start of the call: the first sample of this piece, and its row of the output)
-        k.wave_pevery = pe; k.pfirst = pe - done % pe; k.wave_pout = probes_of(0) + 4 * (size_t)jp * (size_t)np;
+        k.wave_pevery = pe; k.pfirst = pe - done % pe; k.wave_pout = po.at(0, jp);
         c->probes_in_wave = 0;
       }
       if ((rc = run_steps(c, n, av, k))) return rc;
       if (pwave && c->probes_in_wave) wbits |= 2;
       if (wf && c->forces_in_wave) wbits |= 1;
-      if (wp && !pwave && (done + n) % pe == 0)
-        for (size_t i = 0; i < ns; ++i) {
-          Slab& s = c->slabs[i];
-          const int n_here = (int)s.pcells_host.size();
-          if (n_here == 0) continue;
-          HIPC(hipSetDevice(s.dev));
-          hipLaunchKernelGGL(lbm::lbm_probe_gather, dim3(cdiv(n_here, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane,
-                             s.pcells, n_here, s.blocked, c->p.density, probes_of(i) + 4 * (size_t)jp * (size_t)np);
-          HIPC(hipGetLastError());
-        }
+      if (wp && !pwave && (done + n) % pe == 0 && (rc = po.gather(jp))) return rc;
     }
-    if (wf) observed_forces(c, n, nval, what->forces + 2L * nb * done);
+    if (wf) fetch_forces(c, n, nval, what->forces + 2L * nb * done);
     gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
     done += n;
     ++pieces;
-    if (wm && done % me == 0)
-      for (size_t i = 0; i < ns; ++i) {
-        Slab& s = c->slabs[i];
-        HIPC(hipSetDevice(s.dev));
-        const long ncell = (long)s.nyl * nx;
-        hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
-                           nx, ncell, s.blocked, c->p.density, (float*)macc[i].p);
-        HIPC(hipGetLastError());
-      }
+    if (wm && done % me == 0 && (rc = mo.add())) return rc;
     if (ws && done % se == 0) {
       if ((rc = derive_all(c, what->fields_out + (size_t)jsnap * (size_t)slot, nullptr, nullptr, s_dev))) return rc;
       ++jsnap;
     }
   }
   // ---- the means, and what was staged for the host
-  for (size_t i = 0; i < ns; ++i) {
-    Slab& s = c->slabs[i];
-    HIPC(hipSetDevice(s.dev));
-    if (wm) {
-      const long ncell = (long)s.nyl * nx;
-      hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, (const float*)macc[i].p, ncell,
-                         (float)mm, mean_of(i));
-      HIPC(hipGetLastError());
-    }
-    HIPC(hipStreamSynchronize(s.sc));
-    if (wm && !m_dev)
-      HIPC(hipMemcpy(what->mean_out + 4L * (s.row0 - base_row) * nx, macc[i].p, sizeof(float) * 4 * (size_t)s.nyl * (size_t)nx, hipMemcpyDeviceToHost));
-  }
-  if (wp && !p_dev) {
-    std::vector<float> tmp;
-    for (size_t i = 0; i < ns; ++i) {
-      Slab& s = c->slabs[i];
-      if (s.pcells_host.empty()) continue;
+  if (wm) { if ((rc = mo.finish(mm))) return rc; }
+  else
+    for (auto& s : c->slabs) {
       HIPC(hipSetDevice(s.dev));
-      if (s.pcells_host.size() == (size_t)np) {            // (every probe is this slab's)
-        HIPC(hipMemcpy(what->probes_out, pstage[i].p, sizeof(float) * pfloat, hipMemcpyDeviceToHost));
-        continue;
-      }
-      tmp.resize(pfloat);
-      HIPC(hipMemcpy(tmp.data(), pstage[i].p, sizeof(float) * pfloat, hipMemcpyDeviceToHost));
-      for (int j = 0; j < mp; ++j)
-        for (const int4& q : s.pcells_host) {
-          const size_t o = 4 * ((size_t)j * np + (size_t)q.z);
-          memcpy(what->probes_out + o, tmp.data() + o, 4 * sizeof(float));
-        }
+      HIPC(hipStreamSynchronize(s.sc));
     }
-  }
+  if (wp && (rc = po.to_host())) return rc;
   c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
   c->observed_in_kernel = bits; c->observed_in_wave = wbits; c->observed_pieces = pieces;
   return LBM_OK;

@@ -10,7 +10,7 @@ struct SnapPlan {
   std::vector<long> stride;
 };
 
-// The kind of a run, handed from lbm_run / lbm_run_sampled / lbm_run_forces through run_steps to the engine that runs it
+// The kind of a run, handed from lbm_run and the observer calls (lbm_host_observe.inc) through run_steps to the engine that runs it
 // (a plain lbm_run: the defaults).  snap (lbm_run_sampled): ONLY the register tiles are tried, with the snapshots in the
 // kernel.  nb > 0 (lbm_run_forces): nb bodies; the run's forces are nval = 2 nb nsteps doubles at sums + nsteps + 1 of every
 // slab (behind the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with
@@ -41,7 +41,7 @@ struct RunKind {
   // flavours; behind a left-over step that is a sample step, lbm_probe_gather.
   float* wave_pout = nullptr;
   int wave_pevery = 0;
-  // wave_fout (lbm_run_sampled / lbm_run_mean on a context wave_fields_admit said yes to; a lattice alone, the register
+  // wave_fout (lbm_run_sampled / lbm_run_mean on a context wave_admit said yes to; a lattice alone, the register
   // tiles kept off): the sample steps are wave_fevery, 2 wave_fevery, ... steps into this run; wave_fout is the first
   // sample's field, [ny][nx][4] floats on the slab's device, wave_fstride the floats from one sample's field to the next;
   // wave_fadd: the samples are added into ONE field (wave_fstride = 0), the sums of a mean.  The groups of K steps take them
