@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
-    "lbm_set_probes", "lbm_run_probes", "lbm_run_observed",
+    "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows",
     "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
@@ -64,6 +64,18 @@ class Observe(C.Structure):
     """Field-for-field lbm_observe (include/lbm_mi355x.h): a NULL pointer = that observer is not wanted."""
     _fields_ = [("forces", C.c_void_p), ("probes_out", C.c_void_p), ("mean_out", C.c_void_p), ("fields_out", C.c_void_p),
                 ("probes_every", C.c_int), ("mean_every", C.c_int), ("fields_every", C.c_int)]
+
+
+class Window(C.Structure):
+    """Field-for-field lbm_window (include/lbm_mi355x.h): the cells (x0 + c sx, y0 + r sy), c < nx, r < ny, of the global
+    lattice.  Window(x0, y0, nx, ny) is a plain sub-rectangle (strides 1)."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("sx", C.c_int), ("sy", C.c_int)]
+
+    def __init__(self, x0=0, y0=0, nx=1, ny=1, sx=1, sy=1):
+        super().__init__(x0, y0, nx, ny, sx, sy)
+
+    def __repr__(self):
+        return "Window(x0=%d, y0=%d, nx=%d, ny=%d, sx=%d, sy=%d)" % (self.x0, self.y0, self.nx, self.ny, self.sx, self.sy)
 
 
 _lib = None
@@ -102,6 +114,8 @@ def load_library():
     lib.lbm_run_probes.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_run_forces.argtypes = [vp, C.c_int, vp, vp]
     lib.lbm_run_observed.argtypes = [vp, C.c_int, vp, C.POINTER(Observe)]
+    lib.lbm_run_window.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(Window), vp]
+    lib.lbm_window_rows.argtypes = [C.POINTER(Window), C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
@@ -129,6 +143,14 @@ def plan_tiles(nx: int, rows: int, slabs_per_device: int = 1, compute_units: int
     ty, r = C.c_int(0), C.c_int(0)
     rc = load_library().lbm_plan_tiles(nx, rows, slabs_per_device, compute_units, C.byref(ty), C.byref(r))
     return (ty.value, r.value) if rc == 0 else None
+
+
+def window_rows(window: Window, nx: int, ny: int, row_begin: int, row_end: int):
+    """(first, count): the rows first .. first + count - 1 of `window` lie in rows [row_begin, row_end) of an nx x ny
+    lattice (lbm_window_rows: host arithmetic, no device).  Raises LbmError where the window is not legal there."""
+    first, count = C.c_int(0), C.c_int(0)
+    _check(load_library().lbm_window_rows(C.byref(window), nx, ny, row_begin, row_end, C.byref(first), C.byref(count)))
+    return first.value, count.value
 
 
 def device_count() -> int:
@@ -263,6 +285,22 @@ class Lattice:
         probes, ptr = self._output(out, shape, "out")
         _check(self._lib.lbm_run_probes(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, probes
+
+    def run_window(self, nsteps: int, every: int, window: Window, out=None):
+        """lbm_run with snapshots of a window after steps every, 2 every, ...: returns (av_vels[nsteps], windows) where
+        windows is (m, window.ny, window.nx, 4) float32 (m = nsteps // every) -- the bits run_sampled has in the cells
+        (window.x0 + c window.sx, window.y0 + r window.sy) of the global lattice -- a numpy array, or `out`, a contiguous
+        float32 torch tensor of that shape on the context's GPU, filled there.  A rank context fills the window rows that
+        lie in its own lattice rows (window_rows with slab_rows) and zeroes the others.  The register tiles take the
+        window inside their kernels (info("window_in_kernel") == 1); where lbm_wave runs it rides in its launches
+        (info("window_in_wave") == 1); elsewhere the steps run in pieces of `every` with a windowed derive kernel behind
+        each.  Traffic, staging and host copy scale with the window, not with the lattice."""
+        m = max(nsteps, 0) // every if every > 0 else 0
+        shape = (m, window.ny, window.nx, 4)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        windows, ptr = self._output(out, shape, "out")
+        _check(self._lib.lbm_run_window(self._ctx, nsteps, av.ctypes.data, every, C.byref(window), ptr))
+        return av, windows
 
     def set_bodies(self, body, nbodies: int):
         """Labels blocked cells 1..nbodies (0: not counted) for run_forces: body is int[ny, nx] over the global lattice

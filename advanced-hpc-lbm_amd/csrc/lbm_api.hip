@@ -210,6 +210,12 @@ struct Slab {
   int* pslot = nullptr;
   uint32_t* pwords = nullptr;
   int pty = 0;
+  // windows (lbm_run_window): the register tiles' tables of the last window this slab ran, laid out as pslot / pwords, for
+  // tiles of wty rows (0: not built) and the window wkey; the probe set and its tables are not touched
+  int* wslot = nullptr;
+  uint32_t* wwords = nullptr;
+  int wty = 0;
+  lbm_window wkey = {0, 0, 0, 0, 0, 0};
   // lbm_run_observed, probes without forces in the kRegForce | kRegProbe flavour: a force slot table of fslot_none_n tiles
   // that are all -1 (no tile counts anything)
   int* fslot_none = nullptr;
@@ -266,6 +272,8 @@ struct lbm_ctx {
   long wave_launches = 0;      // lbm_wave kernels this context has launched so far, every flavour (launch_wave counts them)
   int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
   int probes_in_wave = 0;      // 1: the last lbm_run_probes took its values inside lbm_wave launches
+  int window_in_kernel = 0;    // 1: the last lbm_run_window took its window inside the register tiles
+  int window_in_wave = 0;      // 1: the last lbm_run_window took its window inside lbm_wave launches
   int observed_in_wave = 0;    // the last lbm_run_observed: bits 1 forces, 2 probes taken inside lbm_wave launches
   int observed_in_kernel = 0;  // the last lbm_run_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
   int observed_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
@@ -692,7 +700,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (rr) return rr;
     if (done) {
       c->engine_last = 3;
-      if (k.snap && k.probe) c->probes_in_kernel = 1;
+      if (k.snap && k.window) c->window_in_kernel = 1;
+      else if (k.snap && k.probe) c->probes_in_kernel = 1;
       else if (k.snap && k.mean) c->mean_in_kernel = 1;
       else if (k.snap) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
@@ -737,7 +746,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     int rc;
     if (psample(s) && (rc = launch_probe_gather(c, sl, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes))) return rc;
     if (fsample(s) && k.wave_fadd && (rc = launch_mean_add(c, sl, k.wave_fout))) return rc;
-    if (fsample(s) && !k.wave_fadd) {
+    if (fsample(s) && k.win && (rc = launch_derive_window(c, sl, k.win->w, 0, k.win->w.ny, fslot(s)))) return rc;
+    if (fsample(s) && !k.wave_fadd && !k.win) {
       const long ncell = (long)sl.nyl * nx;
       hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
                          nx, ncell, sl.blocked, c->p.density, fslot(s), k.wave_fpart, k.wave_fmass);
@@ -861,7 +871,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
       }
       WaveFields wf;
       if (fw && wave) {                                  // likewise: the first sample's field
-        wf.stride = k.wave_fstride; wf.add = k.wave_fadd;
+        wf.stride = k.wave_fstride; wf.add = k.wave_fadd; wf.win = k.win ? &k.win->wave : nullptr;
         for (int l = K; l >= 1; --l)
           if (fsample(tt + l)) { wf.mask |= 1u << (l - 1); wf.out = fslot(tt + l); }
       }
@@ -869,7 +879,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     }
     if (fwave) c->forces_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
-    if (fw && wave) { if (k.wave_fadd) c->mean_in_wave = 1; else c->samples_in_wave = 1; }
+    if (fw && wave) { if (k.win) c->window_in_wave = 1; else if (k.wave_fadd) c->mean_in_wave = 1; else c->samples_in_wave = 1; }
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -1171,6 +1181,8 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "wave_launches")) { *value = (double)c->wave_launches; return LBM_OK; }
   if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
   if (!strcmp(key, "probes_in_wave")) { *value = c->probes_in_wave; return LBM_OK; }
+  if (!strcmp(key, "window_in_kernel")) { *value = c->window_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "window_in_wave")) { *value = c->window_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_wave")) { *value = c->observed_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }
   if (!strcmp(key, "observed_pieces")) { *value = c->observed_pieces; return LBM_OK; }

@@ -567,6 +567,22 @@ wave_fn wave_field_kernel(int K, int C, int flavour) {
   return wave_field_kernel_f<4, 1>(flavour);
 }
 
+// ... and their window flavour (lbm_run_window): the lone-lattice forms only, where the field flavour is instantiated
+template <int K, int C>
+wave_fn wave_window_kernel_f(int flavour) {
+  switch (flavour & 3) {
+    case 0: return lbm::lbm_wave<K, 0, false, C, false, false, false, true>;
+    case 1: return lbm::lbm_wave<K, 1, false, C, false, false, false, true>;
+    case 2: return lbm::lbm_wave<K, 2, false, C, false, false, false, true>;
+    default: return lbm::lbm_wave<K, 3, false, C, false, false, false, true>;
+  }
+}
+wave_fn wave_window_kernel(int K, int C, int flavour) {
+  if (K == 8) return C == 2 ? wave_window_kernel_f<8, 2>(flavour) : wave_window_kernel_f<8, 1>(flavour);
+  if (K == 6) return wave_window_kernel_f<6, 1>(flavour);
+  return wave_window_kernel_f<4, 1>(flavour);
+}
+
 int wave_blocks_per_cu(int K, int C) {
   static int cache[16][3] = {};                 // (the answer does not change; lbm_set_option asks often)
   if (K < 16 && C < 3 && cache[K][C] > 0) return cache[K][C];
@@ -667,18 +683,20 @@ struct WaveProbes {
 
 // What a launch of the field flavour is told (RunKind::wave_fout; nullptr: no fields): the sample levels of its K steps (bit
 // l - 1: step tt + l), the field of the first of them, the floats from one sample's field to the next, store or add.
+// win (lbm_run_window): the window flavour instead -- out and stride are then of windows, and nothing is added.
 struct WaveFields {
   float* out = nullptr;
   unsigned mask = 0u;
   long stride = 0;
   bool add = false;
+  const lbm::WaveWin* win = nullptr;
 };
 
 // One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li.  nb > 0 (lbm_run_forces, wave_force_ready
 // said yes): the force flavour, and behind it the fold of the group's forces into the run's sums (of nsteps steps).
 // wp.out (wave_probe_ready said yes): the probe flavour, or the force-and-probe flavour; a group without a sample step
 // runs what it would run without probes.  wf.out (wave_admit said yes; no forces, no probes beside it): the field
-// flavour for a group that holds a sample step, the plain kernel for one that holds none.
+// flavour (wf.win: the window flavour) for a group that holds a sample step, the plain kernel for one that holds none.
 int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0, WaveProbes wp = WaveProbes(),
                 WaveFields wf = WaveFields()) {
   Slab& s = c->slabs[0];
@@ -708,6 +726,7 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   a.fidx = nullptr; a.fcells = nullptr; a.contrib = nullptr; a.fcells_n = 0;
   a.pidx = nullptr; a.pout = nullptr; a.nprobes = 0; a.pmask = 0u; a.prow = 0; a.density = c->p.density;
   a.fmask = 0u; a.fout = nullptr; a.fstride = 0; a.fadd = 0;
+  a.win = lbm::WaveWin{0, 0, 0, 1u, 1u, 0u, 0u, 0u, 0u};
   const bool probes = wp.out != nullptr && wp.mask != 0u;
   const bool fields = wf.out != nullptr && wf.mask != 0u;
   if (fields && (wp.out != nullptr || nb_bodies > 0)) return fail(LBM_EINVAL, "lbm_wave: the field flavour runs beside neither forces nor probes");
@@ -719,7 +738,8 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   };
   if (fields) {
     a.fmask = wf.mask; a.fout = wf.out; a.fstride = wf.stride; a.fadd = wf.add ? 1 : 0;
-    launch(wave_field_kernel(K, wave_C(c, K), flavour));
+    if (wf.win) { a.fadd = 0; a.win = *wf.win; launch(wave_window_kernel(K, wave_C(c, K), flavour)); }
+    else launch(wave_field_kernel(K, wave_C(c, K), flavour));
   } else if (probes && nb_bodies > 0 && s.fcells_n > 0) {
     a.blocked = s.fpmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n;
     launch(wave_probe_kernel<true>(K, wave_C(c, K), flavour));

@@ -1,6 +1,6 @@
 // lbm_host_observe.inc -- part of lbm_api.hip (included there, in front of run_steps): the observer calls -- lbm_run_sampled,
-// lbm_run_forces, lbm_run_mean, lbm_run_probes with lbm_set_bodies / lbm_set_probes, and lbm_run_observed -- and the one
-// copy of what they share:
+// lbm_run_forces, lbm_run_mean, lbm_run_probes with lbm_set_bodies / lbm_set_probes, lbm_run_observed, and lbm_run_window
+// with lbm_window_rows (WindowOut, window_tables, launch_derive_window: in front of it) -- and the one copy of what they share:
 //   output_on_device, ranks_agree          where an output lies; a rank context's ranks take the same path and fail together
 //   launch_probe_gather / _mean_add / _mean_div   the one launch site of each small kernel (run_steps' pgather uses them too)
 //   fetch_forces                           a run's forces from behind its per-step sums
@@ -583,6 +583,254 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
     HIPC(hipStreamSynchronize(s.sc));
   }
   return po.to_host();
+}
+
+// ----------------------------------------------------------------- windows (lbm_run_window)
+static_assert(sizeof(lbm_window) == 24 && offsetof(lbm_window, x0) == 0 && offsetof(lbm_window, y0) == 4 && offsetof(lbm_window, nx) == 8 &&
+              offsetof(lbm_window, ny) == 12 && offsetof(lbm_window, sx) == 16 && offsetof(lbm_window, sy) == 20, "the layout lbm_mi355x.h states");
+
+// Is w a window of an nx x ny lattice?  64-bit arithmetic: coordinates near INT_MAX must not wrap.
+static int window_check(const lbm_window* w, int nx, int ny) {
+  if (!w) return fail(LBM_EINVAL, "win is NULL");
+  if (nx < 1 || ny < 1) return fail(LBM_EINVAL, "a %d x %d lattice holds no window", nx, ny);
+  if (w->nx < 1 || w->ny < 1 || w->sx < 1 || w->sy < 1)
+    return fail(LBM_EINVAL, "a window needs nx, ny, sx, sy >= 1 (got %d x %d cells at strides %d, %d)", w->nx, w->ny, w->sx, w->sy);
+  if (w->x0 < 0 || w->y0 < 0) return fail(LBM_EINVAL, "a window starts inside the lattice (got x0 = %d, y0 = %d)", w->x0, w->y0);
+  const long long xl = (long long)w->x0 + ((long long)w->nx - 1) * (long long)w->sx, yl = (long long)w->y0 + ((long long)w->ny - 1) * (long long)w->sy;
+  if (xl >= nx || yl >= ny)
+    return fail(LBM_EINVAL, "the window's last cell (%lld, %lld) is outside the %d x %d lattice (windows do not wrap)", xl, yl, nx, ny);
+  return LBM_OK;
+}
+
+extern "C" int lbm_window_rows(const lbm_window* w, int nx, int ny, int row_begin, int row_end, int* first, int* count) {
+  int rc;
+  if ((rc = window_check(w, nx, ny))) return rc;
+  if (row_begin > row_end) return fail(LBM_EINVAL, "row_begin %d > row_end %d", row_begin, row_end);
+  // window row r lies at lattice row y0 + r sy: the r with row_begin <= y0 + r sy < row_end
+  auto rows_below = [&](long long row) -> long long {    // window rows whose lattice row is < row
+    const long long d = row - (long long)w->y0;
+    if (d <= 0) return 0;
+    return std::min<long long>(w->ny, (d + w->sy - 1) / w->sy);
+  };
+  const long long a = rows_below(row_begin), b = rows_below(row_end);
+  if (first) *first = (int)a;
+  if (count) *count = (int)(b - a);
+  return LBM_OK;
+}
+
+namespace {
+
+// the window cells of a slab's stored lattice into out4 = float[count][w.nx][4]: the slab's window rows first .. first + count - 1
+int launch_derive_window(const lbm_ctx* c, Slab& s, const lbm_window& w, int first, int count, float* out4) {
+  if (count <= 0) return LBM_OK;
+  const long ncell = (long)count * w.nx;
+  const long yl0 = (long)w.y0 + (long)first * w.sy - s.row0;
+  HIPC(hipSetDevice(s.dev));
+  hipLaunchKernelGGL(lbm::lbm_derive_window, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
+                     w.x0, w.nx > 1 ? w.sx : 1, w.nx, (int)yl0, count > 1 ? w.sy : 1, ncell, s.blocked, c->p.density, out4);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// The register tiles' tables of a slab for a window and tiles of ty rows, laid out exactly as probe_tables lays out pslot /
+// pwords: slots in the order of the tiles (only tiles that hold a window cell have one); a cell's word is its place among the
+// SLAB's window rows + 1, (r - first) w.nx + c + 1 -- the slab's output pointer is its first window row's.  Kept by
+// (window, tiling); the probe set's tables are not touched.  LBM_ENOMEM: nothing queued.
+int window_tables(lbm_ctx* c, Slab& s, int ty, int ntx, const lbm_window& w, int first, int count) {
+  (void)c;
+  if (s.wty == ty && memcmp(&s.wkey, &w, sizeof(w)) == 0) return LBM_OK;
+  HIPC(hipSetDevice(s.dev));
+  const int nty = s.nyl / ty, ntiles = ntx * nty;
+  std::vector<int> slot(ntiles, -1);
+  auto cell_y = [&](int r) { return (int)((long)w.y0 + (long)(first + r) * w.sy - s.row0); };
+  auto cell_x = [&](int cc) { return (int)((long)w.x0 + (long)cc * w.sx); };
+  for (int r = 0; r < count; ++r)
+    for (int cc = 0; cc < w.nx; ++cc) slot[(cell_y(r) / ty) * ntx + cell_x(cc) / 64] = 0;
+  int n = 0;
+  for (int& v : slot) if (v == 0) v = n++;
+  std::vector<uint32_t> words((size_t)n * ty * 64, 0u);
+  for (int r = 0; r < count; ++r) {
+    const int y = cell_y(r);
+    for (int cc = 0; cc < w.nx; ++cc) {
+      const int x = cell_x(cc);
+      words[((size_t)slot[(y / ty) * ntx + x / 64] * ty + y % ty) * 64 + x % 64] = (uint32_t)((long)r * w.nx + cc) + 1u;
+    }
+  }
+  if (s.wslot) HIPC(hipFree(s.wslot));
+  if (s.wwords) HIPC(hipFree(s.wwords));
+  s.wslot = nullptr; s.wwords = nullptr; s.wty = 0;
+  if (hipMalloc((void**)&s.wslot, sizeof(int) * ntiles) != hipSuccess ||
+      (n > 0 && hipMalloc((void**)&s.wwords, sizeof(uint32_t) * words.size()) != hipSuccess)) {
+    (void)hipGetLastError();
+    if (s.wslot) (void)hipFree(s.wslot);
+    s.wslot = nullptr; s.wwords = nullptr;
+    return fail(LBM_ENOMEM, "no room on device %d for the window tables (%d tiles)", s.dev, n);
+  }
+  HIPC(hipMemcpy(s.wslot, slot.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
+  if (n > 0) HIPC(hipMemcpy(s.wwords, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
+  s.wty = ty; s.wkey = w;
+  return LBM_OK;
+}
+
+// Where one call's windows go, [m][w.ny][w.nx][4] floats.  Device output is written in place; host output goes through one
+// staging buffer per slab that holds a window row, of the slab's own window rows only -- [m][count][w.nx][4], copied out by
+// to_host -- or, where that does not fit, of ONE sample (`single`: the split path alone, copied out behind each sample).
+struct WindowOut {
+  lbm_ctx* c;
+  lbm_window w;
+  float* out = nullptr;
+  bool on_dev = false, single = false;
+  int m = 0;
+  size_t wfloats = 0;                      // floats of one window
+  long local = 0;                          // window rows that the slabs of this context hold
+  std::vector<int> first, count;           // per slab: its window rows
+  std::vector<DeviceTemp> stage;
+
+  WindowOut(lbm_ctx* ctx, const lbm_window& win) : c(ctx), w(win) {
+    wfloats = 4 * (size_t)w.nx * (size_t)w.ny;
+    for (auto& s : c->slabs) {
+      int f = 0, n = 0;
+      (void)lbm_window_rows(&w, c->p.nx, c->p.ny, s.row0, s.row0 + s.nyl, &f, &n);
+      first.push_back(f); count.push_back(n); local += n;
+    }
+  }
+  int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
+  size_t slab_floats(size_t i) const { return 4 * (size_t)w.nx * (size_t)count[i]; }
+  // the staging of m_ samples, or of one (LBM_ENOMEM: nothing queued, nothing kept)
+  int prepare(int m_, bool one) {
+    m = m_; single = one;
+    stage.clear(); stage.resize(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (on_dev || count[i] == 0) continue;
+      const size_t bytes = sizeof(float) * slab_floats(i) * (size_t)(one ? 1 : m);
+      HIPC(hipSetDevice(s.dev));
+      if (hipMalloc(&stage[i].p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        stage[i].p = nullptr;
+        return fail(LBM_ENOMEM, "no room on device %d for %d window(s) of slab %zu (%zu bytes)", s.dev, one ? 1 : m, i, bytes);
+      }
+    }
+    return LBM_OK;
+  }
+  // the window rows of other ranks' lattice rows read +0.0f
+  int zero_foreign() {
+    if (local >= w.ny) return LBM_OK;
+    if (on_dev) {
+      Slab& s = c->slabs[0];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemsetAsync(out, 0, sizeof(float) * wfloats * (size_t)m, s.sc));
+      HIPC(hipStreamSynchronize(s.sc));
+    } else memset(out, 0, sizeof(float) * wfloats * (size_t)m);
+    return LBM_OK;
+  }
+  // where slab i's first window row of sample j goes (a slab without a window row stores nothing: NULL), and the floats
+  // from one sample to the next there
+  long stride(size_t i) const { return on_dev ? (long)wfloats : (long)slab_floats(i); }
+  float* at(size_t i, int j) const {
+    if (count[i] == 0) return nullptr;
+    if (on_dev) return out + (size_t)j * wfloats + 4 * (size_t)first[i] * (size_t)w.nx;
+    return (float*)stage[i].p + (single ? 0 : (size_t)j * slab_floats(i));
+  }
+  float* host_at(size_t i, int j) const { return out + (size_t)j * wfloats + 4 * (size_t)first[i] * (size_t)w.nx; }
+  // the window cells of the stored lattice into sample j, on every slab that holds a window row
+  int derive(int j) {
+    int rc;
+    for (size_t i = 0; i < c->slabs.size(); ++i)
+      if ((rc = launch_derive_window(c, c->slabs[i], w, first[i], count[i], at(i, j)))) return rc;
+    if (!single || on_dev) return LBM_OK;
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipStreamSynchronize(s.sc));
+      HIPC(hipMemcpy(host_at(i, j), stage[i].p, sizeof(float) * slab_floats(i), hipMemcpyDeviceToHost));
+    }
+    return LBM_OK;
+  }
+  // every slab's stream waited for, and what was staged into the caller's array
+  int finish() {
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipStreamSynchronize(s.sc));
+      if (on_dev || single || count[i] == 0) continue;
+      const size_t wbytes = sizeof(float) * slab_floats(i);
+      if (count[i] == w.ny) HIPC(hipMemcpy(out, stage[i].p, wbytes * (size_t)m, hipMemcpyDeviceToHost));
+      else HIPC(hipMemcpy2D(host_at(i, 0), sizeof(float) * wfloats, stage[i].p, wbytes, wbytes, (size_t)m, hipMemcpyDeviceToHost));
+    }
+    return LBM_OK;
+  }
+};
+
+// the window as lbm_wave's window flavour tests it; false: a multiply-high would not be exact (extent x stride >= 2^32)
+bool window_for_wave(const lbm_window& w, lbm::WaveWin* out) {
+  const unsigned long long sx = w.nx > 1 ? (unsigned)w.sx : 1u, sy = w.ny > 1 ? (unsigned)w.sy : 1u;
+  const unsigned long long xl = (unsigned long long)(w.nx - 1) * sx, yl = (unsigned long long)(w.ny - 1) * sy;
+  if (xl * sx >= (1ull << 32) || yl * sy >= (1ull << 32)) return false;
+  out->x0 = w.x0; out->y0 = w.y0; out->nx = w.nx;
+  out->sx = (unsigned)sx; out->sy = (unsigned)sy; out->xlast = (unsigned)xl; out->ylast = (unsigned)yl;
+  out->mx = sx > 1 ? (unsigned)((1ull << 32) / sx + 1ull) : 0u;
+  out->my = sy > 1 ? (unsigned)((1ull << 32) / sy + 1ull) : 0u;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every, const lbm_window* win, float* window_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  int rc;
+  if ((rc = window_check(win, c->p.nx, c->p.ny))) return rc;
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every < 0) return fail(LBM_EINVAL, "every < 0");
+  const int m = every > 0 ? nsteps / every : 0;
+  if (m > 0 && !window_out) return fail(LBM_EINVAL, "window_out is NULL but %d window(s) are due", m);
+  const unsigned long long wfl = 4ull * (unsigned long long)win->nx * (unsigned long long)win->ny;
+  if ((unsigned long long)m > (unsigned long long)(PTRDIFF_MAX / 4) / wfl)
+    return fail(LBM_EINVAL, "%d windows of %llu floats do not fit the address space", m, wfl);
+  WinPlan plan;
+  plan.w = *win;
+  const bool wave_exact = window_for_wave(plan.w, &plan.wave);
+  WindowOut wo(c, plan.w);
+  if (m > 0 && (rc = wo.locate(window_out, "window_out"))) return rc;
+  c->window_in_kernel = 0; c->window_in_wave = 0;
+  if (m == 0) return run_steps(c, nsteps, av_vels);
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room is decided here, before anything is queued.  The staging of m windows, or
+  // the register tiles' tables, that do not fit: the split path with the staging of one window, the same bits.
+  bool in_kernel = regtile_is_next(c);
+  bool staged = wo.prepare(m, false) == LBM_OK;
+  for (size_t i = 0; i < c->slabs.size() && staged && in_kernel; ++i)
+    in_kernel = window_tables(c, c->slabs[i], c->tplan.ty, c->tplan.ntx, plan.w, wo.first[i], wo.count[i]) == LBM_OK;
+  rc = staged ? LBM_OK : wo.prepare(m, true);
+  in_kernel = in_kernel && staged;
+  if ((rc = ranks_agree(c, rc, &in_kernel, "the window"))) return rc;
+  if ((rc = wo.zero_foreign())) return rc;
+  if (in_kernel) {
+    // ---- in the kernel: the probe flavour of the register tiles, every slab's tiles store their window cells straight
+    // into their places of device output / of the slab's staging
+    SnapPlan sp;
+    sp.every = every;
+    for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(wo.at(i, 0)); sp.stride.push_back(wo.stride(i)); }
+    RunKind k;
+    k.snap = &sp; k.window = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    if (c->window_in_kernel) return wo.finish();
+    // (the register tiles did not run, or gave up with the lattice untouched: the paths below repeat the run and store every cell again)
+  }
+  // ---- where lbm_run would run lbm_wave (a lattice alone; admission as lbm_run_sampled's): ONE run, the groups of K steps
+  // that hold a sample step in lbm_wave's window flavour, lbm_derive_window behind the left-over steps that are sample steps.
+  // Device output is written in place, host output goes through the one staging of the m windows.
+  if (staged && wave_exact && nsteps >= c->time_block && wave_admit(c)) {
+    RunKind k;
+    k.no_tiles = true; k.wave_fout = wo.at(0, 0); k.wave_fevery = every; k.wave_fstride = wo.stride(0); k.win = &plan;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    return wo.finish();
+  }
+  // ---- the step loop split at the sample steps: each piece a complete run, then the window cells of the stored lattice
+  // derived into sample j on every local slab
+  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int j) { return wo.derive(j); }))) return rc;
+  return wo.finish();
 }
 
 static_assert(sizeof(lbm_observe) == 48 && offsetof(lbm_observe, forces) == 0 && offsetof(lbm_observe, probes_out) == 8 &&

@@ -53,6 +53,18 @@ struct RunKind {
   bool wave_fadd = false;
   float* wave_fpart = nullptr;
   double* wave_fmass = nullptr;
+  // window (lbm_run_window, with snap): as probe -- the kRegProbe flavour -- but with the slabs' window tables (window_tables)
+  // in place of the probe set's.  win (lbm_run_window, with wave_fout on a context wave_admit said yes to): wave_fout and
+  // wave_fstride are of windows, the groups of K steps take them inside lbm_wave's window flavour (win->wave); behind a
+  // left-over step that is a sample step, lbm_derive_window into the slot (no sums, wave_fpart / wave_fmass unused).
+  bool window = false;
+  const struct WinPlan* win = nullptr;
+};
+
+// The window of one lbm_run_window call: as given (validated), and as lbm_wave's window flavour tests it.
+struct WinPlan {
+  lbm_window w;
+  lbm::WaveWin wave;
 };
 
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the
@@ -409,7 +421,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const bool fast = (c->variant & lbm::kFastMath) != 0, async = c->regtile_async != 0;
   const bool fk = k.nb > 0 && k.force_tiles;            // lbm_run_forces: the kRegForce flavour, with its larger LDS
   const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
-  const bool pk = k.snap && k.probe;                    // lbm_run_probes: the kRegProbe flavour, with its larger LDS
+  const bool pk = k.snap && (k.probe || k.window);      // lbm_run_probes, lbm_run_window: the kRegProbe flavour, with its larger LDS
   const bool fpk = k.piece;                             // lbm_run_observed: the kRegForce | kRegProbe flavour (forces counted when fk)
   const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : 0;
   auto kernel = [&](int fl) {
@@ -538,6 +550,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       a.density = c->p.density;
       a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
       if (pk && !fpk) { a.fslot = s.pslot; a.fwords = s.pwords; a.fpart = nullptr; a.nslots = 0; }   // (the probe flavour's tables: same members)
+      if (pk && !fpk && k.window) { a.fslot = s.wslot; a.fwords = s.wwords; }                        // (... fed a window's tables)
       a.pfirst = k.pfirst; a.pslot = s.pslot; a.pwords = s.pwords;   // (the force + probe flavour's)
       if (fpk && !pk) { a.pslot = s.fslot_none; a.pwords = nullptr; a.pfirst = 0x7fffffff; }   // (... with no probe wanted: no tile samples)
       if (fpk && !fk) { a.fslot = s.fslot_none; a.fwords = nullptr; a.fpart = nullptr; a.nslots = 0; }   // (... with no force wanted: no tile counts)

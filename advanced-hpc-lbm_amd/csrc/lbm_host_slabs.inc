@@ -372,6 +372,8 @@ void slab_free(Slab& s) {
   if (s.pcells) (void)hipFree(s.pcells);
   if (s.pslot) (void)hipFree(s.pslot);
   if (s.pwords) (void)hipFree(s.pwords);
+  if (s.wslot) (void)hipFree(s.wslot);
+  if (s.wwords) (void)hipFree(s.wwords);
   if (s.fpart) (void)hipFree(s.fpart);
   if (s.sums && !s.sums_direct) (void)hipFree(s.sums);
   if (s.sums_host) (void)hipHostFree(s.sums_host);

@@ -1243,6 +1243,27 @@ __global__ __launch_bounds__(kBlock) void lbm_probe_gather(const float* lat, lon
   *reinterpret_cast<f4a*>(row4 + 4 * (long)cw.y) = v;
 }
 
+// lbm_run_window on every engine but the register tiles' probe flavour and lbm_wave's window flavour: behind each piece of
+// `every` steps one thread per window cell of the slab takes derive_cell of its cell from the stored lattice (the bits
+// lbm_derive gives that cell) and stores them into its place of the sample: the slab's window rows are nrows rows of wnx
+// cells, cell (r, c) at row yl0 + r sy (the slab's numbering), column x0 + c sx; out4 = where the slab's first window row
+// of this sample goes, float[nrows][wnx][4].  No sums, no partial buffers.
+__global__ __launch_bounds__(kBlock) void lbm_derive_window(const float* lat, long plane, int pitch, int x0, int sx, int wnx,
+                                                            int yl0, int sy, long ncell, const uint8_t* blocked, float density,
+                                                            float* out4) {
+#pragma clang fp contract(off)
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ncell) return;
+  const long r = t / wnx; const int cc = (int)(t - r * wnx);
+  const long o = ((long)yl0 + r * sy) * pitch + ((long)x0 + (long)cc * sx);
+  float f[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
+  float rho;
+  const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
+  *reinterpret_cast<f4a*>(out4 + 4 * t) = v;
+}
+
 __global__ __launch_bounds__(kBlock) void lbm_fold_double(const double* in, int count, double* out) {
   __shared__ double red_d[kBlock / 64];
   double s = 0.0;

@@ -25,6 +25,14 @@
 
 namespace lbm {
 
+// The window of the window flavour (lbm_run_window), as the kernel tests it: cell (x, y) is window cell (c, r) when
+// x - x0 = c sx <= xlast and y - y0 = r sy <= ylast.  c and r come from a multiply-high by mx / my = floor(2^32 / stride) + 1
+// (exact while extent x stride < 2^32, which the host checks; stride 1: no multiply).  A window of one column / row is given stride 1.
+struct WaveWin {
+  int x0, y0, nx;              // first column, first row, cells per window row
+  unsigned sx, sy, xlast, ylast, mx, my;
+};
+
 struct WaveArgs {
   const float* src;            // lattice at step t (accelerate phase of step t+1 already applied)
   float* dst;                  // lattice at step t+K
@@ -78,6 +86,10 @@ struct WaveArgs {
   float* fout;                 // the output base of the pass's first sample
   long fstride;                // floats between consecutive samples' outputs (snapshots: one field; sums: 0)
   int fadd;                    // 0: stored (snapshots); 1: added to what is there (the sums of lbm_run_mean)
+  // ---- the window flavour (WINDOW; a lattice alone, lbm_run_window): fmask, fout and fstride as above, but a sample's
+  // output is the window, [win.ny][win.nx][4], and only the window's cells are derived and stored (appended: every earlier
+  // member keeps its offset)
+  WaveWin win;
 };
 
 constexpr int kWaveBlock = 256;   // four independent waves per block (they only meet for the final sums)
@@ -123,11 +135,17 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // and stores the four floats at 4 * (row * nx + column) of the sample's field: a snapshot (fadd = 0; one 16-byte store per
 // cell, a lane's two cells 32 contiguous bytes), or an add into the sums of a mean (fadd = 1; fstride = 0: load the four
 // sums, four float adds, store them back -- no contraction, lbm_mean_add's arithmetic).
+// WINDOW (lbm_run_window where lbm_wave runs; a lattice alone, a flavour of its own): at the same point and on the same fmask
+// levels as FIELD, but the level's row S0 + j - l is tested against the window's rows first -- wave-uniform: a row outside
+// the window costs one scalar test and never reaches derive_cell -- and then each of the lane's C cells against the window's
+// columns; a cell of the window goes through derive_cell with the plain obstacle bit of mreg and is stored with one 16-byte
+// store at 4 * (r * win.nx + c) of the sample's window.  No map, no index array, no division (WaveWin), nothing held across
+// the loop: what the test needs is recomputed at the sample level from kernel arguments.  Windows are stored, never summed.
 // Why the adds come in the order of the steps, as lbm_mean_add's do: own_row and out_ok do not depend on the level, so ONE
 // lane of ONE wave owns a cell at every level of a pass; it reaches levels l and l + 1 of a row in consecutive iterations,
 // in program order; so the adds of one pass into a cell's sums are same-thread accesses to one address (plain loads and
 // stores, not the nontemporal helpers), and the adds of different passes are ordered by the stream.
-template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false>
+template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false, bool WINDOW = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
 void lbm_wave(const WaveArgs a) {
   constexpr bool FAST = (MODE & kFastMath) != 0, NTS = (MODE & kNtStore) != 0, NTL = (MODE & kNtLoad) != 0;
@@ -137,6 +155,7 @@ void lbm_wave(const WaveArgs a) {
   static_assert(!(FORCE && SLAB), "the force flavour is for a lattice alone");
   static_assert(!(PROBE && SLAB), "the probe flavours are for a lattice alone");
   static_assert(!(FIELD && (SLAB || FORCE || PROBE)), "the field flavour is for a lattice alone, and a flavour of its own");
+  static_assert(!(WINDOW && (SLAB || FORCE || PROBE || FIELD)), "the window flavour is for a lattice alone, and a flavour of its own");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -298,6 +317,29 @@ void lbm_wave(const WaveArgs a) {
         }
       }
     };
+    // WINDOW, at a sample level behind collide_cell(s): the window's cells of the level's row into the sample's window
+    [[maybe_unused]] auto store_window = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
+      if (own_row && ((a.fmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
+        const unsigned ry = (unsigned)(S0 + j - l - a.win.y0);  // (a row below the window wraps past ylast)
+        if (ry <= a.win.ylast) {                                // (wave-uniform, as is the rest of the row test)
+          const unsigned r = a.win.sy == 1u ? ry : __umulhi(ry, a.win.my);
+          if (r * a.win.sy == ry && out_ok) {
+#pragma clang fp contract(off)
+            float* o = a.fout + (long)__builtin_popcount(a.fmask & ((1u << (l - 1)) - 1u)) * a.fstride + 4 * (long)r * a.win.nx;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+              const unsigned cx = (unsigned)(X0 - K + C * lane + c - a.win.x0);
+              const unsigned q = a.win.sx == 1u ? cx : __umulhi(cx, a.win.mx);
+              if (cx <= a.win.xlast && q * a.win.sx == cx) {
+                float rho;
+                const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
+                *reinterpret_cast<f4a*>(o + 4 * (long)q) = v;
+              }
+            }
+          }
+        }
+      }
+    };
     float nxt[C][9]; unsigned nblk;
     load_row(nxt, nblk);
     // One iteration.  STEADY: past the 2K fill iterations of the chunk every level has its history, the "is this level
@@ -357,6 +399,7 @@ void lbm_wave(const WaveArgs a) {
             const float sp = collide_cell<FAST>(p[0], blk, a.omega);
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
+            if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
             if (acc) accelerate_cell(p[0], blk, a.a1, a.a2);
             sum[l - 1] += (out_ok && own_row) ? sp : 0.f;
           } else {
@@ -367,6 +410,7 @@ void lbm_wave(const WaveArgs a) {
             collide_cells<FAST, C>(p, blk, a.omega, sp);      // the lane's cells statement by statement: independent chains
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
+            if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
 #pragma unroll
             for (int c = 0; c < C; ++c)
               if (acc) accelerate_cell(p[c], blk[c], a.a1, a.a2);

@@ -323,6 +323,59 @@ typedef struct {
    Overlapping observers of one kind with different periods: not offered. */
 int lbm_run_observed(lbm_ctx* ctx, int nsteps, float* av_vels, const lbm_observe* what);
 
+/*
+ * Snapshots of a window: a sub-rectangle of the lattice, optionally every sx-th column and sy-th row of it, stored from
+ * inside the kernels (a movie of the wake behind a body, a quarter-resolution view of the whole channel).  Traffic,
+ * staging and host copy scale with the window, not with the lattice.
+ * Layout (plain C): sizeof(lbm_window) = 24, six ints, no padding.
+ */
+typedef struct { int x0, y0, nx, ny, sx, sy; } lbm_window;
+/* The window holds the cells (x0 + c sx, y0 + r sy), c in [0, nx), r in [0, ny), of the GLOBAL lattice (in every mode).
+   Points are sampled, not averaged.  It does not wrap: nx, ny, sx, sy >= 1; x0, y0 >= 0; x0 + (nx - 1) sx < lattice nx,
+   y0 + (ny - 1) sy < lattice ny (checked in 64-bit arithmetic).  The whole lattice at stride 1 is a legal window.
+
+   lbm_run that also writes window_out[m][win->ny][win->nx][4] = u_x, u_y, |u|, pressure of the window's cells after steps
+   every, 2 every, ..., m every (m = nsteps / every; every = 0, or no sample step in nsteps: none, exactly lbm_run, nothing
+   written, window_out may be NULL).
+   Definition, bit for bit: window_out[j][r][c][:] equals fields_out[j][win->y0 + r win->sy][win->x0 + c win->sx][:] of
+   lbm_run_sampled(ctx, nsteps, av_vels, every, fields_out) from the same state with the same options; a blocked cell
+   reads 0, 0, 0, density / 3.  av_vels, the lattice and everything after the call are what they are for lbm_run_sampled
+   on the same context: lbm_run's bits wherever the register tiles or lbm_wave took the window, within float rounding of
+   the per-step sum on the split path.  window_out: host memory, or device memory of the device that holds every slab of
+   the context (then nothing is copied to the host).  Single-process contexts with several slabs write the whole window.
+   Rank contexts: the window is global on every rank and every rank's array has the full window shape; a rank fills the
+   window rows that lie in its own lattice rows (lbm_window_rows with lbm_slab_rows tells which) and writes +0.0f to the
+   others; no communication is added.
+   Which kernels take the window:
+   - The register-tile engines take it inside their kernels (info "window_in_kernel" = 1), in the probe flavour fed per-slab
+     window tables (one word per cell of a tile that holds a window cell: its place in the window + 1): on a sample step
+     one 16-byte store per window cell, a row without one costs a scalar branch, a tile without one nothing.  The probe
+     set of lbm_set_probes and its tables are untouched.  Host output: each slab stages its own window rows only
+     (16 m win->nx rows bytes), copied out after the run.  av_vels is lbm_run's, bit for bit.
+   - Where lbm_wave runs (a lattice alone on its GPU with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block;
+     the register tiles refuse first), the window rides in its launches (info "window_in_wave" = 1, "window_in_kernel" =
+     0): a window flavour of lbm_wave tests the row of a sample level against the window (wave-uniform), then each of a
+     lane's cells against its columns (arithmetic on the six ints, no map, no division), and stores a window cell's four
+     floats in one 16-byte store; passes without a sample step run the plain kernel, one kernel per pass; the steps left
+     over behind the last full pass go as lbm_run's do, with lbm_derive_window behind those that are sample steps.
+     av_vels is lbm_run's, bit for bit.  Host output goes through ONE device staging of m windows; if that does not fit
+     (or a window's extent times its stride passes 2^32) the run takes the split path: the same bits, no error.
+   - Every other engine -- contexts where lbm_march runs, slabs with neighbours under copy / RCCL / streaming peer-to-peer,
+     rank contexts, runs shorter than time_block, a register-tile run that gave up -- runs the steps in pieces of `every`
+     with lbm_derive_window behind each piece on every local slab: one thread per window cell of the slab (correct, not
+     fast; the same bits; both keys read 0).
+   LBM_EINVAL with nothing queued and the lattice untouched: NULL ctx or win; a window outside the rules above; nsteps < 0;
+   every < 0; window_out NULL with m > 0; a device pointer on another device than the slabs'; m x window floats past the
+   address space.  LBM_ENOMEM likewise when a staging or table does not fit and no path with the same bits is left.
+   Rank contexts agree on room and on the path before anything is queued.
+   Not offered: windows inside lbm_run_observed (its struct layout is frozen), means over a window, block-averaged
+   downsampling, windows that wrap, windows from the command-line tool. */
+int lbm_run_window(lbm_ctx* ctx, int nsteps, float* av_vels, int every, const lbm_window* win, float* window_out);
+/* Host arithmetic only (no device needed, as lbm_plan_tiles): validates win against an nx x ny lattice (LBM_EINVAL: not a
+   legal window, or row_begin > row_end) and returns which window rows lie in lattice rows [row_begin, row_end): rows
+   *first .. *first + *count - 1 of the window (*count may be 0; first and count may be NULL). */
+int lbm_window_rows(const lbm_window* win, int nx, int ny, int row_begin, int row_end, int* first, int* count);
+
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
 int lbm_last_run_ms(const lbm_ctx* ctx, double* gpu_ms, double* wall_ms);
@@ -385,7 +438,9 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "mean_in_wave" (1: the last lbm_run_mean took its sums inside lbm_wave launches),
  * "wave_launches" (the lbm_wave kernels this context has launched on a lattice alone, every flavour: one per pass of K steps),
  * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles),
- * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches), "observed_in_kernel",
+ * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches),
+ * "window_in_kernel" (1: the last lbm_run_window took its window inside the register tiles),
+ * "window_in_wave" (1: the last lbm_run_window took its window inside lbm_wave launches), "observed_in_kernel",
  * "observed_in_wave", "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
