@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
     "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows",
+    "lbm_set_accel", "lbm_run_driven",
     "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
@@ -116,6 +117,8 @@ def load_library():
     lib.lbm_run_observed.argtypes = [vp, C.c_int, vp, C.POINTER(Observe)]
     lib.lbm_run_window.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(Window), vp]
     lib.lbm_window_rows.argtypes = [C.POINTER(Window), C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
+    lib.lbm_set_accel.argtypes = [vp, C.c_float]
+    lib.lbm_run_driven.argtypes = [vp, C.c_int, vp, vp]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
@@ -228,6 +231,30 @@ class Lattice:
         """nsteps x (timestep_new2 + swap); returns av_vels[nsteps] (float32)."""
         av = np.empty(max(nsteps, 0), dtype=np.float32)
         _check(self._lib.lbm_run(self._ctx, nsteps, av.ctypes.data))
+        return av
+
+    def set_accel(self, accel: float):
+        """Replaces the context's acceleration for every later run (lbm_set_accel): only the value is stored, nothing is
+        queued; info("accel") reads it.  A non-finite value is refused and the old one kept.  `params` is the caller's and
+        is not touched."""
+        _check(self._lib.lbm_set_accel(self._ctx, float(accel)))
+
+    def run_driven(self, accel) -> np.ndarray:
+        """lbm_run with a per-step acceleration: step t of the call is driven by accel[t] instead of the context's value
+        (a ramp, a pulsatile or oscillatory forcing, a controller's output); nsteps = len(accel); returns av_vels[nsteps].
+        accel is anything np.asarray turns into a one-dimensional array of real numbers (converted to contiguous float32);
+        every entry must be finite.  The lattice is bit-identical to `for a in accel: set_accel(a); run(1)`; the context's
+        own acceleration is untouched.  The register tiles read the schedule inside their kernel
+        (info("driven_in_kernel") == 1), a lattice alone under lbm_wave takes it in its launches
+        (info("driven_in_wave") == 1); elsewhere the one-step kernel runs each step with its own constants."""
+        arr = np.asarray(accel)
+        if arr.ndim != 1:
+            raise LbmError(f"accel must be one-dimensional (one value per step), got shape {arr.shape}")
+        if arr.dtype.kind not in "fiu":
+            raise LbmError(f"accel must hold real numbers, got dtype {arr.dtype}")
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        av = np.empty(arr.size, dtype=np.float32)
+        _check(self._lib.lbm_run_driven(self._ctx, arr.size, av.ctypes.data, arr.ctypes.data if arr.size else None))
         return av
 
     def run_sampled(self, nsteps: int, every: int, out=None):

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <mutex>
 #include <string>
@@ -226,6 +227,9 @@ struct Slab {
   uint8_t* pmap = nullptr;
   uint8_t* fpmap = nullptr;
   int* pidx = nullptr;
+  // lbm_run_driven on the register tiles: the schedule's (a1, a2) pairs on the device, room for dtab_cap steps
+  float* dtab = nullptr;
+  long dtab_cap = 0;
 };
 
 }  // namespace
@@ -274,6 +278,8 @@ struct lbm_ctx {
   int probes_in_wave = 0;      // 1: the last lbm_run_probes took its values inside lbm_wave launches
   int window_in_kernel = 0;    // 1: the last lbm_run_window took its window inside the register tiles
   int window_in_wave = 0;      // 1: the last lbm_run_window took its window inside lbm_wave launches
+  int driven_in_kernel = 0;    // 1: the last lbm_run_driven ran inside the register tiles (their kRegDrive flavour)
+  int driven_in_wave = 0;      // 1: the last lbm_run_driven ran its groups of K steps inside lbm_wave launches (the driven flavour)
   int observed_in_wave = 0;    // the last lbm_run_observed: bits 1 forces, 2 probes taken inside lbm_wave launches
   int observed_in_kernel = 0;  // the last lbm_run_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
   int observed_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
@@ -687,6 +693,10 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   const float a2 = c->p.density * c->p.accel / 36.f;
   const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour; lbm_wave in its force flavour where lbm_run would
                               // run it (fwave, below); else the one-step kernel, lbm_body_forces behind each step
+  const bool dr = k.drive != nullptr;   // lbm_run_driven: the register tiles in their kRegDrive flavour; lbm_wave in its driven flavour on a
+                                        // lattice alone (dwave, below); else the one-step kernel, each step with its own constants
+  auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };   // the accelerate constants of step t (0-based) of this run
+  auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };
   if (!k.no_tiles && (!fo || k.force_tiles) && regtile_is_next(c)) {
     bool done = false;
     int rr = run_regtile(c, nsteps, av_vels, &done, k);
@@ -705,12 +715,13 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
       else if (k.snap && k.mean) c->mean_in_kernel = 1;
       else if (k.snap) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
+      if (dr) c->driven_in_kernel = 1;
       if (k.ran) *k.ran = true;
       return LBM_OK;
     }
   }
   if (k.piece) return LBM_OK;   // (lbm_run_observed: nothing stepped; it runs the piece again off the tiles)
-  if (c->engine >= 2 && !fo) return fail(LBM_EINVAL, "the register tiles cannot run here (%s), or this lattice has no register tiling (engine = %d)",
+  if (c->engine >= 2 && !fo && !dr) return fail(LBM_EINVAL, "the register tiles cannot run here (%s), or this lattice has no register tiling (engine = %d)",
                                          c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
   if (k.snap) return LBM_OK;
   if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels, k); }
@@ -724,8 +735,11 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
     fwave = (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap && wave_force_ready(c, c->time_block);
   }
-  // (behind those groups the left-over steps go as lbm_run's do, in pairs where it takes pairs: av_vels is lbm_run's bits)
-  const bool pairs = (!fo || fwave) && t2_eligible(c) && nsteps >= 2;
+  // lbm_run_driven likewise: the groups of K steps in lbm_wave's driven flavour on a lattice alone (wave_admit's terms)
+  const bool dwave = dr && nsteps >= c->time_block && wave_admit(c);
+  // (behind those groups the left-over steps go as lbm_run's do, in pairs where it takes pairs: av_vels is lbm_run's bits;
+  // a driven run takes no pairs -- lbm_sweep2 has one pair of constants for its two steps)
+  const bool pairs = (!fo || fwave) && !dr && t2_eligible(c) && nsteps >= 2;
   // probes on an admitted context (RunKind::wave_pout): is step s (1-based) of this run a sample step, and its output row
   const bool pw = k.wave_pout != nullptr;
   auto psample = [&](int s) { return pw && s >= k.pfirst && (s - k.pfirst) % k.wave_pevery == 0; };
@@ -764,9 +778,9 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
 
-  const bool slabs_march = !fo && ex && march_slabs_on(c) && nsteps >= slab_K(c);
-  const bool bands = !fo && ex && !slabs_march && march_bands_on(c) && nsteps >= slab_K(c);   // RCCL transport: ghost bands
-  if (!fo && (slabs_march || nsteps >= c->time_block) && (rc = check_march_partials(c, slabs_march))) return rc;   // (before anything is queued)
+  const bool slabs_march = !fo && !dr && ex && march_slabs_on(c) && nsteps >= slab_K(c);
+  const bool bands = !fo && !dr && ex && !slabs_march && march_bands_on(c) && nsteps >= slab_K(c);   // RCCL transport: ghost bands
+  if (!fo && (!dr || dwave) && (slabs_march || nsteps >= c->time_block) && (rc = check_march_partials(c, slabs_march))) return rc;   // (before anything is queued)
   if (bands) {
     if ((rc = bands_setup(c, slab_K(c)))) return rc;
     for (auto& s : c->slabs) {
@@ -781,7 +795,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     HIPC(hipSetDevice(s.dev));
     if (s.accel_row >= 0) {
       hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, s.sc,
-                         s.lat[c->cur], s.plane, s.pitch, nx, s.accel_row, s.blocked, a1, a2);
+                         s.lat[c->cur], s.plane, s.pitch, nx, s.accel_row, s.blocked, da1(0), da2(0));
       HIPC(hipGetLastError());
     }
     if (slabs_march) HIPC(hipEventRecord(s.ev_march[1], s.sc));   // "launch -1": the starting lattice is in place
@@ -859,7 +873,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
       if ((rc = prime_halos((li & 1) ^ 1))) return rc;
     }
   } else
-  if ((!fo || fwave) && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
+  if ((!fo || fwave) && (!dr || dwave) && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
     const int K = c->time_block, ngroups = nsteps / K;
     const bool wave = use_wave_kernel(c);
     for (int g = 0; g < ngroups; ++g, ++li, tt += K) {
@@ -875,9 +889,14 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
         for (int l = K; l >= 1; --l)
           if (fsample(tt + l)) { wf.mask |= 1u << (l - 1); wf.out = fslot(tt + l); }
       }
-      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, wp, wf) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+      // (a driven pass from step tt: level l applies the accelerate phase of step tt + l, the last pass's level K none)
+      float drv[16] = {0.f};
+      if (dwave)
+        for (int l = 1; l <= K && tt + l < nsteps; ++l) { drv[2 * (l - 1)] = da1(tt + l); drv[2 * (l - 1) + 1] = da2(tt + l); }
+      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, wp, wf, dwave ? drv : nullptr) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
     }
     if (fwave) c->forces_in_wave = 1;
+    if (dwave) c->driven_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
     if (fw && wave) { if (k.win) c->window_in_wave = 1; else if (k.wave_fadd) c->mean_in_wave = 1; else c->samples_in_wave = 1; }
     Slab& s = c->slabs[0];
@@ -915,7 +934,9 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   const int first_single = tt;
   for (; tt < nsteps; ++tt, ++li) {
     const bool ps = psample(tt + 1) || fsample(tt + 1);
-    if ((rc = launch_single(c, li, tt, tt == nsteps - 1 || ps, tt > first_single, a1, a2))) return rc;
+    // (the rows a step writes carry the NEXT step's accelerate phase: its constants)
+    const bool lst = tt == nsteps - 1;
+    if ((rc = launch_single(c, li, tt, lst || ps, tt > first_single, lst ? a1 : da1(tt + 1), lst ? a2 : da2(tt + 1)))) return rc;
     if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
     if (ps && (rc = pgather(tt + 1, tt + 1 < nsteps))) return rc;
   }
@@ -937,6 +958,51 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
 }
 
 extern "C" int lbm_run(lbm_ctx* c, int nsteps, float* av_vels) { return lbm_run_sampled(c, nsteps, av_vels, 0, nullptr); }
+
+extern "C" int lbm_set_accel(lbm_ctx* c, float accel) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (!std::isfinite(accel)) return fail(LBM_EINVAL, "accel is not finite");
+  c->p.accel = accel;          // (every run makes its accelerate constants from c->p when it starts: nothing else to do)
+  return LBM_OK;
+}
+
+// lbm_run with a per-step acceleration: the constants of every step made here, on the host, by lbm_run's
+// expression; then the register tiles' kRegDrive flavour with the table on the device, lbm_wave's driven flavour on a lattice
+// alone, or the one-step kernel -- run_steps decides as it does for lbm_run_forces.
+extern "C" int lbm_run_driven(lbm_ctx* c, int nsteps, float* av_vels, const float* accel) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (nsteps > 0 && !accel) return fail(LBM_EINVAL, "accel is NULL");
+  for (int t = 0; t < nsteps; ++t)
+    if (!std::isfinite(accel[t])) return fail(LBM_EINVAL, "accel[%d] is not finite", t);
+  c->driven_in_kernel = 0; c->driven_in_wave = 0;
+  if (nsteps == 0) return run_steps(c, 0, av_vels);
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  std::vector<float> pairs(2 * (size_t)nsteps);
+  for (int t = 0; t < nsteps; ++t) {
+    pairs[2 * (size_t)t] = c->p.density * accel[t] / 9.f;          // d2q9-bgk.c:230-231, as run_steps makes the context's
+    pairs[2 * (size_t)t + 1] = c->p.density * accel[t] / 36.f;
+  }
+  // ---- the register tiles need the table on the device: decided here, before anything is queued; no room, or a rank that
+  // would not use the tiles: every rank takes the one-step path (the same bits), nobody fails
+  bool in_kernel = regtile_is_next(c);
+  if (in_kernel)
+    for (auto& s : c->slabs) {
+      if (s.dtab_cap >= nsteps) continue;
+      if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); in_kernel = false; break; }
+      long cap = std::max(1024L, s.dtab_cap);
+      while (cap < nsteps) cap *= 2;
+      if (s.dtab) (void)hipFree(s.dtab);
+      s.dtab = nullptr; s.dtab_cap = 0;
+      if (hipMalloc((void**)&s.dtab, sizeof(float) * 2 * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); s.dtab = nullptr; in_kernel = false; break; }
+      s.dtab_cap = cap;
+    }
+  int rc;
+  if ((rc = ranks_agree(c, LBM_OK, &in_kernel, "the schedule"))) return rc;
+  RunKind k;
+  k.drive = pairs.data(); k.no_tiles = !in_kernel;
+  return run_steps(c, nsteps, av_vels, k);
+}
 
 extern "C" int lbm_last_run_ms(const lbm_ctx* c, double* gpu_ms, double* wall_ms) {
   if (!c) return fail(LBM_EINVAL, "ctx is NULL");
@@ -1183,6 +1249,9 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "probes_in_wave")) { *value = c->probes_in_wave; return LBM_OK; }
   if (!strcmp(key, "window_in_kernel")) { *value = c->window_in_kernel; return LBM_OK; }
   if (!strcmp(key, "window_in_wave")) { *value = c->window_in_wave; return LBM_OK; }
+  if (!strcmp(key, "accel")) { *value = (double)c->p.accel; return LBM_OK; }
+  if (!strcmp(key, "driven_in_kernel")) { *value = c->driven_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "driven_in_wave")) { *value = c->driven_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_wave")) { *value = c->observed_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }
   if (!strcmp(key, "observed_pieces")) { *value = c->observed_pieces; return LBM_OK; }

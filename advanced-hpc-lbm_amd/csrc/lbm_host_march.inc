@@ -567,6 +567,22 @@ wave_fn wave_field_kernel(int K, int C, int flavour) {
   return wave_field_kernel_f<4, 1>(flavour);
 }
 
+// ... and their driven flavour (lbm_run_driven): the lone-lattice forms only, the set the force flavour has
+template <int K, int C>
+wave_fn wave_driven_kernel_f(int flavour) {
+  switch (flavour & 3) {
+    case 0: return lbm::lbm_wave<K, 0, false, C, false, false, false, false, true>;
+    case 1: return lbm::lbm_wave<K, 1, false, C, false, false, false, false, true>;
+    case 2: return lbm::lbm_wave<K, 2, false, C, false, false, false, false, true>;
+    default: return lbm::lbm_wave<K, 3, false, C, false, false, false, false, true>;
+  }
+}
+wave_fn wave_driven_kernel(int K, int C, int flavour) {
+  if (K == 8) return C == 2 ? wave_driven_kernel_f<8, 2>(flavour) : wave_driven_kernel_f<8, 1>(flavour);
+  if (K == 6) return wave_driven_kernel_f<6, 1>(flavour);
+  return wave_driven_kernel_f<4, 1>(flavour);
+}
+
 // ... and their window flavour (lbm_run_window): the lone-lattice forms only, where the field flavour is instantiated
 template <int K, int C>
 wave_fn wave_window_kernel_f(int flavour) {
@@ -697,8 +713,10 @@ struct WaveFields {
 // wp.out (wave_probe_ready said yes): the probe flavour, or the force-and-probe flavour; a group without a sample step
 // runs what it would run without probes.  wf.out (wave_admit said yes; no forces, no probes beside it): the field
 // flavour (wf.win: the window flavour) for a group that holds a sample step, the plain kernel for one that holds none.
+// drv (lbm_run_driven; no observer beside it): the driven flavour -- drv[2 (l - 1)], drv[2 (l - 1) + 1] = the constants level l
+// applies, K pairs.
 int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0, WaveProbes wp = WaveProbes(),
-                WaveFields wf = WaveFields()) {
+                WaveFields wf = WaveFields(), const float* drv = nullptr) {
   Slab& s = c->slabs[0];
   HIPC(hipSetDevice(s.dev));
   const int K = c->time_block;
@@ -727,6 +745,8 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   a.pidx = nullptr; a.pout = nullptr; a.nprobes = 0; a.pmask = 0u; a.prow = 0; a.density = c->p.density;
   a.fmask = 0u; a.fout = nullptr; a.fstride = 0; a.fadd = 0;
   a.win = lbm::WaveWin{0, 0, 0, 1u, 1u, 0u, 0u, 0u, 0u};
+  for (int i = 0; i < 16; ++i) a.drv[i] = (drv && i < 2 * K) ? drv[i] : 0.f;
+  if (drv && (wp.out != nullptr || wf.out != nullptr || nb_bodies > 0)) return fail(LBM_EINVAL, "lbm_wave: the driven flavour runs beside no observer");
   const bool probes = wp.out != nullptr && wp.mask != 0u;
   const bool fields = wf.out != nullptr && wf.mask != 0u;
   if (fields && (wp.out != nullptr || nb_bodies > 0)) return fail(LBM_EINVAL, "lbm_wave: the field flavour runs beside neither forces nor probes");
@@ -736,7 +756,8 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
     hipLaunchKernelGGL(f, dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
     ++c->wave_launches;
   };
-  if (fields) {
+  if (drv) launch(wave_driven_kernel(K, wave_C(c, K), flavour));
+  else if (fields) {
     a.fmask = wf.mask; a.fout = wf.out; a.fstride = wf.stride; a.fadd = wf.add ? 1 : 0;
     if (wf.win) { a.fadd = 0; a.win = *wf.win; launch(wave_window_kernel(K, wave_C(c, K), flavour)); }
     else launch(wave_field_kernel(K, wave_C(c, K), flavour));

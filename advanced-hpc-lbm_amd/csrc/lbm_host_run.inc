@@ -59,6 +59,11 @@ struct RunKind {
   // left-over step that is a sample step, lbm_derive_window into the slot (no sums, wave_fpart / wave_fmass unused).
   bool window = false;
   const struct WinPlan* win = nullptr;
+  // drive (lbm_run_driven): drive[2 t], drive[2 t + 1] = (a1, a2) of the accelerate phase of step t (0-based) of this run, host
+  // memory, in place of the context's pair.  The register tiles run their kRegDrive flavour (the slabs' device tables,
+  // Slab::dtab, have room: the caller asked); off them, a lattice alone that wave_admit said yes to runs its groups of K
+  // steps in lbm_wave's driven flavour; every other step goes through the one-step kernel with its own pair.
+  const float* drive = nullptr;
 };
 
 // The window of one lbm_run_window call: as given (validated), and as lbm_wave's window flavour tests it.
@@ -335,6 +340,7 @@ auto regtile_kernel(int r, bool fast, bool async, int flavour) {
   if (flavour == lbm::kRegForce) return regtile_flavour<SLAB, lbm::kRegForce>(r, fast, async);
   if (flavour == lbm::kRegMean) return regtile_flavour<SLAB, lbm::kRegMean>(r, fast, async);
   if (flavour == lbm::kRegProbe) return regtile_flavour<SLAB, lbm::kRegProbe>(r, fast, async);
+  if (flavour == lbm::kRegDrive) return regtile_flavour<SLAB, lbm::kRegDrive>(r, fast, async);
   if (flavour == (lbm::kRegForce | lbm::kRegProbe)) return regtile_flavour<SLAB, lbm::kRegForce | lbm::kRegProbe>(r, fast, async);
   return regtile_flavour<SLAB, 0>(r, fast, async);
 }
@@ -423,7 +429,8 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
   const bool pk = k.snap && (k.probe || k.window);      // lbm_run_probes, lbm_run_window: the kRegProbe flavour, with its larger LDS
   const bool fpk = k.piece;                             // lbm_run_observed: the kRegForce | kRegProbe flavour (forces counted when fk)
-  const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : 0;
+  const bool dk = k.drive != nullptr;                   // lbm_run_driven: the kRegDrive flavour (the plain flavour's LDS)
+  const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : dk ? lbm::kRegDrive : 0;
   auto kernel = [&](int fl) {
     return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
                 : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
@@ -564,6 +571,12 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
         a.mail_bytes_s = (unsigned)so.tmail_bytes; a.mail_bytes_n = (unsigned)no.tmail_bytes;
       }
       a.nty_s = t.nty; a.nty_n = t.nty;
+      a.drive = nullptr;
+      if (dk) {                       // the schedule, in front of the slab's launch on its stream: 8 bytes per step
+        HIPC(hipSetDevice(s.dev));
+        HIPC(hipMemcpyAsync(s.dtab, k.drive, sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
+        a.drive = s.dtab;
+      }
     }
   static unsigned long long* stats_buf = nullptr;
   constexpr size_t kStatsWords = 1028 + 72;   // [0], [1]: the counts; [1028 ..]: the first wave to give up (lbm_regtile.hip.h, await)
@@ -703,13 +716,16 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (!c->p2p_connected) return fail(LBM_EINVAL, "peer-to-peer halos are not connected (lbm_p2p_connect)");
   const int nx = c->p.nx;
   const float a1 = c->p.density * c->p.accel / 9.f, a2 = c->p.density * c->p.accel / 36.f;
-  const bool pairs = k.nb == 0 && t2_eligible(c) && nsteps >= 2;   // (lbm_run_forces: one step per launch, forces behind each)
+  const bool dr = k.drive != nullptr;                              // lbm_run_driven: one step per launch, each with its own constants
+  auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };      // the accelerate constants of step t (0-based) of this run
+  auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };
+  const bool pairs = k.nb == 0 && !dr && t2_eligible(c) && nsteps >= 2;   // (lbm_run_forces: one step per launch, forces behind each)
   const int ntx = nx / kT2X;
   const int push_grid = cdiv(nx, lbm::kBlock);
   int rc;
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
-  const bool march = k.nb == 0 && p2p_march_on(c) && nsteps >= slab_K(c);
+  const bool march = k.nb == 0 && !dr && p2p_march_on(c) && nsteps >= slab_K(c);
   if (march && (rc = check_march_partials(c, true))) return rc;   // (before anything is queued)
 
   auto push = [&](Slab& s, const float* lat, uint32_t seq, bool do_push) -> int {
@@ -727,7 +743,7 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     HIPC(hipSetDevice(s.dev));
     if (s.accel_row >= 0) {
       hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, s.sc,
-                         s.lat[c->cur], s.plane, s.pitch, nx, s.accel_row, s.blocked, a1, a2);
+                         s.lat[c->cur], s.plane, s.pitch, nx, s.accel_row, s.blocked, da1(0), da2(0));
       HIPC(hipGetLastError());
     }
   }
@@ -835,7 +851,7 @@ int run_p2p(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
       a.plane = s.plane; a.pitch = s.pitch; a.nx = nx; a.nyl = s.nyl;
       a.blocked = s.blocked; a.omega = c->p.omega;
       a.accel_row = last ? -1 : s.accel_row;
-      a.a1 = a1; a.a2 = a2;
+      a.a1 = last ? a1 : da1(tt + 1); a.a2 = last ? a2 : da2(tt + 1);   // (the rows it writes carry the NEXT step's accelerate phase)
       a.partials = s.partials[q];
       const float* gs = s.ghost_s[(seq - 1) & 1] + h3;
       const float* gn = s.ghost_n[(seq - 1) & 1] + h3;

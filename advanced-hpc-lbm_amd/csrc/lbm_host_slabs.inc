@@ -375,6 +375,7 @@ void slab_free(Slab& s) {
   if (s.wslot) (void)hipFree(s.wslot);
   if (s.wwords) (void)hipFree(s.wwords);
   if (s.fpart) (void)hipFree(s.fpart);
+  if (s.dtab) (void)hipFree(s.dtab);
   if (s.sums && !s.sums_direct) (void)hipFree(s.sums);
   if (s.sums_host) (void)hipHostFree(s.sums_host);
   if (s.err_host) (void)hipHostFree(s.err_host);

@@ -59,6 +59,8 @@ constexpr int kRegMean = 65536;   // lbm_regtile: time-averaged fields summed du
                                   // kRegSnap: three sums per cell in LDS, one in a register, one 16-byte store per cell after the last step
 constexpr int kRegProbe = 131072; // lbm_regtile: per-step time series at chosen cells (lbm_run_probes).  A flavour of its own, like
                                   // kRegSnap: one word per cell in LDS, on a sample step one 16-byte store per PROBE and nothing else
+constexpr int kRegDrive = 262144; // lbm_regtile: a per-step acceleration schedule (lbm_run_driven).  A flavour of its own, like kRegSnap: the
+                                  // waves that hold the accelerate row read each step's constants from a table, by a scalar load
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
 // Per-step forces of a whole-run launch with kRegForce: partials[step][slot][8] (8 = four labels x two components, the
@@ -143,6 +145,11 @@ struct RegTileArgs {
   // At the END, so that every member above keeps its place.
   int pfirst;
   const int* pslot; const uint32_t* pwords;
+  // ---- a schedule (lbm_run_driven, flavour kRegDrive only): drive[s][2] = (a1, a2) of the accelerate phase of step s + 1 of
+  // the run, s = 0 .. nsteps - 1, made on the host as a1 and a2 above are; entry 0 is the prologue's, entry s what the rows
+  // written in step s carry (the last step writes none); a1, a2 unused.  Device memory, read through the constant address
+  // space by the waves that hold the accelerate row.  At the END, so that every member above keeps its place.
+  const float* drive;
 };
 
 // LDS bytes of a block of nw waves with r rows per wave (see the kernel)
@@ -189,6 +196,8 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool FORCE = (MODE & kRegForce) != 0;
   constexpr bool MEAN = (MODE & kRegMean) != 0;
   constexpr bool PROBE = (MODE & kRegProbe) != 0;
+  constexpr bool DRIVE = (MODE & kRegDrive) != 0;
+  static_assert(!(DRIVE && (SNAP || FORCE || MEAN || PROBE)), "the schedule is a flavour of its own");
   static_assert(!(MEAN && (SNAP || FORCE)) && !(PROBE && (SNAP || MEAN)), "one flavour per launch, or forces with probes");
   // The mail of the loop issued and waited for BY HAND (R > 1): see "the asynchronous loop" below
   constexpr bool ASYNC = (MODE & kRegAsync) != 0 && R > 1;
@@ -251,6 +260,17 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   const int rho0 = w * R;                                   // tile row of this wave's first row
   const int gx = bx * 64 + lane, gy0 = by * TY + rho0;
   if (tid == 0) *lds_abort = 0u;
+  // the accelerate constants of the rows written in step s (s = 0: the prologue): the kernel's arguments, or (DRIVE) entry s
+  // of the schedule -- a wave-uniform address in the constant address space: ONE scalar load (s_load_dwordx2, counted in
+  // lgkmcnt, not in vmcnt: the counted vmcnt waits of the asynchronous loop see exactly the operations they see without
+  // it), asked for only by the waves that hold the accelerate row, behind the wave-uniform test the loop makes anyway
+  auto accel_consts = [&](int s, float& a1, float& a2) {
+    if constexpr (DRIVE) {
+      typedef const __attribute__((address_space(4))) float* cfloats_t;
+      const cfloats_t t = (cfloats_t)(unsigned long long)a.drive + 2 * (long)s;
+      a1 = t[0]; a2 = t[1];
+    } else { a1 = a.a1; a2 = a.a2; }
+  };
   if constexpr (SNAP || MEAN || PROBE) {
     if (tid == 0) { lds_snap[1] = MEAN ? (long long)a.nx : a.snap_stride; lds_snap[2] = (long long)(unsigned)a.every | ((long long)__float_as_uint(a.density) << 32); }
     if (lane == 0) lds_snap_at[w] = (long long)a.snap;
@@ -536,7 +556,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
     float q[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) q[k] = q0[r][k];
-    if (gy0 + r == a.accel_row) accelerate_cell(q, blk[r], a.a1, a.a2);   // accelerate phase of the first step
+    if (gy0 + r == a.accel_row) { if constexpr (DRIVE) { float a1, a2; accel_consts(0, a1, a2); accelerate_cell(q, blk[r], a1, a2); } else accelerate_cell(q, blk[r], a.a1, a.a2); }   // accelerate phase of the first step
     f[r][2] = q[2]; f[r][4] = q[4]; f[r][5] = q[5]; f[r][6] = q[6]; f[r][7] = q[7]; f[r][8] = q[8];
     if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = q[0]; own[(r * 3 + 1) * 64] = q[1]; own[(r * 3 + 2) * 64] = q[3]; }
     else { f[r][0] = q[0]; f[r][1] = q[1]; f[r][3] = q[3]; }
@@ -754,7 +774,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
           // forces (a row with a labelled cell only): LDS and DPP work and lane 0's LDS add, no vector-memory operation --
           // the counted vmcnt waits see exactly the operations they see without it
           if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
-          if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
+          if (gy0 + r == a.accel_row && !laststep) { if constexpr (DRIVE) { float a1, a2; accel_consts(s, a1, a2); accelerate_cell(p, blk[r], a1, a2); } else accelerate_cell(p, blk[r], a.a1, a.a2); }
           f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
           if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = p[0]; own[(r * 3 + 1) * 64] = p[1]; own[(r * 3 + 2) * 64] = p[3]; }
           else { f[r][0] = p[0]; f[r][1] = p[1]; f[r][3] = p[3]; }
@@ -902,7 +922,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
         else snap_row(r, p, blk[r]);
       }
       if constexpr (FORCE) { const uint32_t lb = (frow >> (4 * r)) & 15u; if (lb != 0u) force_row(r, p, lb, s); }
-      if (gy0 + r == a.accel_row && !laststep) accelerate_cell(p, blk[r], a.a1, a.a2);
+      if (gy0 + r == a.accel_row && !laststep) { if constexpr (DRIVE) { float a1, a2; accel_consts(s, a1, a2); accelerate_cell(p, blk[r], a1, a2); } else accelerate_cell(p, blk[r], a.a1, a.a2); }
       f[r][2] = p[2]; f[r][4] = p[4]; f[r][5] = p[5]; f[r][6] = p[6]; f[r][7] = p[7]; f[r][8] = p[8];
       if constexpr (OWN_LDS) { own[(r * 3 + 0) * 64] = p[0]; own[(r * 3 + 1) * 64] = p[1]; own[(r * 3 + 2) * 64] = p[3]; }
       else { f[r][0] = p[0]; f[r][1] = p[1]; f[r][3] = p[3]; }

@@ -90,6 +90,10 @@ struct WaveArgs {
   // output is the window, [win.ny][win.nx][4], and only the window's cells are derived and stored (appended: every earlier
   // member keeps its offset)
   WaveWin win;
+  // ---- the driven flavour (DRIVEN; a lattice alone, lbm_run_driven): drv[2 (l - 1)], drv[2 (l - 1) + 1] = (a1, a2) of the
+  // accelerate phase that level l applies -- that of step t + l + 1 -- made on the host as a1 and a2 are; a1, a2 unused; level
+  // K's pair is read only under accel_out (appended: every earlier member keeps its offset)
+  float drv[16];
 };
 
 constexpr int kWaveBlock = 256;   // four independent waves per block (they only meet for the final sums)
@@ -145,7 +149,12 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // lane of ONE wave owns a cell at every level of a pass; it reaches levels l and l + 1 of a row in consecutive iterations,
 // in program order; so the adds of one pass into a cell's sums are same-thread accesses to one address (plain loads and
 // stores, not the nontemporal helpers), and the adds of different passes are ordered by the stream.
-template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false, bool WINDOW = false>
+// DRIVEN (lbm_run_driven where lbm_wave runs; a lattice alone, a flavour of its own): level l takes its accelerate constants from
+// the pass's K pairs in the kernel's arguments (scalar registers, the level is a compile-time constant of the unrolled loop)
+// where every other flavour takes a1, a2; both images of the accelerate row that a chunk's fill rows may pass within a level
+// take that level's pair.  Nothing else differs from the plain kernel.
+template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false, bool WINDOW = false,
+          bool DRIVEN = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
 void lbm_wave(const WaveArgs a) {
   constexpr bool FAST = (MODE & kFastMath) != 0, NTS = (MODE & kNtStore) != 0, NTL = (MODE & kNtLoad) != 0;
@@ -156,6 +165,8 @@ void lbm_wave(const WaveArgs a) {
   static_assert(!(PROBE && SLAB), "the probe flavours are for a lattice alone");
   static_assert(!(FIELD && (SLAB || FORCE || PROBE)), "the field flavour is for a lattice alone, and a flavour of its own");
   static_assert(!(WINDOW && (SLAB || FORCE || PROBE || FIELD)), "the window flavour is for a lattice alone, and a flavour of its own");
+  static_assert(!(DRIVEN && (SLAB || FORCE || PROBE || FIELD || WINDOW)), "the driven flavour is for a lattice alone, and a flavour of its own");
+  static_assert(!DRIVEN || K <= 8, "K pairs of constants in the arguments");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -374,6 +385,7 @@ void lbm_wave(const WaveArgs a) {
           // to the west: one whole-wave DPP shift; likewise to the east.
           const bool acc = ((j - l == jacc) || (j - l == jacc2) || (SLAB && j - l == jacc3)) && (l < K || a.accel_out != 0);
           const bool own_row = (j - l >= K) && (j - l < K + hy);
+          const float la1 = DRIVEN ? a.drv[2 * (l - 1)] : a.a1, la2 = DRIVEN ? a.drv[2 * (l - 1) + 1] : a.a2;
 #pragma unroll
           for (int c = 0; c < C; ++c) {
             const int cw = (c == 0) ? C - 1 : c - 1, ce = (c == C - 1) ? 0 : c + 1;
@@ -400,7 +412,7 @@ void lbm_wave(const WaveArgs a) {
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
             if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
-            if (acc) accelerate_cell(p[0], blk, a.a1, a.a2);
+            if (acc) accelerate_cell(p[0], blk, la1, la2);
             sum[l - 1] += (out_ok && own_row) ? sp : 0.f;
           } else {
             bool blk[C];
@@ -413,7 +425,7 @@ void lbm_wave(const WaveArgs a) {
             if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
 #pragma unroll
             for (int c = 0; c < C; ++c)
-              if (acc) accelerate_cell(p[c], blk[c], a.a1, a.a2);
+              if (acc) accelerate_cell(p[c], blk[c], la1, la2);
             // (the K sums stay in registers: as lane-private LDS words -- read, add, write per level -- they cost the two-column
             // kernel 12 % at K = 8 and 18 % at K = 6, more than the eight dwords the K = 8 loop spills without them)
 #pragma unroll

@@ -376,6 +376,51 @@ int lbm_run_window(lbm_ctx* ctx, int nsteps, float* av_vels, int every, const lb
    *first .. *first + *count - 1 of the window (*count may be 0; first and count may be NULL). */
 int lbm_window_rows(const lbm_window* win, int nx, int ny, int row_begin, int row_end, int* first, int* count);
 
+/*
+ * The acceleration as an input of the run (a ramp over the first thousand steps instead of an impulsive start, a pulsatile
+ * or oscillatory channel, a loop closed on av_vels) -- the one parameter of a context that is not frozen at lbm_create.
+ */
+/* Replaces the context's acceleration for every later run (lbm_run and all lbm_run_* calls).  Only stores the value: queues
+   nothing, rebuilds no table, changes no engine choice (every run makes its accelerate constants from the context's
+   parameters when it starts).  Info "accel" reads it.  Rank contexts: the caller sets the same value on every rank.
+   LBM_EINVAL: NULL ctx, or a non-finite value (the old value is kept). */
+int lbm_set_accel(lbm_ctx* ctx, float accel);
+/* lbm_run with step t (0-based within the call) driven by accel[t] instead of the context's value.
+   Definition: step t of the call is the reference's step (accelerate, stream, bounce-back, collide; d2q9-bgk.c:228-1813)
+   with params.accel = accel[t].  The two accelerate constants of a step are made on the host, in float, by the expression
+   every run uses: density * accel[t] / 9.f and density * accel[t] / 36.f -- a schedule whose every entry equals the
+   context's acceleration is therefore lbm_run, constant for constant.  Any finite value is legal, of either sign, and zero:
+   what the accelerate guard (d2q9-bgk.c:238-241) does with it is what the reference's statements do with that value;
+   nothing is special-cased.  accel: host memory, float[nsteps].
+   The lattice and everything after the call are bit-identical to
+       for (t = 0; t < nsteps; ++t) { lbm_set_accel(ctx, accel[t]); lbm_run(ctx, 1, ...); }
+   from the same state with the same options, on every engine -- except that the context's own acceleration is untouched
+   by lbm_run_driven.  av_vels: the engine's own per-step sums; equal to that loop's within float rounding of the per-step
+   sum; with a constant schedule equal to the context's acceleration bit-identical to lbm_run's wherever the register tiles
+   ran, and in lbm_wave for the steps inside full passes.
+   Which kernels take the schedule:
+   - The register-tile engines, alone and across slabs, run a flavour of their own (info "driven_in_kernel" = 1): the
+     (a1, a2) pairs go to the device before the launch (8 bytes per step), and the waves that hold the accelerate row read a
+     step's pair with one scalar load.  If the flavour cannot be resident, the table has no room or the run gives up (lattice
+     untouched), the one-step path below runs the same schedule.
+   - Where lbm_wave runs (a lattice alone on its GPU with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block),
+     a driven flavour of lbm_wave takes the K pairs of a pass in its arguments (info "driven_in_wave" = 1,
+     "driven_in_kernel" = 0; "wave_launches" grows by one per pass); the steps left over behind the last full pass go one
+     at a time through the one-step kernel, each with its own constants.
+   - Every other engine -- contexts where lbm_march or lbm_sweep2 would run, slabs with neighbours under copy / RCCL /
+     streaming peer-to-peer, rank contexts off the register tiles, runs shorter than time_block, a register-tile run that
+     gave up -- runs the one-step kernel, each step with its own constants (correct, not fast; the same lattice bits; both
+     keys read 0).
+   Rank contexts: every rank passes the same schedule and gets the global av_vels, as with lbm_run; the ranks agree on the
+   path before anything is queued.
+   LBM_EINVAL with nothing queued and the lattice untouched: NULL ctx; nsteps < 0; accel NULL with nsteps > 0; a non-finite
+   entry (the message names its index).  LBM_ENOMEM likewise when the device table does not fit and no path with the same
+   bits is left (the one-step path needs no table).  nsteps = 0: success, nothing runs.
+   Not offered: a schedule inside lbm_run_observed or the single observer calls (piecewise-constant forcing with observers
+   is lbm_set_accel between calls); schedules for omega or density; a schedule from the command-line tool; device-memory
+   schedules. */
+int lbm_run_driven(lbm_ctx* ctx, int nsteps, float* av_vels, const float* accel);
+
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
 int lbm_last_run_ms(const lbm_ctx* ctx, double* gpu_ms, double* wall_ms);
@@ -441,7 +486,9 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches),
  * "window_in_kernel" (1: the last lbm_run_window took its window inside the register tiles),
  * "window_in_wave" (1: the last lbm_run_window took its window inside lbm_wave launches), "observed_in_kernel",
- * "observed_in_wave", "observed_pieces" (lbm_run_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * "observed_in_wave", "observed_pieces" (lbm_run_observed), "accel" (the context's acceleration: lbm_create's, or the last lbm_set_accel's),
+ * "driven_in_kernel" (1: the last lbm_run_driven ran inside the register tiles), "driven_in_wave" (1: the last lbm_run_driven
+ * ran its groups of K steps inside lbm_wave launches), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */
