@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
     "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows",
-    "lbm_set_accel", "lbm_run_driven",
+    "lbm_set_accel", "lbm_run_driven", "lbm_run_driven_observed",
     "lbm_last_run_ms", "lbm_read_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
@@ -119,6 +119,7 @@ def load_library():
     lib.lbm_window_rows.argtypes = [C.POINTER(Window), C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
     lib.lbm_set_accel.argtypes = [vp, C.c_float]
     lib.lbm_run_driven.argtypes = [vp, C.c_int, vp, vp]
+    lib.lbm_run_driven_observed.argtypes = [vp, C.c_int, vp, vp, C.POINTER(Observe)]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
@@ -375,7 +376,33 @@ class Lattice:
         contiguous float32 CUDA tensors given as probes_out / mean_out / fields_out, filled on the GPU.  Where lbm_wave
         runs, forces and probes ride together in its launches and cut no piece (info("observed_in_wave"): bits 1 forces,
         2 probes; info("observed_in_kernel") means the register tiles and reads 0 there)."""
-        n = max(nsteps, 0)
+        av, res, what = self._observe(max(nsteps, 0), forces, probes_every, mean_every, fields_every, probes_out, mean_out, fields_out)
+        _check(self._lib.lbm_run_observed(self._ctx, nsteps, av.ctypes.data if av.size else None, C.byref(what)))
+        return res
+
+    def run_driven_observed(self, accel, forces: bool = False, probes_every: int = 0, mean_every: int = 0,
+                            fields_every: int = 0, probes_out=None, mean_out=None, fields_out=None):
+        """run_driven that also observes (lbm_run_driven_observed): step t is driven by accel[t], nsteps = len(accel), and
+        the keyword arguments and the returned dict are run_observed's.  No observer wanted: exactly run_driven.  One
+        observer alone is legal.  Probes, means and snapshots are bit for bit what their definitions give from the lattices
+        of `for a in accel: set_accel(a); run(1)`; the context's own acceleration is untouched.  The register tiles run
+        every piece in one flavour that reads the schedule from a device table (info("driven_observed_in_kernel"): bits
+        1 forces, 2 probes); where lbm_wave runs, forces and probes ride in its launches with the K pairs of a pass
+        (info("driven_observed_in_wave")); info("driven_observed_pieces") counts the step-loop pieces."""
+        arr = np.asarray(accel)
+        if arr.ndim != 1:
+            raise LbmError(f"accel must be one-dimensional (one value per step), got shape {arr.shape}")
+        if arr.dtype.kind not in "fiu":
+            raise LbmError(f"accel must hold real numbers, got dtype {arr.dtype}")
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        av, res, what = self._observe(arr.size, forces, probes_every, mean_every, fields_every, probes_out, mean_out, fields_out)
+        _check(self._lib.lbm_run_driven_observed(self._ctx, arr.size, av.ctypes.data if av.size else None,
+                                                 arr.ctypes.data if arr.size else None, C.byref(what)))
+        return res
+
+    def _observe(self, n, forces, probes_every, mean_every, fields_every, probes_out, mean_out, fields_out):
+        """The outputs of one run_observed / run_driven_observed call of n steps: (av_vels, the dict to return, the
+        lbm_observe that names them)."""
         av = np.empty(n, dtype=np.float32)
         res = {"av_vels": av}
         what = Observe()
@@ -398,8 +425,7 @@ class Lattice:
             res["fields"], ptr = self._output(fields_out, shape, "fields_out")
             what.fields_out = ptr if ptr is not None else av.ctypes.data
             what.fields_every = fields_every
-        _check(self._lib.lbm_run_observed(self._ctx, nsteps, av.ctypes.data if n else None, C.byref(what)))
-        return res
+        return av, res, what
 
     def last_run_ms(self):
         g, w = C.c_double(0), C.c_double(0)

@@ -280,6 +280,9 @@ struct lbm_ctx {
   int window_in_wave = 0;      // 1: the last lbm_run_window took its window inside lbm_wave launches
   int driven_in_kernel = 0;    // 1: the last lbm_run_driven ran inside the register tiles (their kRegDrive flavour)
   int driven_in_wave = 0;      // 1: the last lbm_run_driven ran its groups of K steps inside lbm_wave launches (the driven flavour)
+  int driven_observed_in_kernel = 0;  // the last lbm_run_driven_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
+  int driven_observed_in_wave = 0;    // ... bits 1 forces, 2 probes taken inside lbm_wave launches
+  int driven_observed_pieces = 0;     // ... and the step-loop pieces it ran
   int observed_in_wave = 0;    // the last lbm_run_observed: bits 1 forces, 2 probes taken inside lbm_wave launches
   int observed_in_kernel = 0;  // the last lbm_run_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
   int observed_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
@@ -695,6 +698,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
                               // run it (fwave, below); else the one-step kernel, lbm_body_forces behind each step
   const bool dr = k.drive != nullptr;   // lbm_run_driven: the register tiles in their kRegDrive flavour; lbm_wave in its driven flavour on a
                                         // lattice alone (dwave, below); else the one-step kernel, each step with its own constants
+                                        // (with forces or probes beside it, lbm_run_driven_observed: the driven force-and-probe flavours)
   auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };   // the accelerate constants of step t (0-based) of this run
   auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };
   if (!k.no_tiles && (!fo || k.force_tiles) && regtile_is_next(c)) {
@@ -748,6 +752,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   const bool fw = k.wave_fout != nullptr;
   // (the field flavour is a flavour of its own: refused before anything is queued, launch_wave would refuse it mid-run)
   if (fw && (pw || fo)) return fail(LBM_EINVAL, "run_steps: fields inside lbm_wave run beside neither probes nor forces");
+  if (fw && dr) return fail(LBM_EINVAL, "run_steps: fields inside lbm_wave run under no schedule");
   auto fsample = [&](int s) { return fw && s % k.wave_fevery == 0; };
   auto fslot = [&](int s) { return k.wave_fout + (size_t)(s / k.wave_fevery - 1) * (size_t)k.wave_fstride; };
   // ... a left-over step that is a sample step: the probes' cells of the lattice just stored (stored WITHOUT the next step's
@@ -769,7 +774,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     }
     if (then_accelerate && sl.accel_row >= 0) {
       hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, sl.sc,
-                         sl.lat[c->cur], sl.plane, sl.pitch, nx, sl.accel_row, sl.blocked, a1, a2);
+                         sl.lat[c->cur], sl.plane, sl.pitch, nx, sl.accel_row, sl.blocked, da1(s), da2(s));   // (step s + 1's phase: entry s)
       HIPC(hipGetLastError());
     }
     return LBM_OK;
@@ -987,16 +992,8 @@ extern "C" int lbm_run_driven(lbm_ctx* c, int nsteps, float* av_vels, const floa
   // would not use the tiles: every rank takes the one-step path (the same bits), nobody fails
   bool in_kernel = regtile_is_next(c);
   if (in_kernel)
-    for (auto& s : c->slabs) {
-      if (s.dtab_cap >= nsteps) continue;
-      if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); in_kernel = false; break; }
-      long cap = std::max(1024L, s.dtab_cap);
-      while (cap < nsteps) cap *= 2;
-      if (s.dtab) (void)hipFree(s.dtab);
-      s.dtab = nullptr; s.dtab_cap = 0;
-      if (hipMalloc((void**)&s.dtab, sizeof(float) * 2 * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); s.dtab = nullptr; in_kernel = false; break; }
-      s.dtab_cap = cap;
-    }
+    for (auto& s : c->slabs)
+      if (!drive_table_room(s, nsteps)) { in_kernel = false; break; }
   int rc;
   if ((rc = ranks_agree(c, LBM_OK, &in_kernel, "the schedule"))) return rc;
   RunKind k;
@@ -1252,6 +1249,9 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "accel")) { *value = (double)c->p.accel; return LBM_OK; }
   if (!strcmp(key, "driven_in_kernel")) { *value = c->driven_in_kernel; return LBM_OK; }
   if (!strcmp(key, "driven_in_wave")) { *value = c->driven_in_wave; return LBM_OK; }
+  if (!strcmp(key, "driven_observed_in_kernel")) { *value = c->driven_observed_in_kernel; return LBM_OK; }
+  if (!strcmp(key, "driven_observed_in_wave")) { *value = c->driven_observed_in_wave; return LBM_OK; }
+  if (!strcmp(key, "driven_observed_pieces")) { *value = c->driven_observed_pieces; return LBM_OK; }
   if (!strcmp(key, "observed_in_wave")) { *value = c->observed_in_wave; return LBM_OK; }
   if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }
   if (!strcmp(key, "observed_pieces")) { *value = c->observed_pieces; return LBM_OK; }

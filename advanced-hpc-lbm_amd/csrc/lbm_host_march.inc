@@ -583,6 +583,22 @@ wave_fn wave_driven_kernel(int K, int C, int flavour) {
   return wave_driven_kernel_f<4, 1>(flavour);
 }
 
+// ... and the driven force-and-probe flavour (lbm_run_driven_observed): the same set
+template <int K, int C>
+wave_fn wave_driven_observed_kernel_f(int flavour) {
+  switch (flavour & 3) {
+    case 0: return lbm::lbm_wave<K, 0, false, C, true, true, false, false, true>;
+    case 1: return lbm::lbm_wave<K, 1, false, C, true, true, false, false, true>;
+    case 2: return lbm::lbm_wave<K, 2, false, C, true, true, false, false, true>;
+    default: return lbm::lbm_wave<K, 3, false, C, true, true, false, false, true>;
+  }
+}
+wave_fn wave_driven_observed_kernel(int K, int C, int flavour) {
+  if (K == 8) return C == 2 ? wave_driven_observed_kernel_f<8, 2>(flavour) : wave_driven_observed_kernel_f<8, 1>(flavour);
+  if (K == 6) return wave_driven_observed_kernel_f<6, 1>(flavour);
+  return wave_driven_observed_kernel_f<4, 1>(flavour);
+}
+
 // ... and their window flavour (lbm_run_window): the lone-lattice forms only, where the field flavour is instantiated
 template <int K, int C>
 wave_fn wave_window_kernel_f(int flavour) {
@@ -713,8 +729,10 @@ struct WaveFields {
 // wp.out (wave_probe_ready said yes): the probe flavour, or the force-and-probe flavour; a group without a sample step
 // runs what it would run without probes.  wf.out (wave_admit said yes; no forces, no probes beside it): the field
 // flavour (wf.win: the window flavour) for a group that holds a sample step, the plain kernel for one that holds none.
-// drv (lbm_run_driven; no observer beside it): the driven flavour -- drv[2 (l - 1)], drv[2 (l - 1) + 1] = the constants level l
-// applies, K pairs.
+// drv (lbm_run_driven): the driven flavour -- drv[2 (l - 1)], drv[2 (l - 1) + 1] = the constants level l applies, K pairs.
+// drv beside forces (nb_bodies > 0) or probes (wp.out; lbm_run_driven_observed): EVERY group runs the driven force-and-probe
+// flavour, a sample step in it or not, on the map that marks what is wanted (an observer that is not wanted: nothing marked).
+// drv beside fields: refused (run_steps refuses it before anything is queued).
 int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0, WaveProbes wp = WaveProbes(),
                 WaveFields wf = WaveFields(), const float* drv = nullptr) {
   Slab& s = c->slabs[0];
@@ -746,7 +764,7 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   a.fmask = 0u; a.fout = nullptr; a.fstride = 0; a.fadd = 0;
   a.win = lbm::WaveWin{0, 0, 0, 1u, 1u, 0u, 0u, 0u, 0u};
   for (int i = 0; i < 16; ++i) a.drv[i] = (drv && i < 2 * K) ? drv[i] : 0.f;
-  if (drv && (wp.out != nullptr || wf.out != nullptr || nb_bodies > 0)) return fail(LBM_EINVAL, "lbm_wave: the driven flavour runs beside no observer");
+  if (drv && wf.out != nullptr) return fail(LBM_EINVAL, "lbm_wave: the driven flavour runs beside no fields");
   const bool probes = wp.out != nullptr && wp.mask != 0u;
   const bool fields = wf.out != nullptr && wf.mask != 0u;
   if (fields && (wp.out != nullptr || nb_bodies > 0)) return fail(LBM_EINVAL, "lbm_wave: the field flavour runs beside neither forces nor probes");
@@ -756,7 +774,12 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
     hipLaunchKernelGGL(f, dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
     ++c->wave_launches;
   };
-  if (drv) launch(wave_driven_kernel(K, wave_C(c, K), flavour));
+  if (drv && (nb_bodies > 0 || wp.out != nullptr)) {
+    const bool counted = nb_bodies > 0 && s.fcells_n > 0;
+    a.blocked = wp.out != nullptr ? (counted ? s.fpmap : s.pmap) : (counted ? s.fmap : s.blocked);
+    if (counted) { a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n; }
+    launch(wave_driven_observed_kernel(K, wave_C(c, K), flavour));
+  } else if (drv) launch(wave_driven_kernel(K, wave_C(c, K), flavour));
   else if (fields) {
     a.fmask = wf.mask; a.fout = wf.out; a.fstride = wf.stride; a.fadd = wf.add ? 1 : 0;
     if (wf.win) { a.fadd = 0; a.win = *wf.win; launch(wave_window_kernel(K, wave_C(c, K), flavour)); }

@@ -279,6 +279,20 @@ int observed_no_force_table(Slab& s, int ntiles) {
   return LBM_OK;
 }
 
+// room on a slab's device for the (a1, a2) pairs of a schedule of nsteps steps (Slab::dtab; lbm_run_driven and
+// lbm_run_driven_observed on the register tiles).  false: no room, nothing queued -- the caller keeps off the tiles
+bool drive_table_room(Slab& s, int nsteps) {
+  if (s.dtab_cap >= nsteps) return true;
+  if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+  long cap = std::max(1024L, s.dtab_cap);
+  while (cap < nsteps) cap *= 2;
+  if (s.dtab) (void)hipFree(s.dtab);
+  s.dtab = nullptr; s.dtab_cap = 0;
+  if (hipMalloc((void**)&s.dtab, sizeof(float) * 2 * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); s.dtab = nullptr; return false; }
+  s.dtab_cap = cap;
+  return true;
+}
+
 }  // namespace
 
 extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every, float* fields_out) {
@@ -837,9 +851,19 @@ static_assert(sizeof(lbm_observe) == 48 && offsetof(lbm_observe, forces) == 0 &&
               offsetof(lbm_observe, mean_out) == 16 && offsetof(lbm_observe, fields_out) == 24 && offsetof(lbm_observe, probes_every) == 32 &&
               offsetof(lbm_observe, mean_every) == 36 && offsetof(lbm_observe, fields_every) == 40, "the layout lbm_mi355x.h states");
 
-extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observe* what) {
-  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
-  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+// lbm_run_observed and lbm_run_driven_observed (driven; accel: the schedule, float[nsteps] of host memory, checked by the
+// caller): one body, one copy of the cutting logic.  Under a schedule (DESIGN.md 3.17):
+//   - every piece is handed its part of the schedule: RunKind::drive is the host table of (a1, a2) pairs advanced by `done`
+//     pairs; the register tiles run kRegForce | kRegProbe | kRegDrive on the device table (Slab::dtab: the whole call's,
+//     uploaded once in front of the first piece; RunKind::drive_at = done);
+//   - there are no driven single calls: one observer alone goes through the pieces too (none wanted: lbm_run_driven itself);
+//   - forces ride in lbm_wave launches where run_steps finds both the force and the driven flavour admitted, probes where
+//     wave_probes_admit says yes -- one flavour with all three, an observer that is not wanted marks nothing in its map;
+//   - the keys are "driven_observed_in_kernel", "driven_observed_in_wave", "driven_observed_pieces".
+static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observe* what, bool driven, const float* accel) {
+  int& key_kernel = driven ? c->driven_observed_in_kernel : c->observed_in_kernel;
+  int& key_wave = driven ? c->driven_observed_in_wave : c->observed_in_wave;
+  int& key_pieces = driven ? c->driven_observed_pieces : c->observed_pieces;
   const bool wf = what && what->forces, wp = what && what->probes_out, wm = what && what->mean_out;
   bool ws = what && what->fields_out;
   const int pe = wp ? what->probes_every : 0, me = wm ? what->mean_every : 0, se = ws ? what->fields_every : 0;
@@ -861,11 +885,17 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   if (wp && (rc = po.locate(what->probes_out, "probes_out"))) return rc;
   if (wm && (rc = mo.locate(what->mean_out, "mean_out"))) return rc;
   if (ws && (rc = output_on_device(c, what->fields_out, "fields_out", &s_dev))) return rc;
-  c->observed_in_kernel = 0; c->observed_in_wave = 0; c->observed_pieces = 0;
+  key_kernel = 0; key_wave = 0; key_pieces = 0;
   if (wf) c->forces_in_wave = 0;                          // (set by any piece whose forces rode in lbm_wave launches)
-  // ---- none, or one alone: the call itself
+  // ---- none, or one alone: the call itself (under a schedule: none is lbm_run_driven, one alone goes through the pieces)
   const int wanted = (wf ? 1 : 0) + (wp ? 1 : 0) + (wm ? 1 : 0) + (ws ? 1 : 0);
-  if (wanted <= 1) {
+  if (driven && nsteps == 0) return run_steps(c, 0, av_vels);   // (success, nothing runs)
+  if (driven && wanted == 0) {
+    const int r = lbm_run_driven(c, nsteps, av_vels, accel);
+    if (!r && nsteps > 0 && (c->driven_in_kernel || c->driven_in_wave)) key_pieces = 1;
+    return r;
+  }
+  if (!driven && wanted <= 1) {
     if (wf) { rc = lbm_run_forces(c, nsteps, av_vels, what->forces); if (!rc && c->forces_in_kernel) c->observed_in_kernel = 1; if (!rc && c->forces_in_wave) c->observed_in_wave = 1; }
     else if (wp) { rc = lbm_run_probes(c, nsteps, av_vels, pe, what->probes_out); if (!rc && c->probes_in_kernel) c->observed_in_kernel = 2; if (!rc && c->probes_in_wave) c->observed_in_wave = 2; }
     else if (wm) { rc = lbm_run_mean(c, nsteps, av_vels, me, what->mean_out); if (!rc && c->mean_in_kernel) c->observed_in_kernel = 4; }
@@ -903,7 +933,24 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   }
   if (!rc && wp) rc = po.prepare(mp);
   if (!rc && wm) rc = mo.prepare();
+  // the schedule: the pairs made on the host by run_steps' own expression, as lbm_run_driven makes them; room for the whole
+  // call's table on every slab's device where the tiles would run -- no room: the call keeps off the tiles, nobody fails
+  std::vector<float> pairs;
+  if (driven) {
+    pairs.resize(2 * (size_t)nsteps);
+    for (int t = 0; t < nsteps; ++t) {
+      pairs[2 * (size_t)t] = c->p.density * accel[t] / 9.f;          // d2q9-bgk.c:230-231
+      pairs[2 * (size_t)t + 1] = c->p.density * accel[t] / 36.f;
+    }
+    for (size_t i = 0; i < ns && !rc && tiles; ++i)
+      if (!drive_table_room(c->slabs[i], nsteps)) tiles = false;
+  }
   if ((rc = ranks_agree(c, rc, &tiles, "the observers' buffers"))) return rc;
+  if (driven && tiles)
+    for (auto& s : c->slabs) {
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemcpyAsync(s.dtab, pairs.data(), sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
+    }
   // probes where lbm_run would run lbm_wave (a lattice alone): they ride in its launches, beside the forces if those are
   // wanted, and cut no piece; decided here, before anything is queued (no: lbm_probe_gather behind pieces cut at their steps)
   const bool pwave = wp && !rc && !tiles && wave_probes_admit(c, wf);
@@ -913,6 +960,7 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
   // ---- the pieces
   double gpu_ms = 0.0, wall_ms = 0.0;
   int done = 0, pieces = 0, bits = 0, jsnap = 0;
+  bool in_launches = false;                               // (under a schedule) a piece ran on the tiles, or its groups of K steps in lbm_wave
   while (done < nsteps) {
     const bool on_tiles = tiles && regtile_is_next(c);
     int next = nsteps;
@@ -925,6 +973,7 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     float* av = av_vels ? av_vels + done : nullptr;
     RunKind k;
     if (wf) { k.nb = nb; k.nval = nval; k.force_tiles = on_tiles; }
+    if (driven) { k.drive = pairs.data() + 2 * (size_t)done; k.drive_at = done; }
     if (on_tiles) {
       SnapPlan sp;
       sp.every = pe;
@@ -935,6 +984,7 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
       if ((rc = run_steps(c, n, av, k))) return rc;
       if (!ran) { tiles = false; continue; }              // (nothing stepped: this piece again, off the tiles)
       bits |= (wf ? 1 : 0) | (wp ? 2 : 0);
+      in_launches = true;
     } else {
       k.no_tiles = true;
       if (pwave) {
@@ -942,7 +992,9 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
         k.wave_pevery = pe; k.pfirst = pe - done % pe; k.wave_pout = po.at(0, jp);
         c->probes_in_wave = 0;
       }
+      if (driven) c->driven_in_wave = 0;
       if ((rc = run_steps(c, n, av, k))) return rc;
+      if (driven && c->driven_in_wave) in_launches = true;
       if (pwave && c->probes_in_wave) wbits |= 2;
       if (wf && c->forces_in_wave) wbits |= 1;
       if (wp && !pwave && (done + n) % pe == 0 && (rc = po.gather(jp))) return rc;
@@ -966,6 +1018,22 @@ extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lb
     }
   if (wp && (rc = po.to_host())) return rc;
   c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
-  c->observed_in_kernel = bits; c->observed_in_wave = wbits; c->observed_pieces = pieces;
+  // (under a schedule the three keys read 0 where the whole call took the one-step path)
+  key_kernel = bits; key_wave = wbits; key_pieces = (!driven || in_launches) ? pieces : 0;
   return LBM_OK;
+}
+
+extern "C" int lbm_run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observe* what) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  return run_observed(c, nsteps, av_vels, what, false, nullptr);
+}
+
+extern "C" int lbm_run_driven_observed(lbm_ctx* c, int nsteps, float* av_vels, const float* accel, const lbm_observe* what) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (nsteps > 0 && !accel) return fail(LBM_EINVAL, "accel is NULL");
+  for (int t = 0; t < nsteps; ++t)
+    if (!std::isfinite(accel[t])) return fail(LBM_EINVAL, "accel[%d] is not finite", t);
+  return run_observed(c, nsteps, av_vels, what, true, accel);
 }

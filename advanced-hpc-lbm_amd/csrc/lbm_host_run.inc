@@ -64,6 +64,11 @@ struct RunKind {
   // Slab::dtab, have room: the caller asked); off them, a lattice alone that wave_admit said yes to runs its groups of K
   // steps in lbm_wave's driven flavour; every other step goes through the one-step kernel with its own pair.
   const float* drive = nullptr;
+  // drive with piece (lbm_run_driven_observed): the register tiles run their kRegForce | kRegProbe | kRegDrive flavour.  The
+  // table of the WHOLE call is on the slabs' devices already (uploaded once, before the first piece); drive_at is the call's
+  // step this piece starts at: the launch is handed Slab::dtab advanced by that many pairs, and uploads nothing.  drive
+  // itself is the host table advanced likewise, for every path off the tiles.
+  long drive_at = 0;
 };
 
 // The window of one lbm_run_window call: as given (validated), and as lbm_wave's window flavour tests it.
@@ -342,6 +347,7 @@ auto regtile_kernel(int r, bool fast, bool async, int flavour) {
   if (flavour == lbm::kRegProbe) return regtile_flavour<SLAB, lbm::kRegProbe>(r, fast, async);
   if (flavour == lbm::kRegDrive) return regtile_flavour<SLAB, lbm::kRegDrive>(r, fast, async);
   if (flavour == (lbm::kRegForce | lbm::kRegProbe)) return regtile_flavour<SLAB, lbm::kRegForce | lbm::kRegProbe>(r, fast, async);
+  if (flavour == (lbm::kRegForce | lbm::kRegProbe | lbm::kRegDrive)) return regtile_flavour<SLAB, lbm::kRegForce | lbm::kRegProbe | lbm::kRegDrive>(r, fast, async);
   return regtile_flavour<SLAB, 0>(r, fast, async);
 }
 
@@ -429,8 +435,9 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
   const bool pk = k.snap && (k.probe || k.window);      // lbm_run_probes, lbm_run_window: the kRegProbe flavour, with its larger LDS
   const bool fpk = k.piece;                             // lbm_run_observed: the kRegForce | kRegProbe flavour (forces counted when fk)
-  const bool dk = k.drive != nullptr;                   // lbm_run_driven: the kRegDrive flavour (the plain flavour's LDS)
-  const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : dk ? lbm::kRegDrive : 0;
+  const bool dk = k.drive != nullptr;                   // lbm_run_driven: the kRegDrive flavour (the plain flavour's LDS); with fpk,
+                                                        // lbm_run_driven_observed: kRegForce | kRegProbe | kRegDrive (the force-and-probe flavour's)
+  const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe | (dk ? lbm::kRegDrive : 0)) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : dk ? lbm::kRegDrive : 0;
   auto kernel = [&](int fl) {
     return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
                 : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
@@ -572,7 +579,8 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       }
       a.nty_s = t.nty; a.nty_n = t.nty;
       a.drive = nullptr;
-      if (dk) {                       // the schedule, in front of the slab's launch on its stream: 8 bytes per step
+      if (dk && fpk) a.drive = s.dtab + 2 * k.drive_at;   // (a piece: the whole call's table is there, uploaded once)
+      else if (dk) {                  // the schedule, in front of the slab's launch on its stream: 8 bytes per step
         HIPC(hipSetDevice(s.dev));
         HIPC(hipMemcpyAsync(s.dtab, k.drive, sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
         a.drive = s.dtab;

@@ -60,7 +60,9 @@ constexpr int kRegMean = 65536;   // lbm_regtile: time-averaged fields summed du
 constexpr int kRegProbe = 131072; // lbm_regtile: per-step time series at chosen cells (lbm_run_probes).  A flavour of its own, like
                                   // kRegSnap: one word per cell in LDS, on a sample step one 16-byte store per PROBE and nothing else
 constexpr int kRegDrive = 262144; // lbm_regtile: a per-step acceleration schedule (lbm_run_driven).  A flavour of its own, like kRegSnap: the
-                                  // waves that hold the accelerate row read each step's constants from a table, by a scalar load
+                                  // waves that hold the accelerate row read each step's constants from a table, by a scalar load.
+                                  // kRegForce | kRegProbe | kRegDrive (lbm_run_driven_observed): the force-and-probe flavour with the
+                                  // accelerate constants taken this way -- the one product of flavours there is
 typedef __attribute__((address_space(1))) unsigned int gu32;
 
 // Per-step forces of a whole-run launch with kRegForce: partials[step][slot][8] (8 = four labels x two components, the
@@ -145,7 +147,8 @@ struct RegTileArgs {
   // At the END, so that every member above keeps its place.
   int pfirst;
   const int* pslot; const uint32_t* pwords;
-  // ---- a schedule (lbm_run_driven, flavour kRegDrive only): drive[s][2] = (a1, a2) of the accelerate phase of step s + 1 of
+  // ---- a schedule (lbm_run_driven, flavour kRegDrive; lbm_run_driven_observed, kRegForce | kRegProbe | kRegDrive -- a piece
+  // that starts `done` steps into its call is handed the call's table advanced by `done` pairs): drive[s][2] = (a1, a2) of the accelerate phase of step s + 1 of
   // the run, s = 0 .. nsteps - 1, made on the host as a1 and a2 above are; entry 0 is the prologue's, entry s what the rows
   // written in step s carry (the last step writes none); a1, a2 unused.  Device memory, read through the constant address
   // space by the waves that hold the accelerate row.  At the END, so that every member above keeps its place.
@@ -197,7 +200,7 @@ __device__ __forceinline__ void regtile_body(const RegTileArgs& a) {
   constexpr bool MEAN = (MODE & kRegMean) != 0;
   constexpr bool PROBE = (MODE & kRegProbe) != 0;
   constexpr bool DRIVE = (MODE & kRegDrive) != 0;
-  static_assert(!(DRIVE && (SNAP || FORCE || MEAN || PROBE)), "the schedule is a flavour of its own");
+  static_assert(!(DRIVE && (SNAP || MEAN || FORCE != PROBE)), "the schedule is a flavour of its own, or rides with forces and probes");
   static_assert(!(MEAN && (SNAP || FORCE)) && !(PROBE && (SNAP || MEAN)), "one flavour per launch, or forces with probes");
   // The mail of the loop issued and waited for BY HAND (R > 1): see "the asynchronous loop" below
   constexpr bool ASYNC = (MODE & kRegAsync) != 0 && R > 1;

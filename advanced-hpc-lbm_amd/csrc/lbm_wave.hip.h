@@ -153,6 +153,11 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // the pass's K pairs in the kernel's arguments (scalar registers, the level is a compile-time constant of the unrolled loop)
 // where every other flavour takes a1, a2; both images of the accelerate row that a chunk's fill rows may pass within a level
 // take that level's pair.  Nothing else differs from the plain kernel.
+// FORCE, PROBE and DRIVEN together (lbm_run_driven_observed; the one product of flavours there is): the force-and-probe flavour
+// with the constants taken as DRIVEN takes them.  It serves forces alone, probes alone or both: `blocked` is then whichever
+// map marks what is wanted -- the force map (no probe bit: no lane ever stores a probe, pidx is not read), the probe map (no
+// counted cell: contrib and fidx are not read), the force-and-probe map, or the plain obstacle bytes, whose values 0 and 1
+// are a map that marks nothing.
 template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false, bool WINDOW = false,
           bool DRIVEN = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
@@ -165,7 +170,7 @@ void lbm_wave(const WaveArgs a) {
   static_assert(!(PROBE && SLAB), "the probe flavours are for a lattice alone");
   static_assert(!(FIELD && (SLAB || FORCE || PROBE)), "the field flavour is for a lattice alone, and a flavour of its own");
   static_assert(!(WINDOW && (SLAB || FORCE || PROBE || FIELD)), "the window flavour is for a lattice alone, and a flavour of its own");
-  static_assert(!(DRIVEN && (SLAB || FORCE || PROBE || FIELD || WINDOW)), "the driven flavour is for a lattice alone, and a flavour of its own");
+  static_assert(!(DRIVEN && (SLAB || FORCE != PROBE || FIELD || WINDOW)), "the driven flavour is for a lattice alone: alone, or with forces and probes");
   static_assert(!DRIVEN || K <= 8, "K pairs of constants in the arguments");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];

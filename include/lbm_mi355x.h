@@ -416,10 +416,57 @@ int lbm_set_accel(lbm_ctx* ctx, float accel);
    LBM_EINVAL with nothing queued and the lattice untouched: NULL ctx; nsteps < 0; accel NULL with nsteps > 0; a non-finite
    entry (the message names its index).  LBM_ENOMEM likewise when the device table does not fit and no path with the same
    bits is left (the one-step path needs no table).  nsteps = 0: success, nothing runs.
-   Not offered: a schedule inside lbm_run_observed or the single observer calls (piecewise-constant forcing with observers
-   is lbm_set_accel between calls); schedules for omega or density; a schedule from the command-line tool; device-memory
-   schedules. */
+   Observers under a schedule: lbm_run_driven_observed, below.
+   Not offered: a schedule inside the single observer calls or lbm_run_window (lbm_run_driven_observed with one observer
+   serves the former); schedules for omega or density; a schedule from the command-line tool; device-memory schedules. */
 int lbm_run_driven(lbm_ctx* ctx, int nsteps, float* av_vels, const float* accel);
+/* lbm_run_driven(ctx, nsteps, av_vels, accel) that also fills the outputs named in `what` (lbm_observe, as lbm_run_observed
+   takes it: layout, periods, rank conventions, host or device memory per pointer, forces in host memory).  what NULL, or
+   all four pointers NULL: exactly lbm_run_driven, av_vels bits included.  One observer alone is legal (there are no driven
+   single calls: this call serves them).  Sample steps count from the start of the call, the three periods are independent.
+   The context's own acceleration is untouched.
+   Definition: let X_t be what lbm_final_state returns after step t of the loop
+       lbm_set_accel(ctx, accel[t]); lbm_run(ctx, 1, ...);
+   from the same state with the same options.  Probes, snapshots and means are defined from X_t exactly as lbm_run_probes,
+   lbm_run_sampled and lbm_run_mean define theirs from lbm_run_sampled's snapshots (the float sum in step order, the
+   correctly rounded division, the blocked cells' constants, the -0 handling), and are bit for bit that on every engine.
+   forces[t] is F_b (lbm_run_forces) on the lattice stored after step t of that loop.
+   Bit for bit, and to rounding:
+   - the lattice and everything after the call: lbm_run_driven's, hence the loop's, on every engine;
+   - forces where lbm_wave or the one-step kernel took them: the bits of lbm_set_accel(accel[t]); lbm_run_forces(ctx, 1, ...)
+     per step under engine 1, time_block 1 ("the bits of the one-step path"); where the register tiles took them: their own
+     fixed-order sums, as for lbm_run_forces there;
+   - with a constant schedule equal to the context's acceleration, forces and av_vels are bit-identical to
+     lbm_run_observed's with the same `what` on the same context and options, wherever the register tiles ran, and in
+     lbm_wave for the steps inside full passes;
+   - av_vels otherwise: lbm_run_driven's contract (the loop's within float rounding of the per-step sum).
+   Which kernels run:
+   - The register-tile engines, alone and across slabs: EVERY piece of the call runs one flavour, forces and probes under
+     a schedule, whichever observers are wanted (one that is not gets a table of -1s).  The whole call's (a1, a2) pairs go
+     to the device once; a piece that starts `done` steps into the call reads from pair `done` on, by scalar loads.  Forces
+     and probes cut no piece; means and snapshots are taken behind pieces that end on their sample steps.
+   - Where lbm_wave runs (lbm_run_driven's terms, and lbm_run_forces' / lbm_run_probes' for their maps): one flavour of
+     lbm_wave with forces, probes and the K pairs of a pass (an observer that is not wanted marks nothing in its map);
+     forces and probes cut no piece; means and snapshots cut pieces at their sample steps and are taken behind them; the
+     steps left over behind the last full pass of a piece go through the one-step kernel, each with its own pair, forces and
+     probes taken behind them.  Maps that do not fit: the one-step path, no error.
+   - Every other engine, pieces shorter than time_block, a register-tile piece that gave up or whose flavour is not
+     resident (it has stepped nothing: that piece again from the same step, off the tiles for the rest of the call): the
+     one-step kernel with each step's own constants, and behind a step the small kernels it calls for.  Correct, not fast,
+     the same bits; the three keys below read 0.
+   Info "driven_observed_in_kernel" (bits 1 forces, 2 probes, 4 means, 8 snapshots: what the last call took inside
+   register-tile launches), "driven_observed_in_wave" (bits 1 forces, 2 probes), "driven_observed_pieces" (the step-loop
+   pieces of the last call; 0 where the whole call took the one-step path).  What "observed_*", "driven_in_*" and the single calls' "*_in_kernel" / "*_in_wave" keys read
+   after this call is unspecified.
+   Refusals, all with nothing queued and the lattice untouched -- LBM_EINVAL: NULL ctx; nsteps < 0; accel NULL with
+   nsteps > 0; a non-finite entry (the message names its index); forces wanted without bodies; probes wanted without a
+   probe set; probes or means wanted with every <= 0 or no sample step in nsteps (nsteps = 0 included); fields_every < 0;
+   a device pointer on another device than the slabs'.  LBM_ENOMEM when a staging, table or partial buffer does not fit and
+   no path with the same bits is left (a schedule table that does not fit: the call keeps off the register tiles and does
+   not fail).  nsteps = 0 otherwise: success, nothing runs.  Rank contexts agree on room and on the path before anything is
+   queued.
+   Not offered: windows under a schedule; schedules for omega or density; device-memory schedules; the command-line tool. */
+int lbm_run_driven_observed(lbm_ctx* ctx, int nsteps, float* av_vels, const float* accel, const lbm_observe* what);
 
 /* GPU time of the step loop of the last lbm_run, from HIP events on the
  * compute stream of slab 0 (ms), and host wall time of the same region. */
@@ -488,7 +535,8 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "window_in_wave" (1: the last lbm_run_window took its window inside lbm_wave launches), "observed_in_kernel",
  * "observed_in_wave", "observed_pieces" (lbm_run_observed), "accel" (the context's acceleration: lbm_create's, or the last lbm_set_accel's),
  * "driven_in_kernel" (1: the last lbm_run_driven ran inside the register tiles), "driven_in_wave" (1: the last lbm_run_driven
- * ran its groups of K steps inside lbm_wave launches), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
+ * ran its groups of K steps inside lbm_wave launches), "driven_observed_in_kernel", "driven_observed_in_wave",
+ * "driven_observed_pieces" (lbm_run_driven_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
  * "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */

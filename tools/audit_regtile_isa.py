@@ -8,10 +8,12 @@ that retires them (marked `; retire v[a:b] ...` in the asm text) sees -- or dest
 asm `buffer_load_dwordx4` along every path (branches followed both ways, loops once round) until the retiring statement, and
 reports every instruction outside asm statements that touches the destination registers on the way; also scratch use and
 AGPR traffic, and any asynchronous flavour the library selects (plain, kRegSnap, kRegForce, kRegMean, kRegProbe, kRegForce | kRegProbe,
-kRegDrive; alone and across slabs) that is missing from the ISA.  The driven flavour (kRegDrive, lbm_run_driven) must read its
-schedule by scalar loads alone -- a vector-memory load would be counted in vmcnt and break every hand-counted wait behind it --
-so any vector-memory instruction outside the asm statements that a driven instantiation has and its plain twin has not is a
-finding (compared over the whole kernel, the step loop included).  Exit status 1 on any finding.
+kRegDrive, kRegForce | kRegProbe | kRegDrive; alone and across slabs) that is missing from the ISA.  The driven flavours (kRegDrive,
+lbm_run_driven; kRegForce | kRegProbe | kRegDrive, lbm_run_driven_observed) must read their schedule by scalar loads alone -- a
+vector-memory load would be counted in vmcnt and break every hand-counted wait behind it -- so any vector-memory instruction
+outside the asm statements that a driven instantiation has and its twin without kRegDrive (the plain flavour; the
+force-and-probe flavour) has not is a finding (compared over the whole kernel, the step loop included).  Exit status 1 on any
+finding.
 
     python tools/audit_regtile_isa.py [file.s]      (default: compiles advanced-hpc-lbm_amd/csrc/lbm_api.hip -S for gfx950)
 """
@@ -156,22 +158,22 @@ def main():
     # the flavours the library selects must all be here: lbm_run's, the snapshots' (kRegSnap), the forces' (kRegForce), the
     # means' (kRegMean), the probes' (kRegProbe) and lbm_run_observed's forces with probes (kRegForce | kRegProbe), alone and
     # across slabs (kRegSlab), R = 2 and 4, with and without fast math
-    # ... and lbm_run_driven's (kRegDrive)
+    # ... and lbm_run_driven's (kRegDrive) and lbm_run_driven_observed's (kRegForce | kRegProbe | kRegDrive)
     for flav, label in ((0, "plain"), (16384, "snapshot"), (32768, "force"), (65536, "mean"), (131072, "probe"),
-                        (32768 | 131072, "force + probe"), (262144, "driven")):
+                        (32768 | 131072, "force + probe"), (262144, "driven"), (32768 | 131072 | 262144, "driven force + probe")):
         for slab in (0, 8192):
             for r in (2, 4):
                 for fast in (0, 1):
                     if (r, 4096 | flav | slab | fast) not in seen:
                         allf.append(f"{label} instantiation <{r}, {4096 | flav | slab | fast}> missing from the ISA")
-    # a driven instantiation against its plain twin: no vector-memory instruction of the compiler's that the twin has not
+    # a driven instantiation against its twin without kRegDrive: no vector-memory instruction of the compiler's that the twin has not
     for (r, mode), (kname, counts) in sorted(vmem.items()):
         if not (mode & 262144) or (r, mode ^ 262144) not in vmem:
             continue
         twin = vmem[(r, mode ^ 262144)][1]
         for op, n in sorted(counts.items()):
             if n > twin.get(op, 0):
-                allf.append(f"{kname}: {n} x `{op}` outside the asm statements, its plain twin has {twin.get(op, 0)}")
+                allf.append(f"{kname}: {n} x `{op}` outside the asm statements, its twin without kRegDrive has {twin.get(op, 0)}")
     for f in allf[:40]:
         print("  ", f)
     if kernels == 0 or total == 0:
