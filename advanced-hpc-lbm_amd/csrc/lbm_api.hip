@@ -36,6 +36,7 @@
 #include "lbm_march.hip.h"
 #include "lbm_wave.hip.h"
 #include "lbm_regtile.hip.h"
+#include "lbm_tile_table.h"
 
 // ----------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
@@ -119,6 +120,9 @@ static int load() {
 // ----------------------------------------------------------------- context
 namespace {
 
+// A grow-only device buffer of floats (grown_room, lbm_host_slabs.inc); cap in the units of its call site
+struct GrownBuf { float* p = nullptr; long cap = 0; };
+
 struct Slab {
   int dev = 0;
   int row0 = 0, nyl = 0;       // global rows [row0, row0+nyl)
@@ -180,56 +184,44 @@ struct Slab {
   // over xGMI), its per-step tile sums, and the neighbours' mail areas as this device sees them ([0] south, [1] north)
   char* tmail = nullptr;
   size_t tmail_bytes = 0;
-  float* rpartials = nullptr;
-  long rpartials_cap = 0;          // in steps
+  GrownBuf rpartials;              // (cap in steps, ntiles floats each)
   char* tmail_nb[2] = {nullptr, nullptr};
   size_t tmail_nb_bytes[2] = {0, 0};
   bool tmail_nb_ipc[2] = {false, false};
   uint32_t* rabort = nullptr;      // abort word of this slab's device group (owned by the group's first slab)
   hipEvent_t ev_rt = nullptr;      // "the group's launch is over" (recorded on the first slab's stream)
   // bodies (lbm_set_bodies): the slab's blocked labelled cells with a fluid source, {column, local row, mask | label << 8};
-  // on the device as {offset in a plane, word} for lbm_body_forces; the register tiles' tables (lbm_regtile.hip.h, kRegForce)
-  // for tiles of fty rows (0: not built) and their per-step partials
+  // on the device as {offset in a plane, word} for lbm_body_forces; the register tiles' table (lbm_regtile.hip.h, kRegForce)
+  // and their per-step partials
   std::vector<int4> fcells_host;
   int2* fcells = nullptr;
   int fcells_n = 0;
-  int* fslot = nullptr;
-  uint32_t* fwords = nullptr;
-  int fnslots = 0, fty = 0;
-  float* fpart = nullptr;
-  long fpart_cap = 0;              // floats
+  TileTable tforces;
+  GrownBuf fpart;                  // (cap in floats)
   // lbm_wave's force flavour (a lattice alone; lbm_host_march.inc, wave_force_ready): the obstacle bytes with 2 on the cells
   // of fcells, those cells' indices in fcells (dense, read at counted cells only), one group's contributions [K][fcells_n][2]
   uint8_t* fmap = nullptr;
   int* fidx = nullptr;
-  float* fcontrib = nullptr;
-  long fcontrib_cap = 0;           // floats
+  GrownBuf fcontrib;               // (cap in floats)
   // probes (lbm_set_probes): the slab's probes, {column, local row, index in the set}; on the device as {offset in a plane,
-  // index} for lbm_probe_gather; the register tiles' tables (lbm_regtile.hip.h, kRegProbe) for tiles of pty rows (0: not built)
+  // index} for lbm_probe_gather; the register tiles' table (lbm_regtile.hip.h, kRegProbe)
   std::vector<int4> pcells_host;
   int2* pcells = nullptr;
-  int* pslot = nullptr;
-  uint32_t* pwords = nullptr;
-  int pty = 0;
-  // windows (lbm_run_window): the register tiles' tables of the last window this slab ran, laid out as pslot / pwords, for
-  // tiles of wty rows (0: not built) and the window wkey; the probe set and its tables are not touched
-  int* wslot = nullptr;
-  uint32_t* wwords = nullptr;
-  int wty = 0;
+  TileTable tprobes;
+  // windows (lbm_run_window): the register tiles' table of the last window this slab ran, the window wkey, laid out and fed
+  // as the probes'; the probe set and its table are not touched
+  TileTable twindow;
   lbm_window wkey = {0, 0, 0, 0, 0, 0};
-  // lbm_run_observed, probes without forces in the kRegForce | kRegProbe flavour: a force slot table of fslot_none_n tiles
-  // that are all -1 (no tile counts anything)
-  int* fslot_none = nullptr;
-  int fslot_none_n = 0;
+  // the table of -1s, no words: what the kRegForce | kRegProbe flavour is handed for an observer that is not wanted
+  TileTable tnone;
   // lbm_wave's probe flavours (a lattice alone; lbm_host_march.inc, wave_probe_ready): the obstacle bytes with 4 added on the
   // probes' cells (probes alone), the force map with the same (forces and probes: follows both sets), the probes' indices in
   // the set (dense, read at probe cells only)
   uint8_t* pmap = nullptr;
   uint8_t* fpmap = nullptr;
   int* pidx = nullptr;
-  // lbm_run_driven on the register tiles: the schedule's (a1, a2) pairs on the device, room for dtab_cap steps
-  float* dtab = nullptr;
-  long dtab_cap = 0;
+  // lbm_run_driven on the register tiles: the schedule's (a1, a2) pairs on the device
+  GrownBuf dtab;                   // (cap in steps, 2 floats each)
 };
 
 }  // namespace
@@ -685,9 +677,9 @@ static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
 
 #include "lbm_host_observe.inc"
 
-// The step loop of lbm_run.  k.snap (lbm_run_sampled; with k.mean: lbm_run_mean; with k.probe: lbm_run_probes): ONLY the
-// register tiles are tried, with the snapshots (the sums, the probes) in the kernel; if they did not run (samples_in_kernel /
-// mean_in_kernel / probes_in_kernel stays 0), nothing has been stepped and the caller runs the steps in pieces.
+// The step loop of lbm_run.  k.snap (the snapshots, mean, probes and window flavours of RunKind): ONLY the register tiles
+// are tried, with the snapshots (the sums, the probes, the window) in the kernel; if they did not run (the flavour's
+// *_in_kernel key stays 0), nothing has been stepped and the caller runs the steps in pieces.
 static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
@@ -701,7 +693,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
                                         // (with forces or probes beside it, lbm_run_driven_observed: the driven force-and-probe flavours)
   auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };   // the accelerate constants of step t (0-based) of this run
   auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };
-  if (!k.no_tiles && (!fo || k.force_tiles) && regtile_is_next(c)) {
+  if (!k.no_tiles && regtile_is_next(c)) {   // (a forces run that may not use the tiles says no_tiles)
     bool done = false;
     int rr = run_regtile(c, nsteps, av_vels, &done, k);
     if (rr && c->engine == 0) {
@@ -714,17 +706,17 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (rr) return rr;
     if (done) {
       c->engine_last = 3;
-      if (k.snap && k.window) c->window_in_kernel = 1;
-      else if (k.snap && k.probe) c->probes_in_kernel = 1;
-      else if (k.snap && k.mean) c->mean_in_kernel = 1;
-      else if (k.snap) c->samples_in_kernel = 1;
+      if (k.flavour == RegFlavour::window) c->window_in_kernel = 1;
+      else if (k.flavour == RegFlavour::probes || (k.flavour == RegFlavour::piece && k.snap)) c->probes_in_kernel = 1;
+      else if (k.flavour == RegFlavour::mean) c->mean_in_kernel = 1;
+      else if (k.flavour == RegFlavour::snapshots) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
       if (dr) c->driven_in_kernel = 1;
       if (k.ran) *k.ran = true;
       return LBM_OK;
     }
   }
-  if (k.piece) return LBM_OK;   // (lbm_run_observed: nothing stepped; it runs the piece again off the tiles)
+  if (k.flavour == RegFlavour::piece) return LBM_OK;   // (lbm_run_observed: nothing stepped; it runs the piece again off the tiles)
   if (c->engine >= 2 && !fo && !dr) return fail(LBM_EINVAL, "the register tiles cannot run here (%s), or this lattice has no register tiling (engine = %d)",
                                          c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
   if (k.snap) return LBM_OK;

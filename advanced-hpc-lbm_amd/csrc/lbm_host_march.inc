@@ -643,8 +643,8 @@ void wave_plan(lbm_ctx* c) {
 void wave_force_free(Slab& s) {
   if (s.fmap) (void)hipFree(s.fmap);
   if (s.fidx) (void)hipFree(s.fidx);
-  if (s.fcontrib) (void)hipFree(s.fcontrib);
-  s.fmap = nullptr; s.fidx = nullptr; s.fcontrib = nullptr; s.fcontrib_cap = 0;
+  grown_free(s.fcontrib);
+  s.fmap = nullptr; s.fidx = nullptr;
 }
 bool wave_force_ready(lbm_ctx* c, int K) {
   Slab& s = c->slabs[0];
@@ -661,14 +661,7 @@ bool wave_force_ready(lbm_ctx* c, int K) {
     }
     if (!ok) { (void)hipGetLastError(); (void)hipStreamSynchronize(s.sc); wave_force_free(s); return false; }
   }
-  const long need = 2L * K * n;
-  if (need > s.fcontrib_cap) {
-    if (s.fcontrib) (void)hipFree(s.fcontrib);
-    s.fcontrib = nullptr; s.fcontrib_cap = 0;
-    if (hipMalloc((void**)&s.fcontrib, sizeof(float) * (size_t)need) != hipSuccess) { (void)hipGetLastError(); s.fcontrib = nullptr; return false; }
-    s.fcontrib_cap = need;
-  }
-  return true;
+  return grown_room(s, s.fcontrib, 2L * K * n, 1, false);
 }
 
 // The probe flavours' maps of the lone slab, built at the first probe run that wants them: the probe map and the index map
@@ -777,7 +770,7 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   if (drv && (nb_bodies > 0 || wp.out != nullptr)) {
     const bool counted = nb_bodies > 0 && s.fcells_n > 0;
     a.blocked = wp.out != nullptr ? (counted ? s.fpmap : s.pmap) : (counted ? s.fmap : s.blocked);
-    if (counted) { a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n; }
+    if (counted) { a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n; }
     launch(wave_driven_observed_kernel(K, wave_C(c, K), flavour));
   } else if (drv) launch(wave_driven_kernel(K, wave_C(c, K), flavour));
   else if (fields) {
@@ -785,19 +778,19 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
     if (wf.win) { a.fadd = 0; a.win = *wf.win; launch(wave_window_kernel(K, wave_C(c, K), flavour)); }
     else launch(wave_field_kernel(K, wave_C(c, K), flavour));
   } else if (probes && nb_bodies > 0 && s.fcells_n > 0) {
-    a.blocked = s.fpmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n;
+    a.blocked = s.fpmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n;
     launch(wave_probe_kernel<true>(K, wave_C(c, K), flavour));
   } else if (probes) {
     a.blocked = s.pmap;
     launch(wave_probe_kernel<false>(K, wave_C(c, K), flavour));
   } else if (nb_bodies > 0 && s.fcells_n > 0) {
-    a.blocked = s.fmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib; a.fcells_n = s.fcells_n;
+    a.blocked = s.fmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n;
     launch(wave_force_kernel(K, wave_C(c, K), flavour));
   } else
     launch(wave_kernel(K, false, wave_C(c, K), flavour));
   HIPC(hipGetLastError());
   if (nb_bodies > 0) {
-    hipLaunchKernelGGL(lbm::lbm_fold_wave_forces, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.fcontrib, s.fcells, s.fcells_n, nb_bodies,
+    hipLaunchKernelGGL(lbm::lbm_fold_wave_forces, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.fcontrib.p, s.fcells, s.fcells_n, nb_bodies,
                        s.sums + nsteps + 1 + (long)tt * 2 * nb_bodies);
     HIPC(hipGetLastError());
   }

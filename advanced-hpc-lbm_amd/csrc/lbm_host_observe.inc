@@ -7,18 +7,20 @@
 //   ProbeOut, MeanOut                      where one call's probe values / means go: device output in place, host output
 //                                          through per-slab staging (snapshots keep derive_all and their two staging shapes)
 //   run_split                              the step loop cut at the sample steps, plain run_steps pieces (the single calls)
-// Each call keeps its own refusals, the order in which it decides things before anything is queued, and its choice of path.
+//   observers_free                         everything a slab holds for these calls, released in one place (slab_free)
+// Each call keeps its own refusals, the order in which it decides things before anything is queued, and its choice of path; it
+// names what the register tiles would run in RunKind::flavour, and hands its cells to the one table builder (tile_table_set).
 //
 // lbm_run_observed, one run with any subset of the four observers (forces, probes, means, snapshots).  DESIGN.md 3.11.
 //
 // One observer alone IS its own call.  Two or more: the step loop is cut into pieces at the sample steps of the observers that
 // are not taken inside a launch -- means and snapshots always; probes where the register tiles do not run -- and each piece is
 // one run_steps with a RunKind that carries the observers taken inside it.
-//   register tiles   EVERY piece runs the kRegForce | kRegProbe flavour (RunKind::piece), whichever of the two is wanted: it
+//   register tiles   EVERY piece runs the kRegForce | kRegProbe flavour (RegFlavour::piece), whichever of the two is wanted: it
 //            alone knows a first-sample phase (pfirst), and it alone folds the last step's speed sum of a piece that is not the
 //            call's last as the loop folds every other step's (piece_mid) -- a whole-run launch folds its last step in
 //            another order of additions, so pieces of the other flavours would move the last bit of av_vels at the cuts.
-//            An observer that is not wanted gets the table of -1s.  A piece of n steps leaves its forces behind its per-step
+//            An observer that is not wanted gets the table of -1s (empty_table).  A piece of n steps leaves its forces behind its per-step
 //            sums (sums + n + 1), reduced and fetched with them.
 //   elsewhere        forces as lbm_run_forces there (one-step kernel, lbm_body_forces behind each step), lbm_probe_gather
 //            behind the piece that ends on a probe sample step.
@@ -263,35 +265,20 @@ int run_split(lbm_ctx* c, int nsteps, float* av_vels, int every, int m, F after_
   return LBM_OK;
 }
 
-// the table of -1s of a slab for the current tiling (LBM_ENOMEM: nothing queued)
-int observed_no_force_table(Slab& s, int ntiles) {
-  if (s.fslot_none && s.fslot_none_n == ntiles) return LBM_OK;
-  HIPC(hipSetDevice(s.dev));
-  if (s.fslot_none) HIPC(hipFree(s.fslot_none));
-  s.fslot_none = nullptr; s.fslot_none_n = 0;
-  if (hipMalloc((void**)&s.fslot_none, sizeof(int) * (size_t)ntiles) != hipSuccess) {
-    (void)hipGetLastError();
-    s.fslot_none = nullptr;
-    return fail(LBM_ENOMEM, "no room on device %d for the empty force table (%d tiles)", s.dev, ntiles);
-  }
-  HIPC(hipMemset(s.fslot_none, 0xff, sizeof(int) * (size_t)ntiles));
-  s.fslot_none_n = ntiles;
-  return LBM_OK;
+// Everything a slab holds for the observer calls (slab_free): the cell lists, the four tables, the four grown buffers, lbm_wave's maps
+void observers_free(Slab& s) {
+  if (s.fcells) (void)hipFree(s.fcells);
+  if (s.pcells) (void)hipFree(s.pcells);
+  s.fcells = nullptr; s.pcells = nullptr; s.fcells_n = 0;
+  for (TileTable* t : {&s.tforces, &s.tprobes, &s.twindow, &s.tnone}) tile_table_free(*t);
+  for (GrownBuf* b : {&s.rpartials, &s.fpart, &s.dtab, &s.fcontrib}) grown_free(*b);
+  wave_force_free(s);
+  wave_probe_free(s, true);
 }
 
 // room on a slab's device for the (a1, a2) pairs of a schedule of nsteps steps (Slab::dtab; lbm_run_driven and
 // lbm_run_driven_observed on the register tiles).  false: no room, nothing queued -- the caller keeps off the tiles
-bool drive_table_room(Slab& s, int nsteps) {
-  if (s.dtab_cap >= nsteps) return true;
-  if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-  long cap = std::max(1024L, s.dtab_cap);
-  while (cap < nsteps) cap *= 2;
-  if (s.dtab) (void)hipFree(s.dtab);
-  s.dtab = nullptr; s.dtab_cap = 0;
-  if (hipMalloc((void**)&s.dtab, sizeof(float) * 2 * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); s.dtab = nullptr; return false; }
-  s.dtab_cap = cap;
-  return true;
-}
+bool drive_table_room(Slab& s, int nsteps) { return grown_room(s, s.dtab, nsteps, 2, true); }
 
 }  // namespace
 
@@ -333,7 +320,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
       sp.at.push_back((float*)stage[i].p); sp.stride.push_back((long)s.nyl * nx * 4);
     }
     RunKind k;
-    k.snap = &sp;
+    k.flavour = RegFlavour::snapshots; k.snap = &sp;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     if (c->samples_in_kernel) {
       if (!on_dev)
@@ -407,7 +394,8 @@ extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
     Slab& s = c->slabs[k];
     HIPC(hipSetDevice(s.dev));
     if (s.fcells) HIPC(hipFree(s.fcells));
-    s.fcells = nullptr; s.fcells_n = 0; s.fty = 0;
+    s.fcells = nullptr; s.fcells_n = 0;
+    tile_table_free(s.tforces);         // (the register tiles' table: rebuilt by the next run that counts forces)
     wave_force_free(s);                 // (lbm_wave's force maps follow the list: rebuilt by the next forces run that wants them)
     wave_probe_free(s, false);          // (... and so does the force-and-probe map)
     s.fcells_host.swap(lists[k]);
@@ -445,11 +433,11 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
   bool in_kernel = regtile_is_next(c);
   if (in_kernel) {
     for (auto& s : c->slabs)
-      if ((rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps))) break;
+      if ((rc = force_tables(s, c->tplan.ty, c->tplan.ntx, nsteps))) break;
   }
   if ((rc = ranks_agree(c, rc, &in_kernel, "the force partials"))) return rc;
   RunKind k;
-  k.nb = nb; k.nval = nval; k.force_tiles = in_kernel;
+  k.flavour = RegFlavour::forces; k.nb = nb; k.nval = nval; k.no_tiles = !in_kernel;
   if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
   fetch_forces(c, nsteps, nval, forces);
   return LBM_OK;
@@ -477,7 +465,7 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
     sp.every = every;
     for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(mo.at(i)); sp.stride.push_back(0); }
     RunKind k;
-    k.snap = &sp; k.mean = true;
+    k.flavour = RegFlavour::mean; k.snap = &sp;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     if (c->mean_in_kernel) return mo.to_host();
     // (the register tiles did not run, or gave up with the lattice untouched and nothing stored: the pieces below repeat the run)
@@ -543,7 +531,7 @@ extern "C" int lbm_set_probes(lbm_ctx* c, const int* xy, int nprobes) {
     if (s.pcells) HIPC(hipFree(s.pcells));
     s.pcells = (int2*)fresh[k].p; fresh[k].p = nullptr;
     s.pcells_host.swap(lists[k]);
-    s.pty = 0;                      // (the register tiles' tables: rebuilt by the next lbm_run_probes)
+    tile_table_free(s.tprobes);     // (the register tiles' table: rebuilt by the next run that takes probes)
     wave_probe_free(s, true);       // (lbm_wave's probe maps likewise)
   }
   c->nprobes = nprobes;
@@ -566,7 +554,7 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
   if ((rc = po.locate(probes_out, "probes_out"))) return rc;
   bool in_kernel = regtile_is_next(c);
   rc = po.prepare(m);
-  for (size_t i = 0; i < c->slabs.size() && !rc && in_kernel; ++i) rc = probe_tables(c, c->slabs[i], c->tplan.ty, c->tplan.ntx);
+  for (size_t i = 0; i < c->slabs.size() && !rc && in_kernel; ++i) rc = probe_tables(c->slabs[i], c->tplan.ty, c->tplan.ntx);
   if ((rc = ranks_agree(c, rc, &in_kernel, "the probes"))) return rc;
   if ((rc = po.zero_foreign())) return rc;
   if (in_kernel) {
@@ -575,7 +563,7 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
     sp.every = every;
     for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(po.at(i, 0)); sp.stride.push_back(4L * po.np); }
     RunKind k;
-    k.snap = &sp; k.probe = true;
+    k.flavour = RegFlavour::probes; k.snap = &sp;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     if (c->probes_in_kernel) return po.to_host();
     // (the register tiles did not run, or gave up with the lattice untouched: the pieces below repeat the run and store every value again)
@@ -646,44 +634,17 @@ int launch_derive_window(const lbm_ctx* c, Slab& s, const lbm_window& w, int fir
   return LBM_OK;
 }
 
-// The register tiles' tables of a slab for a window and tiles of ty rows, laid out exactly as probe_tables lays out pslot /
-// pwords: slots in the order of the tiles (only tiles that hold a window cell have one); a cell's word is its place among the
-// SLAB's window rows + 1, (r - first) w.nx + c + 1 -- the slab's output pointer is its first window row's.  Kept by
-// (window, tiling); the probe set's tables are not touched.  LBM_ENOMEM: nothing queued.
-int window_tables(lbm_ctx* c, Slab& s, int ty, int ntx, const lbm_window& w, int first, int count) {
-  (void)c;
-  if (s.wty == ty && memcmp(&s.wkey, &w, sizeof(w)) == 0) return LBM_OK;
-  HIPC(hipSetDevice(s.dev));
-  const int nty = s.nyl / ty, ntiles = ntx * nty;
-  std::vector<int> slot(ntiles, -1);
-  auto cell_y = [&](int r) { return (int)((long)w.y0 + (long)(first + r) * w.sy - s.row0); };
-  auto cell_x = [&](int cc) { return (int)((long)w.x0 + (long)cc * w.sx); };
+// The window table of a slab for tiles of ty rows, fed to the probe flavour as the probe set's is: a cell's word is its place
+// among the SLAB's window rows + 1, (r - first) w.nx + c + 1 -- the slab's output pointer is its first window row's.  Kept by
+// (window, tiling); the probe set's table is not touched.  LBM_ENOMEM: nothing queued.
+int window_tables(Slab& s, int ty, int ntx, const lbm_window& w, int first, int count) {
+  if (s.twindow.ty == ty && memcmp(&s.wkey, &w, sizeof(w)) == 0) return LBM_OK;
+  std::vector<TileCell> cells;
   for (int r = 0; r < count; ++r)
-    for (int cc = 0; cc < w.nx; ++cc) slot[(cell_y(r) / ty) * ntx + cell_x(cc) / 64] = 0;
-  int n = 0;
-  for (int& v : slot) if (v == 0) v = n++;
-  std::vector<uint32_t> words((size_t)n * ty * 64, 0u);
-  for (int r = 0; r < count; ++r) {
-    const int y = cell_y(r);
-    for (int cc = 0; cc < w.nx; ++cc) {
-      const int x = cell_x(cc);
-      words[((size_t)slot[(y / ty) * ntx + x / 64] * ty + y % ty) * 64 + x % 64] = (uint32_t)((long)r * w.nx + cc) + 1u;
-    }
-  }
-  if (s.wslot) HIPC(hipFree(s.wslot));
-  if (s.wwords) HIPC(hipFree(s.wwords));
-  s.wslot = nullptr; s.wwords = nullptr; s.wty = 0;
-  if (hipMalloc((void**)&s.wslot, sizeof(int) * ntiles) != hipSuccess ||
-      (n > 0 && hipMalloc((void**)&s.wwords, sizeof(uint32_t) * words.size()) != hipSuccess)) {
-    (void)hipGetLastError();
-    if (s.wslot) (void)hipFree(s.wslot);
-    s.wslot = nullptr; s.wwords = nullptr;
-    return fail(LBM_ENOMEM, "no room on device %d for the window tables (%d tiles)", s.dev, n);
-  }
-  HIPC(hipMemcpy(s.wslot, slot.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
-  if (n > 0) HIPC(hipMemcpy(s.wwords, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
-  s.wty = ty; s.wkey = w;
-  return LBM_OK;
+    for (int cc = 0; cc < w.nx; ++cc)
+      cells.push_back({(int)((long)w.x0 + (long)cc * w.sx), (int)((long)w.y0 + (long)(first + r) * w.sy - s.row0), (uint32_t)((long)r * w.nx + cc) + 1u});
+  s.wkey = w;
+  return tile_table_set(s, s.twindow, ty, ntx, cells, "window");
 }
 
 // Where one call's windows go, [m][w.ny][w.nx][4] floats.  Device output is written in place; host output goes through one
@@ -815,7 +776,7 @@ extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every,
   bool in_kernel = regtile_is_next(c);
   bool staged = wo.prepare(m, false) == LBM_OK;
   for (size_t i = 0; i < c->slabs.size() && staged && in_kernel; ++i)
-    in_kernel = window_tables(c, c->slabs[i], c->tplan.ty, c->tplan.ntx, plan.w, wo.first[i], wo.count[i]) == LBM_OK;
+    in_kernel = window_tables(c->slabs[i], c->tplan.ty, c->tplan.ntx, plan.w, wo.first[i], wo.count[i]) == LBM_OK;
   rc = staged ? LBM_OK : wo.prepare(m, true);
   in_kernel = in_kernel && staged;
   if ((rc = ranks_agree(c, rc, &in_kernel, "the window"))) return rc;
@@ -827,7 +788,7 @@ extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every,
     sp.every = every;
     for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(wo.at(i, 0)); sp.stride.push_back(wo.stride(i)); }
     RunKind k;
-    k.snap = &sp; k.window = true;
+    k.flavour = RegFlavour::window; k.snap = &sp;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     if (c->window_in_kernel) return wo.finish();
     // (the register tiles did not run, or gave up with the lattice untouched: the paths below repeat the run and store every cell again)
@@ -927,9 +888,9 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
       (void)hipGetLastError();
       rc = fail(LBM_ENOMEM, "no room for the sums of %d steps and their forces", nsteps);
     }
-    if (!rc && tiles && !(wf && wp)) rc = observed_no_force_table(s, c->tplan.ntx * c->tplan.nty);
-    if (!rc && wf && tiles) rc = force_tables(c, s, c->tplan.ty, c->tplan.ntx, nsteps);
-    if (!rc && wp && tiles) rc = probe_tables(c, s, c->tplan.ty, c->tplan.ntx);
+    if (!rc && tiles && !(wf && wp)) rc = empty_table(s, c->tplan.ty, c->tplan.ntx);
+    if (!rc && wf && tiles) rc = force_tables(s, c->tplan.ty, c->tplan.ntx, nsteps);
+    if (!rc && wp && tiles) rc = probe_tables(s, c->tplan.ty, c->tplan.ntx);
   }
   if (!rc && wp) rc = po.prepare(mp);
   if (!rc && wm) rc = mo.prepare();
@@ -949,7 +910,7 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
   if (driven && tiles)
     for (auto& s : c->slabs) {
       HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemcpyAsync(s.dtab, pairs.data(), sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
+      HIPC(hipMemcpyAsync(s.dtab.p, pairs.data(), sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
     }
   // probes where lbm_run would run lbm_wave (a lattice alone): they ride in its launches, beside the forces if those are
   // wanted, and cut no piece; decided here, before anything is queued (no: lbm_probe_gather behind pieces cut at their steps)
@@ -972,15 +933,15 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
     const int jp = wp ? done / pe : 0;                    // the probes' samples taken before this piece
     float* av = av_vels ? av_vels + done : nullptr;
     RunKind k;
-    if (wf) { k.nb = nb; k.nval = nval; k.force_tiles = on_tiles; }
+    if (wf) { k.nb = nb; k.nval = nval; }
     if (driven) { k.drive = pairs.data() + 2 * (size_t)done; k.drive_at = done; }
     if (on_tiles) {
       SnapPlan sp;
       sp.every = pe;
       for (size_t i = 0; wp && i < ns; ++i) { sp.at.push_back(po.at(i, jp)); sp.stride.push_back(4L * np); }
       bool ran = false;
-      if (wp) { k.snap = &sp; k.probe = true; k.pfirst = pe - done % pe; }
-      k.piece = true; k.piece_mid = next < nsteps; k.ran = &ran;
+      if (wp) { k.snap = &sp; k.pfirst = pe - done % pe; }
+      k.flavour = RegFlavour::piece; k.piece_mid = next < nsteps; k.ran = &ran;
       if ((rc = run_steps(c, n, av, k))) return rc;
       if (!ran) { tiles = false; continue; }              // (nothing stepped: this piece again, off the tiles)
       bits |= (wf ? 1 : 0) | (wp ? 2 : 0);

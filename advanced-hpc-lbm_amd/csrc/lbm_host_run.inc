@@ -1,5 +1,7 @@
-// lbm_host_run.inc -- part of lbm_api.hip (included there): the end of a run (sums, agreement), the register-tile engine (one
-// driver for a lattice alone and for slabs), the step loop with peer-to-peer halos.
+// lbm_host_run.inc -- part of lbm_api.hip (included there): the kind of a run (RunKind: one flavour field for the register
+// tiles), the end of a run (sums, agreement), the tiles' tables (ONE upload, tile_table_set, of the layout lbm_tile_table.h
+// builds: forces, probes, windows, the empty table), the register-tile engine (one driver for a lattice alone and for
+// slabs; run_regtile turns the flavour into kernel, LDS and tables in one switch), the step loop with peer-to-peer halos.
 namespace {
 
 // Where a register-tile run puts its snapshots (lbm_run_sampled): per local slab, the slab's region of snapshot 0 on its
@@ -11,28 +13,32 @@ struct SnapPlan {
 };
 
 // The kind of a run, handed from lbm_run and the observer calls (lbm_host_observe.inc) through run_steps to the engine that runs it
-// (a plain lbm_run: the defaults).  snap (lbm_run_sampled): ONLY the register tiles are tried, with the snapshots in the
-// kernel.  nb > 0 (lbm_run_forces): nb bodies; the run's forces are nval = 2 nb nsteps doubles at sums + nsteps + 1 of every
-// slab (behind the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with
-// them; force_tiles: the register tiles may run, in their kRegForce flavour (else the run keeps off them).  mean
-// (lbm_run_mean, with snap): as snap, but the kRegMean flavour -- snap->at[i] is where slab i's means go, the strides unused.
-// probe (lbm_run_probes, with snap): as snap, but the kRegProbe flavour -- snap->at[i] is row 0 of the output slab i stores
-// into, stride[i] the floats from one sample's row to the next (4 x the probes of the whole set); the slabs' probe tables
-// (probe_tables) are in place.
-// piece (lbm_run_observed): a piece of a longer call -- ONLY the register tiles are tried, in their kRegForce | kRegProbe
-// flavour, which alone keeps the probes' phase (snap and probe: the first sample pfirst steps into the piece, 1 .. every)
-// and stores the last step's speed sums folded like any other step's (piece_mid, not the last piece of the call: those are the ones used).  Forces beside them
-// when nb > 0 and force_tiles; an observer that is not wanted gets the table of -1s (Slab::fslot_none: no tile counts or
-// stores anything).  *ran tells the caller whether the tiles ran the piece (false with LBM_OK: nothing stepped, nothing of
-// the piece's output is valid).  no_tiles: the register tiles are not tried.
+// (a plain lbm_run: the defaults).  `flavour` says what the register tiles would run, one line each with the other fields it
+// reads; every flavour but plain and forces tries ONLY the tiles (they did not run: nothing has been stepped):
+//   plain      lbm_run, lbm_run_driven: the plain kernel -- kRegDrive under a schedule (drive)
+//   snapshots  lbm_run_sampled: kRegSnap.  snap: per slab, where snapshot 0 goes and the floats to the next one
+//   forces     lbm_run_forces: kRegForce.  nb, nval; the slabs' force tables and partials are in place (force_tables)
+//   mean       lbm_run_mean: kRegMean.  snap: at[i] is where slab i's means go, the strides unused
+//   probes     lbm_run_probes: kRegProbe.  snap: at[i] is row 0 of the output slab i stores into, stride[i] the floats from one
+//              sample's row to the next (4 x the probes of the whole set); the slabs' probe tables are in place (probe_tables)
+//   window     lbm_run_window: as probes, fed the slabs' window tables (window_tables) in place of the probe set's
+//   piece      lbm_run_observed, lbm_run_driven_observed: a piece of a longer call, in the kRegForce | kRegProbe flavour
+//              (| kRegDrive under a schedule: drive, drive_at), which alone keeps the probes' phase and stores the last step's
+//              speed sums folded like any other step's (piece_mid, not the last piece of the call: those are the ones used).
+//              Forces are wanted when nb > 0 (nb, nval, as forces), probes when snap (as probes; pfirst: the first sample
+//              that many steps into the piece, 1 .. every); an observer that is not wanted gets the table of -1s
+//              (Slab::tnone: no tile counts or stores anything).  *ran tells the caller whether the tiles ran the piece
+//              (false with LBM_OK: nothing stepped, nothing of the piece's output is valid).
+// nb > 0 on every path: nb bodies; the run's forces are nval = 2 nb nsteps doubles at sums + nsteps + 1 of every slab (behind
+// the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with them.
+// no_tiles: the register tiles are not tried (the flavour is then read by nobody).
+enum class RegFlavour { plain, snapshots, forces, mean, probes, window, piece };
 struct RunKind {
+  RegFlavour flavour = RegFlavour::plain;
   const SnapPlan* snap = nullptr;
-  bool mean = false;
-  bool probe = false;
   int nb = 0;
   long nval = 0;
-  bool force_tiles = false;
-  bool piece = false, piece_mid = false, no_tiles = false;
+  bool piece_mid = false, no_tiles = false;
   int pfirst = 0;
   bool* ran = nullptr;
   // wave_pout (lbm_run_probes / lbm_run_observed on a context wave_probes_admit said yes to; a lattice alone, the register
@@ -53,18 +59,16 @@ struct RunKind {
   bool wave_fadd = false;
   float* wave_fpart = nullptr;
   double* wave_fmass = nullptr;
-  // window (lbm_run_window, with snap): as probe -- the kRegProbe flavour -- but with the slabs' window tables (window_tables)
-  // in place of the probe set's.  win (lbm_run_window, with wave_fout on a context wave_admit said yes to): wave_fout and
-  // wave_fstride are of windows, the groups of K steps take them inside lbm_wave's window flavour (win->wave); behind a
-  // left-over step that is a sample step, lbm_derive_window into the slot (no sums, wave_fpart / wave_fmass unused).
-  bool window = false;
+  // win (lbm_run_window, with wave_fout on a context wave_admit said yes to): wave_fout and wave_fstride are of windows, the
+  // groups of K steps take them inside lbm_wave's window flavour (win->wave); behind a left-over step that is a sample step,
+  // lbm_derive_window into the slot (no sums, wave_fpart / wave_fmass unused).
   const struct WinPlan* win = nullptr;
   // drive (lbm_run_driven): drive[2 t], drive[2 t + 1] = (a1, a2) of the accelerate phase of step t (0-based) of this run, host
   // memory, in place of the context's pair.  The register tiles run their kRegDrive flavour (the slabs' device tables,
   // Slab::dtab, have room: the caller asked); off them, a lattice alone that wave_admit said yes to runs its groups of K
   // steps in lbm_wave's driven flavour; every other step goes through the one-step kernel with its own pair.
   const float* drive = nullptr;
-  // drive with piece (lbm_run_driven_observed): the register tiles run their kRegForce | kRegProbe | kRegDrive flavour.  The
+  // drive with the piece flavour (lbm_run_driven_observed): the register tiles run kRegForce | kRegProbe | kRegDrive.  The
   // table of the WHOLE call is on the slabs' devices already (uploaded once, before the first piece); drive_at is the call's
   // step this piece starts at: the launch is handed Slab::dtab advanced by that many pairs, and uploads nothing.  drive
   // itself is the host table advanced likewise, for every path off the tiles.
@@ -124,73 +128,59 @@ int collect_sums(lbm_ctx* c, int nsteps, float* av_vels, std::chrono::steady_clo
   return LBM_OK;
 }
 
-// ----------------------------------------------------------------- forces (lbm_run_forces)
-// The register tiles' tables of a slab for tiles of ty rows and ntx columns of tiles, and room for the partials of nsteps
-// steps: slots in the order of the tiles (only tiles that hold a counted cell have one).  LBM_ENOMEM: nothing queued.
-int force_tables(lbm_ctx* c, Slab& s, int ty, int ntx, int nsteps) {
+// ----------------------------------------------------------------- the register tiles' tables (lbm_tile_table.h)
+void tile_table_free(TileTable& t) {
+  if (t.slot) (void)hipFree(t.slot);
+  if (t.words) (void)hipFree(t.words);
+  t = TileTable();
+}
+
+// Table t of a slab for tiles of ty rows and ntx columns of tiles, built from `cells` and uploaded: both arrays or neither.
+// LBM_ENOMEM (`kind`: the table's word in the message): nothing queued, the table left empty.
+int tile_table_set(Slab& s, TileTable& t, int ty, int ntx, const std::vector<TileCell>& cells, const char* kind) {
   HIPC(hipSetDevice(s.dev));
-  if (s.fty != ty) {
-    const int nty = s.nyl / ty, ntiles = ntx * nty;
-    std::vector<int> slot(ntiles, -1);
-    for (const int4& q : s.fcells_host) slot[(q.y / ty) * ntx + q.x / 64] = 0;
-    int n = 0;
-    for (int& v : slot) if (v == 0) v = n++;
-    std::vector<uint32_t> words((size_t)n * ty * 64, 0u);
-    for (const int4& q : s.fcells_host) words[((size_t)slot[(q.y / ty) * ntx + q.x / 64] * ty + q.y % ty) * 64 + q.x % 64] = (uint32_t)q.z;
-    if (s.fslot) HIPC(hipFree(s.fslot));
-    if (s.fwords) HIPC(hipFree(s.fwords));
-    s.fslot = nullptr; s.fwords = nullptr; s.fty = 0; s.fnslots = 0;
-    if (hipMalloc((void**)&s.fslot, sizeof(int) * ntiles) != hipSuccess ||
-        (n > 0 && hipMalloc((void**)&s.fwords, sizeof(uint32_t) * words.size()) != hipSuccess)) {
-      (void)hipGetLastError();
-      return fail(LBM_ENOMEM, "no room on device %d for the force tables (%d tiles)", s.dev, n);
-    }
-    HIPC(hipMemcpy(s.fslot, slot.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
-    if (n > 0) HIPC(hipMemcpy(s.fwords, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
-    s.fty = ty; s.fnslots = n;
+  std::vector<int> slot;
+  std::vector<uint32_t> words;
+  const int n = tile_table_build(ty, ntx, s.nyl / ty, cells, slot, words);
+  tile_table_free(t);
+  if (hipMalloc((void**)&t.slot, sizeof(int) * slot.size()) != hipSuccess ||
+      (n > 0 && hipMalloc((void**)&t.words, sizeof(uint32_t) * words.size()) != hipSuccess)) {
+    (void)hipGetLastError();
+    tile_table_free(t);
+    return fail(LBM_ENOMEM, "no room on device %d for the %s tables (%d tiles)", s.dev, kind, n);
   }
-  const long need = (long)nsteps * s.fnslots * 8;
-  if (need > s.fpart_cap) {
-    if (s.fpart) HIPC(hipFree(s.fpart));
-    s.fpart = nullptr; s.fpart_cap = 0;
-    if (hipMalloc((void**)&s.fpart, sizeof(float) * (size_t)need) != hipSuccess) {
-      (void)hipGetLastError();
-      s.fpart = nullptr;
-      return fail(LBM_ENOMEM, "no room on device %d for the force partials (%d steps x %d tiles)", s.dev, nsteps, s.fnslots);
-    }
-    s.fpart_cap = need;
-  }
+  HIPC(hipMemcpy(t.slot, slot.data(), sizeof(int) * slot.size(), hipMemcpyHostToDevice));
+  if (n > 0) HIPC(hipMemcpy(t.words, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
+  t.nslots = n; t.ty = ty;
   return LBM_OK;
 }
 
-// ----------------------------------------------------------------- probes (lbm_run_probes)
-// The register tiles' tables of a slab for tiles of ty rows and ntx columns of tiles: slots in the order of the tiles (only
-// tiles that hold a probe have one; a slab without probes gets the table of -1s alone).  LBM_ENOMEM: nothing queued.
-int probe_tables(lbm_ctx* c, Slab& s, int ty, int ntx) {
-  (void)c;
-  if (s.pty == ty) return LBM_OK;
-  HIPC(hipSetDevice(s.dev));
-  const int nty = s.nyl / ty, ntiles = ntx * nty;
-  std::vector<int> slot(ntiles, -1);
-  for (const int4& q : s.pcells_host) slot[(q.y / ty) * ntx + q.x / 64] = 0;
-  int n = 0;
-  for (int& v : slot) if (v == 0) v = n++;
-  std::vector<uint32_t> words((size_t)n * ty * 64, 0u);
-  for (const int4& q : s.pcells_host) words[((size_t)slot[(q.y / ty) * ntx + q.x / 64] * ty + q.y % ty) * 64 + q.x % 64] = (uint32_t)q.z + 1u;
-  if (s.pslot) HIPC(hipFree(s.pslot));
-  if (s.pwords) HIPC(hipFree(s.pwords));
-  s.pslot = nullptr; s.pwords = nullptr; s.pty = 0;
-  if (hipMalloc((void**)&s.pslot, sizeof(int) * ntiles) != hipSuccess ||
-      (n > 0 && hipMalloc((void**)&s.pwords, sizeof(uint32_t) * words.size()) != hipSuccess)) {
-    (void)hipGetLastError();
-    if (s.pslot) (void)hipFree(s.pslot);
-    s.pslot = nullptr; s.pwords = nullptr;
-    return fail(LBM_ENOMEM, "no room on device %d for the probe tables (%d tiles)", s.dev, n);
-  }
-  HIPC(hipMemcpy(s.pslot, slot.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
-  if (n > 0) HIPC(hipMemcpy(s.pwords, words.data(), sizeof(uint32_t) * words.size(), hipMemcpyHostToDevice));
-  s.pty = ty;
+// A slab's body cells / probes as the tables take them: the word is mask | label << 8 / the probe's index + 1
+std::vector<TileCell> tile_cells(const std::vector<int4>& cells, uint32_t add) {
+  std::vector<TileCell> v;
+  for (const int4& q : cells) v.push_back({q.x, q.y, (uint32_t)q.z + add});
+  return v;
+}
+
+// The force table of a slab for tiles of ty rows (kept until lbm_set_bodies or another tiling), and room for the partials of
+// nsteps steps.  LBM_ENOMEM: nothing queued.
+int force_tables(Slab& s, int ty, int ntx, int nsteps) {
+  int rc;
+  if (s.tforces.ty != ty && (rc = tile_table_set(s, s.tforces, ty, ntx, tile_cells(s.fcells_host, 0u), "force"))) return rc;
+  if (!grown_room(s, s.fpart, (long)nsteps * s.tforces.nslots * 8, 1, false))
+    return fail(LBM_ENOMEM, "no room on device %d for the force partials (%d steps x %d tiles)", s.dev, nsteps, s.tforces.nslots);
   return LBM_OK;
+}
+
+// The probe table of a slab likewise (kept until lbm_set_probes or another tiling; a slab without probes gets the table of
+// -1s alone), and the table of -1s for an observer that a piece does not want.
+int probe_tables(Slab& s, int ty, int ntx) {
+  return s.tprobes.ty == ty ? LBM_OK : tile_table_set(s, s.tprobes, ty, ntx, tile_cells(s.pcells_host, 1u), "probe");
+}
+int empty_table(Slab& s, int ty, int ntx) {
+  if (s.tnone.ty == ty) return LBM_OK;
+  const int rc = tile_table_set(s, s.tnone, ty, ntx, {}, "empty");
+  return rc == LBM_ENOMEM ? fail(rc, "no room on device %d for the empty force table (%d tiles)", s.dev, ntx * (s.nyl / ty)) : rc;
 }
 
 // Every engine but the register tiles: the forces of step tt (0-based) from the lattice just stored, on the compute stream
@@ -413,10 +403,10 @@ void regtile_free(lbm_ctx* c) {
       s.tmail_nb[side] = nullptr; s.tmail_nb_ipc[side] = false;
     }
     if (s.tmail) (void)hipFree(s.tmail);
-    if (s.rpartials) (void)hipFree(s.rpartials);
+    grown_free(s.rpartials);
     if (s.rabort) (void)hipFree(s.rabort);
     if (s.ev_rt) (void)hipEventDestroy(s.ev_rt);
-    s.tmail = nullptr; s.rpartials = nullptr; s.rabort = nullptr; s.ev_rt = nullptr; s.rpartials_cap = 0;
+    s.tmail = nullptr; s.rabort = nullptr; s.ev_rt = nullptr;
   }
   if (c->rtable) (void)hipHostFree(c->rtable);
   c->rtable = c->rtable_dev = nullptr;
@@ -431,21 +421,34 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   const auto& t = c->tplan;
   const int ns = (int)c->slabs.size(), ntiles = t.ntx * t.nty;
   const bool fast = (c->variant & lbm::kFastMath) != 0, async = c->regtile_async != 0;
-  const bool fk = k.nb > 0 && k.force_tiles;            // lbm_run_forces: the kRegForce flavour, with its larger LDS
-  const bool mk = k.snap && k.mean;                     // lbm_run_mean: the kRegMean flavour, with its larger LDS
-  const bool pk = k.snap && (k.probe || k.window);      // lbm_run_probes, lbm_run_window: the kRegProbe flavour, with its larger LDS
-  const bool fpk = k.piece;                             // lbm_run_observed: the kRegForce | kRegProbe flavour (forces counted when fk)
-  const bool dk = k.drive != nullptr;                   // lbm_run_driven: the kRegDrive flavour (the plain flavour's LDS); with fpk,
-                                                        // lbm_run_driven_observed: kRegForce | kRegProbe | kRegDrive (the force-and-probe flavour's)
-  const int flavour = fpk ? (lbm::kRegForce | lbm::kRegProbe | (dk ? lbm::kRegDrive : 0)) : fk ? lbm::kRegForce : mk ? lbm::kRegMean : pk ? lbm::kRegProbe : k.snap ? lbm::kRegSnap : dk ? lbm::kRegDrive : 0;
+  const dim3 block(64 * t.nw);
+  const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
+  // What RunKind::flavour means to a launch, all of it here: the kernel's flavour and its LDS, and the two tables of a slab it
+  // is handed -- `counted` through RegTileArgs::fslot / fwords (the probe flavour reads its probes or window there), `sampled`
+  // through pslot / pwords (the force-and-probe flavour alone).  A table nobody reads: the table of -1s, built or not.
+  const bool fpk = k.flavour == RegFlavour::piece;
+  const bool fk = k.flavour == RegFlavour::forces || (fpk && k.nb > 0);   // forces are counted: partials, and their fold behind the launch
+  const bool dk = k.drive != nullptr && (fpk || k.flavour == RegFlavour::plain);
+  int flavour = dk ? lbm::kRegDrive : 0;
+  unsigned shm_run = shm;
+  TileTable Slab::*counted = &Slab::tnone, Slab::*sampled = &Slab::tnone;
+  switch (k.flavour) {
+    case RegFlavour::plain: break;
+    case RegFlavour::snapshots: flavour = lbm::kRegSnap; break;
+    case RegFlavour::forces: flavour = lbm::kRegForce; shm_run = (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r); counted = &Slab::tforces; break;
+    case RegFlavour::mean: flavour = lbm::kRegMean; shm_run = (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r); break;
+    case RegFlavour::probes: flavour = lbm::kRegProbe; shm_run = (unsigned)lbm::regtile_lds_bytes_probe(t.nw, t.r); counted = &Slab::tprobes; break;
+    case RegFlavour::window: flavour = lbm::kRegProbe; shm_run = (unsigned)lbm::regtile_lds_bytes_probe(t.nw, t.r); counted = &Slab::twindow; break;
+    case RegFlavour::piece:
+      flavour |= lbm::kRegForce | lbm::kRegProbe; shm_run = (unsigned)lbm::regtile_lds_bytes_force_probe(t.nw, t.r);
+      if (fk) counted = &Slab::tforces;
+      if (k.snap) sampled = &Slab::tprobes;
+      break;
+  }
   auto kernel = [&](int fl) {
     return lone ? reinterpret_cast<const void*>(regtile_kernel<false>(t.r, fast, async, fl))
                 : reinterpret_cast<const void*>(regtile_kernel<true>(t.r, fast, async, fl));
   };
-  const dim3 block(64 * t.nw);
-  const unsigned shm = (unsigned)lbm::regtile_lds_bytes(t.nw, t.r);
-  const unsigned shm_run = fpk ? (unsigned)lbm::regtile_lds_bytes_force_probe(t.nw, t.r) : fk ? (unsigned)lbm::regtile_lds_bytes_force(t.nw, t.r) : mk ? (unsigned)lbm::regtile_lds_bytes_mean(t.nw, t.r)
-                                                                                    : pk ? (unsigned)lbm::regtile_lds_bytes_probe(t.nw, t.r) : shm;
   static const bool want_stats = getenv("LBM_REGTILE_STATS") != nullptr;   // development: missed polls per run
   const bool stats = lone && want_stats;
   int rc;
@@ -503,15 +506,8 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   // buffers: the mail areas, the per-step tile sums, the groups' abort words, the table of arguments
   for (auto& s : c->slabs) {
     if ((rc = regtile_mail_alloc(c, s))) return rc;
-    if (s.rpartials_cap < nsteps + (fpk ? 1 : 0)) {               // (the force + probe flavour: one row more, see RegTileArgs::pfirst)
-      HIPC(hipSetDevice(s.dev));
-      long cap = std::max(1024L, s.rpartials_cap);
-      while (cap < nsteps + (fpk ? 1 : 0)) cap *= 2;
-      if (s.rpartials) HIPC(hipFree(s.rpartials));
-      s.rpartials = nullptr; s.rpartials_cap = 0;
-      HIPC(hipMalloc((void**)&s.rpartials, sizeof(float) * (size_t)cap * ntiles));
-      s.rpartials_cap = cap;
-    }
+    if (!grown_room(s, s.rpartials, nsteps + (fpk ? 1 : 0), ntiles, true))   // (the force + probe flavour: one row more, see RegTileArgs::pfirst)
+      return fail(LBM_EHIP, "no room on device %d for the tile sums of %d steps", s.dev, nsteps);
     if ((rc = ensure_sums(s, nsteps + 1))) return rc;
   }
   for (int g = 0; g < ngroups; ++g) {
@@ -557,17 +553,15 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       a.ty = t.ty; a.ntx = t.ntx; a.nty = t.nty;
       a.nsteps = nsteps; a.tag0 = c->rtag;
       a.mail = s.tmail; a.mail_bytes = (unsigned)s.tmail_bytes;
-      a.partials = s.rpartials; a.abort_word = lead(g).rabort;
+      a.partials = s.rpartials.p; a.abort_word = lead(g).rabort;
       a.fault = (getenv("LBM_REGTILE_FAULT") && i == 0) ? 1 : 0;   // (tests: a tile that never starts)
       a.stats = nullptr;
       a.snap = k.snap ? k.snap->at[i] : nullptr; a.snap_stride = k.snap ? k.snap->stride[i] : 0; a.every = k.snap ? k.snap->every : 0;
       a.density = c->p.density;
-      a.fslot = s.fslot; a.fwords = s.fwords; a.fpart = s.fpart; a.nslots = s.fnslots;
-      if (pk && !fpk) { a.fslot = s.pslot; a.fwords = s.pwords; a.fpart = nullptr; a.nslots = 0; }   // (the probe flavour's tables: same members)
-      if (pk && !fpk && k.window) { a.fslot = s.wslot; a.fwords = s.wwords; }                        // (... fed a window's tables)
-      a.pfirst = k.pfirst; a.pslot = s.pslot; a.pwords = s.pwords;   // (the force + probe flavour's)
-      if (fpk && !pk) { a.pslot = s.fslot_none; a.pwords = nullptr; a.pfirst = 0x7fffffff; }   // (... with no probe wanted: no tile samples)
-      if (fpk && !fk) { a.fslot = s.fslot_none; a.fwords = nullptr; a.fpart = nullptr; a.nslots = 0; }   // (... with no force wanted: no tile counts)
+      a.fslot = (s.*counted).slot; a.fwords = (s.*counted).words;
+      a.fpart = fk ? s.fpart.p : nullptr; a.nslots = fk ? s.tforces.nslots : 0;
+      a.pslot = (s.*sampled).slot; a.pwords = (s.*sampled).words;
+      a.pfirst = (fpk && !k.snap) ? 0x7fffffff : k.pfirst;   // (a piece with no probe wanted: no step is a sample step)
       if (c->rank_mode && c->nranks > 1) {
         a.mail_s = s.tmail_nb[0]; a.mail_n = s.tmail_nb[1];
         a.mail_bytes_s = (unsigned)s.tmail_nb_bytes[0]; a.mail_bytes_n = (unsigned)s.tmail_nb_bytes[1];
@@ -579,11 +573,11 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       }
       a.nty_s = t.nty; a.nty_n = t.nty;
       a.drive = nullptr;
-      if (dk && fpk) a.drive = s.dtab + 2 * k.drive_at;   // (a piece: the whole call's table is there, uploaded once)
+      if (dk && fpk) a.drive = s.dtab.p + 2 * k.drive_at;   // (a piece: the whole call's table is there, uploaded once)
       else if (dk) {                  // the schedule, in front of the slab's launch on its stream: 8 bytes per step
         HIPC(hipSetDevice(s.dev));
-        HIPC(hipMemcpyAsync(s.dtab, k.drive, sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
-        a.drive = s.dtab;
+        HIPC(hipMemcpyAsync(s.dtab.p, k.drive, sizeof(float) * 2 * (size_t)nsteps, hipMemcpyHostToDevice, s.sc));
+        a.drive = s.dtab.p;
       }
     }
   static unsigned long long* stats_buf = nullptr;
@@ -614,14 +608,14 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       Slab& s = c->slabs[order[q]];
       if (q > gstart[g]) HIPC(hipStreamWaitEvent(s.sc, l.ev_rt, 0));
       if (fpk && k.piece_mid)           // a piece, not the call's last: its last step's tile sums as the loop folds them
-        HIPC(hipMemcpyAsync(s.rpartials + (size_t)(nsteps - 1) * ntiles, s.rpartials + (size_t)nsteps * ntiles, sizeof(float) * ntiles,
+        HIPC(hipMemcpyAsync(s.rpartials.p + (size_t)(nsteps - 1) * ntiles, s.rpartials.p + (size_t)nsteps * ntiles, sizeof(float) * ntiles,
                             hipMemcpyDeviceToDevice, s.sc));
       hipLaunchKernelGGL(lbm::lbm_fold_steps, dim3(cdiv(nsteps, lbm::kBlock / 64)), dim3(lbm::kBlock), 0, s.sc,
-                         s.rpartials, ntiles, nsteps, s.sums, l.rabort, s.err_host + 1);
+                         s.rpartials.p, ntiles, nsteps, s.sums, l.rabort, s.err_host + 1);
       HIPC(hipGetLastError());
       if (fk) {
         hipLaunchKernelGGL(lbm::lbm_fold_forces, dim3(cdiv(k.nval, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
-                           s.fpart, s.fnslots, nsteps, k.nb, s.sums + nsteps + 1);
+                           s.fpart.p, s.tforces.nslots, nsteps, k.nb, s.sums + nsteps + 1);
         HIPC(hipGetLastError());
       }
       HIPC(hipEventRecord(s.ev_t1, s.sc));

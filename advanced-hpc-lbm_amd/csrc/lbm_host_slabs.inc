@@ -175,6 +175,21 @@ struct DeviceTemp {
   ~DeviceTemp() { if (p) (void)hipFree(p); }
 };
 
+// A grow-only device buffer of a slab: room for at least `need` units of `per` floats, old contents not kept.  Grows to
+// exactly `need`, or (geometric) by doubling from a floor of 1024.  false: no room -- the HIP error cleared, the buffer empty.
+void grown_free(GrownBuf& b) { if (b.p) (void)hipFree(b.p); b = GrownBuf(); }
+bool grown_room(const Slab& s, GrownBuf& b, long need, size_t per, bool geometric) {
+  if (b.cap >= need) return true;
+  long cap = geometric ? std::max(1024L, b.cap) : need;
+  while (cap < need) cap *= 2;
+  if (hipSetDevice(s.dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+  grown_free(b);
+  if (hipMalloc((void**)&b.p, sizeof(float) * per * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return false; }
+  b.cap = cap;
+  return true;
+}
+void observers_free(Slab& s);   // everything a slab holds for the observer calls (lbm_host_observe.inc)
+
 // Uploads the slab's rows of the global host arrays and converts to the device layout.
 int slab_upload(lbm_ctx* c, Slab& s, const int* obstacles, const float* cells) {
   HIPC(hipSetDevice(s.dev));
@@ -359,23 +374,7 @@ void slab_free(Slab& s) {
     if (s.ev_int[i]) (void)hipEventDestroy(s.ev_int[i]);
   }
   if (s.blocked) (void)hipFree(s.blocked);
-  if (s.fcells) (void)hipFree(s.fcells);
-  if (s.fmap) (void)hipFree(s.fmap);
-  if (s.fidx) (void)hipFree(s.fidx);
-  if (s.fcontrib) (void)hipFree(s.fcontrib);
-  if (s.pmap) (void)hipFree(s.pmap);
-  if (s.fpmap) (void)hipFree(s.fpmap);
-  if (s.pidx) (void)hipFree(s.pidx);
-  if (s.fslot) (void)hipFree(s.fslot);
-  if (s.fslot_none) (void)hipFree(s.fslot_none);
-  if (s.fwords) (void)hipFree(s.fwords);
-  if (s.pcells) (void)hipFree(s.pcells);
-  if (s.pslot) (void)hipFree(s.pslot);
-  if (s.pwords) (void)hipFree(s.pwords);
-  if (s.wslot) (void)hipFree(s.wslot);
-  if (s.wwords) (void)hipFree(s.wwords);
-  if (s.fpart) (void)hipFree(s.fpart);
-  if (s.dtab) (void)hipFree(s.dtab);
+  observers_free(s);
   if (s.sums && !s.sums_direct) (void)hipFree(s.sums);
   if (s.sums_host) (void)hipHostFree(s.sums_host);
   if (s.err_host) (void)hipHostFree(s.err_host);
