@@ -37,6 +37,7 @@
 #include "lbm_wave.hip.h"
 #include "lbm_regtile.hip.h"
 #include "lbm_tile_table.h"
+#include "lbm_wave_pick.h"
 
 // ----------------------------------------------------------------- errors
 static thread_local char g_err[1024] = "";
@@ -306,6 +307,25 @@ struct lbm_ctx {
 constexpr int kT2X = 64, kT2Y = 16;
 // rows of obstacle bytes kept either side of a slab for the ghost bands of the marching kernels (the largest K)
 constexpr int kBandRows = 8;
+// The window of one lbm_run_window call (WaveWants::win): as given (validated), and as lbm_wave's window flavour tests it.
+struct WinPlan {
+  lbm_window w;
+  lbm::WaveWin wave;
+};
+// The constants of a step's accelerate phase (d2q9-bgk.c:230-231), the context's and a schedule's alike: the ONE expression,
+// which is why a schedule of equal entries leaves lbm_run's bits.
+struct AccelPair { float a1, a2; };
+static inline AccelPair accel_pair(float density, float accel) { return {density * accel / 9.f, density * accel / 36.f}; }
+static inline AccelPair accel_pair(const lbm_ctx* c) { return accel_pair(c->p.density, c->p.accel); }
+// a schedule's pairs, (a1, a2) of step t at [2 t], [2 t + 1] (RunKind::drive)
+static std::vector<float> accel_pairs(const lbm_ctx* c, const float* accel, int nsteps) {
+  std::vector<float> pairs(2 * (size_t)nsteps);
+  for (int t = 0; t < nsteps; ++t) {
+    const AccelPair p = accel_pair(c->p.density, accel[t]);
+    pairs[2 * (size_t)t] = p.a1; pairs[2 * (size_t)t + 1] = p.a2;
+  }
+  return pairs;
+}
 
 #include "lbm_host_slabs.inc"
 
@@ -659,20 +679,19 @@ extern "C" int lbm_slab_rows(const lbm_ctx* ctx, int slab, int* row_begin, int* 
 static int derive_all(lbm_ctx* c, float* out4, double* speed_sum, double* mass, bool out_on_device);
 static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k = RunKind());
 
-// May an observer run of this context take its values inside lbm_wave launches?  A lattice alone, no ranks, no exchange,
-// lbm_wave the engine of the groups of K steps, their partial sums fit.  Asked before anything is queued; no: the caller
-// keeps the split path.  (Whether a run is long enough for a group is the caller's question.)  Snapshots and means need no
-// more: the field flavour reads the plain obstacle bytes.  (run_steps' fwave states the same terms but rank_mode: a rank
-// context of one rank that trades no halos takes its forces inside lbm_wave, and keeps doing so.)
-static bool wave_admit(lbm_ctx* c) {
-  if (c->rank_mode || c->exchange != 0 || !march_eligible(c) || !use_wave_kernel(c)) return false;
-  if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
-  return (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap;
+// May a run of this context take what it wants inside lbm_wave launches?  A lattice alone, no ranks, no exchange, lbm_wave the
+// engine of the groups of K steps, their partial sums fit.  Asked before anything is queued; no: the caller keeps the split
+// (a forces run: the one-step) path.  (Whether a run is long enough for a group is the caller's question.)  Snapshots and
+// means need no more: the field flavour reads the plain obstacle bytes.  forces_run: lbm_run_forces' own admission -- a rank
+// context of one rank that trades no halos takes its forces inside lbm_wave, and keeps doing so.
+static bool wave_admit(lbm_ctx* c, bool forces_run) {
+  if ((c->rank_mode && !forces_run) || c->exchange != 0 || !march_eligible(c) || !use_wave_kernel(c)) return false;
+  return wave_partials_fit(c);
 }
 
 // ... and probes (with_forces: forces beside them): the maps in place as well.
 static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
-  return wave_admit(c) && (!with_forces || wave_force_ready(c, c->time_block)) && wave_probe_ready(c, with_forces);
+  return wave_admit(c, false) && (!with_forces || wave_force_ready(c, c->time_block)) && wave_probe_ready(c, with_forces);
 }
 
 #include "lbm_host_observe.inc"
@@ -684,8 +703,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   const int nx = c->p.nx;
-  const float a1 = c->p.density * c->p.accel / 9.f;   // d2q9-bgk.c:230-231
-  const float a2 = c->p.density * c->p.accel / 36.f;
+  const float a1 = accel_pair(c).a1, a2 = accel_pair(c).a2;
   const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour; lbm_wave in its force flavour where lbm_run would
                               // run it (fwave, below); else the one-step kernel, lbm_body_forces behind each step
   const bool dr = k.drive != nullptr;   // lbm_run_driven: the register tiles in their kRegDrive flavour; lbm_wave in its driven flavour on a
@@ -726,27 +744,20 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   int rc;
   // lbm_run_forces where lbm_run would run lbm_wave (a lattice alone): the groups of K steps in lbm_wave's force flavour.
   // Decided before anything is queued; maps, contributions or partials that do not fit: the one-step path, the same bits.
-  bool fwave = false;
-  if (fo && !ex && march_eligible(c) && use_wave_kernel(c) && nsteps >= c->time_block) {
-    if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
-    fwave = (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap && wave_force_ready(c, c->time_block);
-  }
-  // lbm_run_driven likewise: the groups of K steps in lbm_wave's driven flavour on a lattice alone (wave_admit's terms)
-  const bool dwave = dr && nsteps >= c->time_block && wave_admit(c);
+  const bool fwave = fo && nsteps >= c->time_block && wave_admit(c, true) && wave_force_ready(c, c->time_block);
+  // lbm_run_driven likewise: the groups of K steps in lbm_wave's driven flavour on a lattice alone
+  const bool dwave = dr && nsteps >= c->time_block && wave_admit(c, false);
   // (behind those groups the left-over steps go as lbm_run's do, in pairs where it takes pairs: av_vels is lbm_run's bits;
   // a driven run takes no pairs -- lbm_sweep2 has one pair of constants for its two steps)
   const bool pairs = (!fo || fwave) && !dr && t2_eligible(c) && nsteps >= 2;
-  // probes on an admitted context (RunKind::wave_pout): is step s (1-based) of this run a sample step, and its output row
-  const bool pw = k.wave_pout != nullptr;
-  auto psample = [&](int s) { return pw && s >= k.pfirst && (s - k.pfirst) % k.wave_pevery == 0; };
-  auto prow = [&](int s) { return (s - k.pfirst) / k.wave_pevery; };
-  // fields on an admitted context (RunKind::wave_fout): is step s (1-based) of this run a sample step, and its field
-  const bool fw = k.wave_fout != nullptr;
+  // probes and fields on an admitted context (RunKind::wave): is step s (1-based) of this run a sample step of theirs
+  const WaveWants& w = k.wave;
+  const bool pw = w.pout != nullptr, fw = w.fout != nullptr;
   // (the field flavour is a flavour of its own: refused before anything is queued, launch_wave would refuse it mid-run)
   if (fw && (pw || fo)) return fail(LBM_EINVAL, "run_steps: fields inside lbm_wave run beside neither probes nor forces");
   if (fw && dr) return fail(LBM_EINVAL, "run_steps: fields inside lbm_wave run under no schedule");
-  auto fsample = [&](int s) { return fw && s % k.wave_fevery == 0; };
-  auto fslot = [&](int s) { return k.wave_fout + (size_t)(s / k.wave_fevery - 1) * (size_t)k.wave_fstride; };
+  auto psample = [&](int s) { return w.psample(k.pfirst, s); };
+  auto fsample = [&](int s) { return w.fsample(s); };
   // ... a left-over step that is a sample step: the probes' cells of the lattice just stored (stored WITHOUT the next step's
   // accelerate phase, which `then_accelerate` applies behind the gather as the prologue does, to the same bits); for fields
   // likewise, the stored lattice through the kernels of the split path, lbm_derive into the sample's slot or lbm_mean_add
@@ -755,13 +766,13 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     Slab& sl = c->slabs[0];
     HIPC(hipSetDevice(sl.dev));
     int rc;
-    if (psample(s) && (rc = launch_probe_gather(c, sl, k.wave_pout + 4 * (size_t)prow(s) * (size_t)c->nprobes))) return rc;
-    if (fsample(s) && k.wave_fadd && (rc = launch_mean_add(c, sl, k.wave_fout))) return rc;
-    if (fsample(s) && k.win && (rc = launch_derive_window(c, sl, k.win->w, 0, k.win->w.ny, fslot(s)))) return rc;
-    if (fsample(s) && !k.wave_fadd && !k.win) {
+    if (psample(s) && (rc = launch_probe_gather(c, sl, w.pout + 4 * (size_t)w.prow(k.pfirst, s) * (size_t)c->nprobes))) return rc;
+    if (fsample(s) && w.fadd && (rc = launch_mean_add(c, sl, w.fout))) return rc;
+    if (fsample(s) && w.win && (rc = launch_derive_window(c, sl, w.win->w, 0, w.win->w.ny, w.fslot(s)))) return rc;
+    if (fsample(s) && !w.fadd && !w.win) {
       const long ncell = (long)sl.nyl * nx;
       hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
-                         nx, ncell, sl.blocked, c->p.density, fslot(s), k.wave_fpart, k.wave_fmass);
+                         nx, ncell, sl.blocked, c->p.density, w.fslot(s), w.fpart, w.fmass);
       HIPC(hipGetLastError());
     }
     if (then_accelerate && sl.accel_row >= 0) {
@@ -873,29 +884,14 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if ((!fo || fwave) && (!dr || dwave) && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
     const int K = c->time_block, ngroups = nsteps / K;
     const bool wave = use_wave_kernel(c);
-    for (int g = 0; g < ngroups; ++g, ++li, tt += K) {
-      WaveProbes wp;
-      if (pw && wave) {                                  // the group's sample levels and the first one's output row
-        wp.out = k.wave_pout; wp.nprobes = c->nprobes;
-        for (int l = K; l >= 1; --l)
-          if (psample(tt + l)) { wp.mask |= 1u << (l - 1); wp.row = prow(tt + l); }
-      }
-      WaveFields wf;
-      if (fw && wave) {                                  // likewise: the first sample's field
-        wf.stride = k.wave_fstride; wf.add = k.wave_fadd; wf.win = k.win ? &k.win->wave : nullptr;
-        for (int l = K; l >= 1; --l)
-          if (fsample(tt + l)) { wf.mask |= 1u << (l - 1); wf.out = fslot(tt + l); }
-      }
-      // (a driven pass from step tt: level l applies the accelerate phase of step tt + l, the last pass's level K none)
-      float drv[16] = {0.f};
-      if (dwave)
-        for (int l = 1; l <= K && tt + l < nsteps; ++l) { drv[2 * (l - 1)] = da1(tt + l); drv[2 * (l - 1) + 1] = da2(tt + l); }
-      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, wp, wf, dwave ? drv : nullptr) : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
-    }
+    for (int g = 0; g < ngroups; ++g, ++li, tt += K)
+      if ((rc = wave ? launch_wave(c, li, tt, tt + K < nsteps, g > 0, k.nb, nsteps, w, wave_group(w, k.pfirst, k.drive, tt, K, nsteps))
+                     : launch_march(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+    // what rode in those launches (forces and a schedule: admitted above, and only then do the groups run at all)
     if (fwave) c->forces_in_wave = 1;
     if (dwave) c->driven_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
-    if (fw && wave) { if (k.win) c->window_in_wave = 1; else if (k.wave_fadd) c->mean_in_wave = 1; else c->samples_in_wave = 1; }
+    if (fw && wave) (w.win ? c->window_in_wave : w.fadd ? c->mean_in_wave : c->samples_in_wave) = 1;
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -975,11 +971,7 @@ extern "C" int lbm_run_driven(lbm_ctx* c, int nsteps, float* av_vels, const floa
   c->driven_in_kernel = 0; c->driven_in_wave = 0;
   if (nsteps == 0) return run_steps(c, 0, av_vels);
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
-  std::vector<float> pairs(2 * (size_t)nsteps);
-  for (int t = 0; t < nsteps; ++t) {
-    pairs[2 * (size_t)t] = c->p.density * accel[t] / 9.f;          // d2q9-bgk.c:230-231, as run_steps makes the context's
-    pairs[2 * (size_t)t + 1] = c->p.density * accel[t] / 36.f;
-  }
+  const std::vector<float> pairs = accel_pairs(c, accel, nsteps);
   // ---- the register tiles need the table on the device: decided here, before anything is queued; no room, or a rank that
   // would not use the tiles: every rank takes the one-step path (the same bits), nobody fails
   bool in_kernel = regtile_is_next(c);
@@ -1106,7 +1098,7 @@ extern "C" int lbm_timestep(const lbm_param* params, float* cells, float* tmp_ce
   // the reference mutates `cells` (accelerate, row ny-2, d2q9-bgk.c:230-260): do the same
   // host-side so that callers relying on that side effect see it
   {
-    const float a1 = params->density * params->accel / 9.f, a2 = params->density * params->accel / 36.f;
+    const auto [a1, a2] = accel_pair(params->density, params->accel);
     const int jj = params->ny - 2;
     for (int ii = 0; ii < params->nx; ++ii) {
       float* s = cells + 9L * (ii + (long)jj * params->nx);
@@ -1208,56 +1200,45 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
 
 extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!c || !key || !value) return fail(LBM_EINVAL, "NULL argument");
-  if (!strcmp(key, "vector_width")) { *value = c->V; return LBM_OK; }
+  // the keys that read one int of the context
+  static const struct { const char* key; int lbm_ctx::*member; } plain[] = {
+      {"vector_width", &lbm_ctx::V}, {"time_block", &lbm_ctx::time_block}, {"t2_threads", &lbm_ctx::t2_threads},
+      {"wave_rows", &lbm_ctx::wave_rows}, {"wave_cols", &lbm_ctx::wave_cols}, {"wave_capacity", &lbm_ctx::wave_capacity},
+      {"engine", &lbm_ctx::engine}, {"engine_last", &lbm_ctx::engine_last}, {"compute_units", &lbm_ctx::ncu},
+      {"regtile_async", &lbm_ctx::regtile_async}, {"exchange", &lbm_ctx::exchange},
+      {"samples_in_kernel", &lbm_ctx::samples_in_kernel}, {"samples_in_wave", &lbm_ctx::samples_in_wave},
+      {"forces_in_kernel", &lbm_ctx::forces_in_kernel}, {"forces_in_wave", &lbm_ctx::forces_in_wave},
+      {"mean_in_kernel", &lbm_ctx::mean_in_kernel}, {"mean_in_wave", &lbm_ctx::mean_in_wave},
+      {"probes_in_kernel", &lbm_ctx::probes_in_kernel}, {"probes_in_wave", &lbm_ctx::probes_in_wave},
+      {"window_in_kernel", &lbm_ctx::window_in_kernel}, {"window_in_wave", &lbm_ctx::window_in_wave},
+      {"driven_in_kernel", &lbm_ctx::driven_in_kernel}, {"driven_in_wave", &lbm_ctx::driven_in_wave},
+      {"driven_observed_in_kernel", &lbm_ctx::driven_observed_in_kernel}, {"driven_observed_in_wave", &lbm_ctx::driven_observed_in_wave},
+      {"driven_observed_pieces", &lbm_ctx::driven_observed_pieces},
+      {"observed_in_kernel", &lbm_ctx::observed_in_kernel}, {"observed_in_wave", &lbm_ctx::observed_in_wave}, {"observed_pieces", &lbm_ctx::observed_pieces},
+  };
+  for (const auto& e : plain)
+    if (!strcmp(key, e.key)) { *value = c->*e.member; return LBM_OK; }
   if (!strcmp(key, "kernel_variant")) { *value = (double)c->variant; return LBM_OK; }
-  if (!strcmp(key, "time_block")) { *value = c->time_block; return LBM_OK; }
-  if (!strcmp(key, "t2_threads")) { *value = c->t2_threads; return LBM_OK; }
   if (!strcmp(key, "time_block_active")) {
     *value = (march_eligible(c) || p2p_march_on(c) || march_bands_on(c) || (c->exchange != 0 && c->exchange != LBM_EXCHANGE_P2P && march_slabs_on(const_cast<lbm_ctx*>(c))))
                  ? c->time_block : t2_eligible(c) ? 2 : 1;
     return LBM_OK;
   }
   if (!strcmp(key, "march_kernel")) { *value = ((march_eligible(c) && use_wave_kernel(c)) || (c->exchange != 0 && slab_is_wave(slab_K(c)))) ? 1 : 0; return LBM_OK; }
-  if (!strcmp(key, "wave_rows")) { *value = c->wave_rows; return LBM_OK; }
-  if (!strcmp(key, "wave_cols")) { *value = c->wave_cols; return LBM_OK; }
   if (!strcmp(key, "wave_cols_active")) { *value = wave_C(c, c->time_block); return LBM_OK; }   // what lbm_wave<time_block> would run with
   if (!strcmp(key, "wave_out_cols")) { *value = wave_out_cols(c, c->time_block); return LBM_OK; }
-  if (!strcmp(key, "wave_capacity")) { *value = c->wave_capacity; return LBM_OK; }
   if (!strcmp(key, "march_rows")) { *value = c->march_rows > 0 ? c->march_rows : march_pick_rows(c); return LBM_OK; }
   if (!strcmp(key, "fluid_cells")) { *value = (double)c->tot_fluid; return LBM_OK; }
-  if (!strcmp(key, "engine")) { *value = c->engine; return LBM_OK; }
-  if (!strcmp(key, "engine_last")) { *value = c->engine_last; return LBM_OK; }
-  if (!strcmp(key, "samples_in_kernel")) { *value = c->samples_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "forces_in_kernel")) { *value = c->forces_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "forces_in_wave")) { *value = c->forces_in_wave; return LBM_OK; }
-  if (!strcmp(key, "mean_in_kernel")) { *value = c->mean_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "samples_in_wave")) { *value = c->samples_in_wave; return LBM_OK; }
-  if (!strcmp(key, "mean_in_wave")) { *value = c->mean_in_wave; return LBM_OK; }
   if (!strcmp(key, "wave_launches")) { *value = (double)c->wave_launches; return LBM_OK; }
-  if (!strcmp(key, "probes_in_kernel")) { *value = c->probes_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "probes_in_wave")) { *value = c->probes_in_wave; return LBM_OK; }
-  if (!strcmp(key, "window_in_kernel")) { *value = c->window_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "window_in_wave")) { *value = c->window_in_wave; return LBM_OK; }
   if (!strcmp(key, "accel")) { *value = (double)c->p.accel; return LBM_OK; }
-  if (!strcmp(key, "driven_in_kernel")) { *value = c->driven_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "driven_in_wave")) { *value = c->driven_in_wave; return LBM_OK; }
-  if (!strcmp(key, "driven_observed_in_kernel")) { *value = c->driven_observed_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "driven_observed_in_wave")) { *value = c->driven_observed_in_wave; return LBM_OK; }
-  if (!strcmp(key, "driven_observed_pieces")) { *value = c->driven_observed_pieces; return LBM_OK; }
-  if (!strcmp(key, "observed_in_wave")) { *value = c->observed_in_wave; return LBM_OK; }
-  if (!strcmp(key, "observed_in_kernel")) { *value = c->observed_in_kernel; return LBM_OK; }
-  if (!strcmp(key, "observed_pieces")) { *value = c->observed_pieces; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first
     *value = regtile_is_next(c) ? 3 : 1;
     return LBM_OK;
   }
   if (!strcmp(key, "resident_fallback")) { *value = c->resident_broken ? 1 : 0; return LBM_OK; }   // 1: the resident kernel could not run here
   if (!strcmp(key, "regtile_blocks_per_cu")) { *value = c->tplan.bpc; return LBM_OK; }   // occupancy answer (0: not asked yet)
-  if (!strcmp(key, "compute_units")) { *value = c->ncu; return LBM_OK; }
   if (!strcmp(key, "regtile")) { *value = c->tplan.ty * 10.0 + c->tplan.r; return LBM_OK; }
-  if (!strcmp(key, "regtile_async")) { *value = c->regtile_async; return LBM_OK; }
   if (!strcmp(key, "regtile_tag")) { *value = c->rtag; return LBM_OK; }
-  if (!strcmp(key, "exchange")) { *value = c->exchange; return LBM_OK; }
   if (!strcmp(key, "pitch")) { *value = c->slabs[0].pitch; return LBM_OK; }
   if (!strcmp(key, "hbm_bytes")) {
     double b = 0;

@@ -170,7 +170,7 @@ int launch_march(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev) {
   a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = c->p.ny;
   a.blocked = s.blocked; a.omega = c->p.omega;
   a.accel_row = c->p.ny - 2; a.accel_out = accel_out ? 1 : 0;
-  a.a1 = c->p.density * c->p.accel / 9.f; a.a2 = c->p.density * c->p.accel / 36.f;
+  a.a1 = accel_pair(c).a1; a.a2 = accel_pair(c).a2;
   a.H = c->march_rows;
   a.nstrips = cdiv(c->p.nx, Cfg::WOUT); a.nchunks = cdiv(c->p.ny, a.H);
   const int nb = a.nstrips * a.nchunks;
@@ -281,7 +281,7 @@ struct SlabNb { const float* src_s; const float* src_n; long plane_s, plane_n; i
 
 // One marching launch on one slab: steps tt .. tt+K-1, partial sums into buffer q (folding the previous launch's).
 int launch_slab_pass(lbm_ctx* c, Slab& s, const SlabNb& nbr, int K, int q, int tt, bool accel_out, bool fold_prev) {
-  const float a1 = c->p.density * c->p.accel / 9.f, a2 = c->p.density * c->p.accel / 36.f;
+  const auto [a1, a2] = accel_pair(c);
   const int nb = march_slab_blocks(c, s), qp = q ^ 1;
   if ((long)K * nb > s.partial_cap) return fail(LBM_EINVAL, "marching kernel: %d blocks exceed the partial-sum buffer", nb);
   // the lattice's accelerate row (ny-2) in this slab's row numbers, and its periodic images: one of them may fall
@@ -304,7 +304,7 @@ int launch_slab_pass(lbm_ctx* c, Slab& s, const SlabNb& nbr, int K, int q, int t
     a.src_s = nbr.src_s; a.src_n = nbr.src_n; a.plane_s = nbr.plane_s; a.plane_n = nbr.plane_n;
     a.ny_s = nbr.ny_s; a.ny_n = nbr.ny_n; a.blocked_s = nbr.blk_s; a.blocked_n = nbr.blk_n;
     a.acc_rows[0] = ar; a.acc_rows[1] = ar - c->p.ny; a.acc_rows[2] = ar + c->p.ny;
-    hipLaunchKernelGGL(wave_kernel(K, true, wave_C(c, K), flavour), dim3(nb), dim3(lbm::kWaveBlock), 0, s.sc, a);
+    hipLaunchKernelGGL(wave_kernel(K, true, wave_C(c, K), flavour, WaveFlavour::plain), dim3(nb), dim3(lbm::kWaveBlock), 0, s.sc, a);
   } else {
     using Cfg = lbm::MarchCfg<kMarchK>;
     lbm::MarchArgs a;
@@ -450,7 +450,7 @@ int launch_band_rows(lbm_ctx* c, Slab& s, const BandPlan& b, bool edge, int q, i
   a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = s.nyl;
   a.blocked = s.blocked; a.omega = c->p.omega;
   a.accel_row = lbm::kNoRow; a.accel_out = accel_out ? 1 : 0;
-  a.a1 = c->p.density * c->p.accel / 9.f; a.a2 = c->p.density * c->p.accel / 36.f;
+  a.a1 = accel_pair(c).a1; a.a2 = accel_pair(c).a2;
   if (edge) {
     a.H = b.he; a.y_begin = 0; a.y_end = b.he; a.nchunks_a = 1; a.yb_begin = s.nyl - b.he; a.yb_end = s.nyl; a.nchunks = 2;
   } else {
@@ -467,7 +467,7 @@ int launch_band_rows(lbm_ctx* c, Slab& s, const BandPlan& b, bool edge, int q, i
   a.blocked_s = s.band_blk_s + (size_t)(kBandRows - K) * s.pitch; a.blocked_n = s.band_blk_n;
   const int ar = (c->p.ny - 2) - s.row0;
   a.acc_rows[0] = ar; a.acc_rows[1] = ar - c->p.ny; a.acc_rows[2] = ar + c->p.ny;
-  hipLaunchKernelGGL(wave_kernel(K, true, wave_C(c, K), (int)(c->variant & (lbm::kFastMath | lbm::kNtStore))),
+  hipLaunchKernelGGL(wave_kernel(K, true, wave_C(c, K), (int)(c->variant & (lbm::kFastMath | lbm::kNtStore)), WaveFlavour::plain),
                      dim3(nblocks), dim3(lbm::kWaveBlock), 0, st, a);
   HIPC(hipGetLastError());
   return LBM_OK;
@@ -500,126 +500,58 @@ int launch_band_group(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev
 }
 
 // ---- lbm_wave: K steps per pass, one wave per strip of 64 (or 128) columns
-// The instantiations: a lattice alone (K = 4, 6, 8 with one column per lane, K = 8 with two) and a slab with neighbours
-// (K = 8, one or two columns); flavour = IEEE or fast rcp / sqrt (bit 0) x nontemporal stores (bit 1).
-template <int K, bool SLAB, int C>
-wave_fn wave_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, SLAB, C>;
-    case 1: return lbm::lbm_wave<K, 1, SLAB, C>;
-    case 2: return lbm::lbm_wave<K, 2, SLAB, C>;
-    default: return lbm::lbm_wave<K, 3, SLAB, C>;
+// The instantiations: a lattice alone (K = 4, 6, 8 with one column per lane, K = 8 with two) in every flavour, and a slab with
+// neighbours (K = 8, one or two columns) in the plain one; math = IEEE or fast rcp / sqrt (bit 0) x nontemporal stores (bit 1).
+// What a flavour (lbm_wave_pick.h) switches on in the kernel, by lbm_wave's template parameters:
+struct WaveTraits { bool FORCE, PROBE, FIELD, WINDOW, DRIVEN; };
+constexpr WaveTraits kWaveTraits[8] = {
+    /* plain           */ {false, false, false, false, false},
+    /* force           */ {true, false, false, false, false},    // lbm_run_forces
+    /* probe           */ {false, true, false, false, false},    // lbm_run_probes
+    /* force_probe     */ {true, true, false, false, false},     // lbm_run_observed's forces and probes
+    /* field           */ {false, false, true, false, false},    // lbm_run_sampled, lbm_run_mean
+    /* window          */ {false, false, false, true, false},    // lbm_run_window
+    /* driven          */ {false, false, false, false, true},    // lbm_run_driven
+    /* driven_observed */ {true, true, false, false, true},      // lbm_run_driven_observed
+};
+template <int K, bool SLAB, int C, WaveFlavour F>
+wave_fn wave_kernel_m(int math) {
+  constexpr WaveTraits t = kWaveTraits[(int)F];
+  switch (math & 3) {
+    case 0: return lbm::lbm_wave<K, 0, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
+    case 1: return lbm::lbm_wave<K, 1, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
+    case 2: return lbm::lbm_wave<K, 2, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
+    default: return lbm::lbm_wave<K, 3, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
   }
 }
-wave_fn wave_kernel(int K, bool slab, int C, int flavour) {
-  if (slab) return C == 2 ? wave_kernel_f<8, true, 2>(flavour) : wave_kernel_f<8, true, 1>(flavour);     // (K = 8 only)
-  if (K == 8) return C == 2 ? wave_kernel_f<8, false, 2>(flavour) : wave_kernel_f<8, false, 1>(flavour);
-  if (K == 6) return wave_kernel_f<6, false, 1>(flavour);
-  return wave_kernel_f<4, false, 1>(flavour);
+template <WaveFlavour F>
+wave_fn wave_kernel_kc(int K, bool slab, int C, int math) {
+  if constexpr (F == WaveFlavour::plain)
+    if (slab) return C == 2 ? wave_kernel_m<8, true, 2, F>(math) : wave_kernel_m<8, true, 1, F>(math);     // (K = 8 only)
+  if (K == 8) return C == 2 ? wave_kernel_m<8, false, 2, F>(math) : wave_kernel_m<8, false, 1, F>(math);
+  if (K == 6) return wave_kernel_m<6, false, 1, F>(math);
+  return wave_kernel_m<4, false, 1, F>(math);
 }
-
-// ... and their force flavour (lbm_run_forces): the lone-lattice forms only
-template <int K, int C>
-wave_fn wave_force_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, false, C, true>;
-    case 1: return lbm::lbm_wave<K, 1, false, C, true>;
-    case 2: return lbm::lbm_wave<K, 2, false, C, true>;
-    default: return lbm::lbm_wave<K, 3, false, C, true>;
+// (the cases in the order in which the flavours came to the code object: it keeps its kernels in that order)
+wave_fn wave_kernel(int K, bool slab, int C, int math, WaveFlavour f) {
+  switch (f) {
+    case WaveFlavour::plain: return wave_kernel_kc<WaveFlavour::plain>(K, slab, C, math);
+    case WaveFlavour::force: return wave_kernel_kc<WaveFlavour::force>(K, slab, C, math);
+    case WaveFlavour::field: return wave_kernel_kc<WaveFlavour::field>(K, slab, C, math);
+    case WaveFlavour::driven: return wave_kernel_kc<WaveFlavour::driven>(K, slab, C, math);
+    case WaveFlavour::driven_observed: return wave_kernel_kc<WaveFlavour::driven_observed>(K, slab, C, math);
+    case WaveFlavour::window: return wave_kernel_kc<WaveFlavour::window>(K, slab, C, math);
+    case WaveFlavour::force_probe: return wave_kernel_kc<WaveFlavour::force_probe>(K, slab, C, math);
+    case WaveFlavour::probe: return wave_kernel_kc<WaveFlavour::probe>(K, slab, C, math);
   }
-}
-wave_fn wave_force_kernel(int K, int C, int flavour) {
-  if (K == 8) return C == 2 ? wave_force_kernel_f<8, 2>(flavour) : wave_force_kernel_f<8, 1>(flavour);
-  if (K == 6) return wave_force_kernel_f<6, 1>(flavour);
-  return wave_force_kernel_f<4, 1>(flavour);
-}
-
-// ... and their probe flavours (lbm_run_probes; with forces: lbm_run_observed's forces and probes)
-template <int K, int C, bool FORCE>
-wave_fn wave_probe_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, false, C, FORCE, true>;
-    case 1: return lbm::lbm_wave<K, 1, false, C, FORCE, true>;
-    case 2: return lbm::lbm_wave<K, 2, false, C, FORCE, true>;
-    default: return lbm::lbm_wave<K, 3, false, C, FORCE, true>;
-  }
-}
-template <bool FORCE>
-wave_fn wave_probe_kernel(int K, int C, int flavour) {
-  if (K == 8) return C == 2 ? wave_probe_kernel_f<8, 2, FORCE>(flavour) : wave_probe_kernel_f<8, 1, FORCE>(flavour);
-  if (K == 6) return wave_probe_kernel_f<6, 1, FORCE>(flavour);
-  return wave_probe_kernel_f<4, 1, FORCE>(flavour);
-}
-
-// ... and their field flavour (lbm_run_sampled / lbm_run_mean): the lone-lattice forms only
-template <int K, int C>
-wave_fn wave_field_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, false, C, false, false, true>;
-    case 1: return lbm::lbm_wave<K, 1, false, C, false, false, true>;
-    case 2: return lbm::lbm_wave<K, 2, false, C, false, false, true>;
-    default: return lbm::lbm_wave<K, 3, false, C, false, false, true>;
-  }
-}
-wave_fn wave_field_kernel(int K, int C, int flavour) {
-  if (K == 8) return C == 2 ? wave_field_kernel_f<8, 2>(flavour) : wave_field_kernel_f<8, 1>(flavour);
-  if (K == 6) return wave_field_kernel_f<6, 1>(flavour);
-  return wave_field_kernel_f<4, 1>(flavour);
-}
-
-// ... and their driven flavour (lbm_run_driven): the lone-lattice forms only, the set the force flavour has
-template <int K, int C>
-wave_fn wave_driven_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, false, C, false, false, false, false, true>;
-    case 1: return lbm::lbm_wave<K, 1, false, C, false, false, false, false, true>;
-    case 2: return lbm::lbm_wave<K, 2, false, C, false, false, false, false, true>;
-    default: return lbm::lbm_wave<K, 3, false, C, false, false, false, false, true>;
-  }
-}
-wave_fn wave_driven_kernel(int K, int C, int flavour) {
-  if (K == 8) return C == 2 ? wave_driven_kernel_f<8, 2>(flavour) : wave_driven_kernel_f<8, 1>(flavour);
-  if (K == 6) return wave_driven_kernel_f<6, 1>(flavour);
-  return wave_driven_kernel_f<4, 1>(flavour);
-}
-
-// ... and the driven force-and-probe flavour (lbm_run_driven_observed): the same set
-template <int K, int C>
-wave_fn wave_driven_observed_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, false, C, true, true, false, false, true>;
-    case 1: return lbm::lbm_wave<K, 1, false, C, true, true, false, false, true>;
-    case 2: return lbm::lbm_wave<K, 2, false, C, true, true, false, false, true>;
-    default: return lbm::lbm_wave<K, 3, false, C, true, true, false, false, true>;
-  }
-}
-wave_fn wave_driven_observed_kernel(int K, int C, int flavour) {
-  if (K == 8) return C == 2 ? wave_driven_observed_kernel_f<8, 2>(flavour) : wave_driven_observed_kernel_f<8, 1>(flavour);
-  if (K == 6) return wave_driven_observed_kernel_f<6, 1>(flavour);
-  return wave_driven_observed_kernel_f<4, 1>(flavour);
-}
-
-// ... and their window flavour (lbm_run_window): the lone-lattice forms only, where the field flavour is instantiated
-template <int K, int C>
-wave_fn wave_window_kernel_f(int flavour) {
-  switch (flavour & 3) {
-    case 0: return lbm::lbm_wave<K, 0, false, C, false, false, false, true>;
-    case 1: return lbm::lbm_wave<K, 1, false, C, false, false, false, true>;
-    case 2: return lbm::lbm_wave<K, 2, false, C, false, false, false, true>;
-    default: return lbm::lbm_wave<K, 3, false, C, false, false, false, true>;
-  }
-}
-wave_fn wave_window_kernel(int K, int C, int flavour) {
-  if (K == 8) return C == 2 ? wave_window_kernel_f<8, 2>(flavour) : wave_window_kernel_f<8, 1>(flavour);
-  if (K == 6) return wave_window_kernel_f<6, 1>(flavour);
-  return wave_window_kernel_f<4, 1>(flavour);
+  return nullptr;
 }
 
 int wave_blocks_per_cu(int K, int C) {
   static int cache[16][3] = {};                 // (the answer does not change; lbm_set_option asks often)
   if (K < 16 && C < 3 && cache[K][C] > 0) return cache[K][C];
   int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(wave_kernel(K, false, C, 1)), lbm::kWaveBlock, 0) != hipSuccess) { (void)hipGetLastError(); n = 0; }
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(wave_kernel(K, false, C, 1, WaveFlavour::plain)), lbm::kWaveBlock, 0) != hipSuccess) { (void)hipGetLastError(); n = 0; }
   if (K < 16 && C < 3) cache[K][C] = n;
   return n;
 }
@@ -636,6 +568,13 @@ void wave_plan(lbm_ctx* c) {
   if (c->wave_rows > 0) return;
   c->wave_rows = (K == 8) ? slab_wave_rows(c, c->p.ny, 8) : std::min(c->p.ny, K >= 6 ? 64 : 32);   // (K = 8: whole rounds of the chip's wave slots)
 }
+// The blocks of one lbm_wave launch on the lone slab (the chunk heights chosen first, where they are not yet), and the bound
+// admission, launch_wave and check_march_partials ask about: their partial sums, K floats per block, fit the slab's buffer.
+inline int wave_blocks(lbm_ctx* c) {
+  if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
+  return cdiv((long)cdiv(c->p.nx, wave_out_cols(c, c->time_block)) * cdiv(c->p.ny, c->wave_rows), lbm::kWaveBlock / 64);
+}
+inline bool wave_partials_fit(lbm_ctx* c) { return (long)c->time_block * wave_blocks(c) <= c->slabs[0].partial_cap; }
 
 // The force flavour's buffers of the lone slab: the force map and the index map (built at the first forces run that wants
 // them, freed with fcells by lbm_set_bodies) and the contributions of one group of K steps (the stream orders the fold of
@@ -698,96 +637,51 @@ bool wave_probe_ready(lbm_ctx* c, bool with_forces) {
   return s.pmap || build(s.pmap, s.blocked);
 }
 
-// What a launch of the probe flavours is told (RunKind::wave_pout; nullptr: no probes): the sample levels of its K steps
-// (bit l - 1: step tt + l), the output row of the first of them, row 0 of the output, the probes in the set.
-struct WaveProbes {
-  float* out = nullptr;
-  unsigned mask = 0u;
-  int row = 0, nprobes = 0;
-};
-
-// What a launch of the field flavour is told (RunKind::wave_fout; nullptr: no fields): the sample levels of its K steps (bit
-// l - 1: step tt + l), the field of the first of them, the floats from one sample's field to the next, store or add.
-// win (lbm_run_window): the window flavour instead -- out and stride are then of windows, and nothing is added.
-struct WaveFields {
-  float* out = nullptr;
-  unsigned mask = 0u;
-  long stride = 0;
-  bool add = false;
-  const lbm::WaveWin* win = nullptr;
-};
-
-// One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li.  nb > 0 (lbm_run_forces, wave_force_ready
-// said yes): the force flavour, and behind it the fold of the group's forces into the run's sums (of nsteps steps).
-// wp.out (wave_probe_ready said yes): the probe flavour, or the force-and-probe flavour; a group without a sample step
-// runs what it would run without probes.  wf.out (wave_admit said yes; no forces, no probes beside it): the field
-// flavour (wf.win: the window flavour) for a group that holds a sample step, the plain kernel for one that holds none.
-// drv (lbm_run_driven): the driven flavour -- drv[2 (l - 1)], drv[2 (l - 1) + 1] = the constants level l applies, K pairs.
-// drv beside forces (nb_bodies > 0) or probes (wp.out; lbm_run_driven_observed): EVERY group runs the driven force-and-probe
-// flavour, a sample step in it or not, on the map that marks what is wanted (an observer that is not wanted: nothing marked).
-// drv beside fields: refused (run_steps refuses it before anything is queued).
-int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies = 0, int nsteps = 0, WaveProbes wp = WaveProbes(),
-                WaveFields wf = WaveFields(), const float* drv = nullptr) {
+// One lbm_wave launch: steps tt .. tt+K-1 of the lone slab, launch index li; w: what the run wants from its groups, g: what
+// this one is told (lbm_wave_pick.h).  Which flavour runs on which obstacle map is wave_pick's answer; here its arguments
+// are filled.  nb_bodies > 0 (lbm_run_forces, wave_force_ready said yes): behind the launch, the fold of the group's forces
+// into the run's sums (of nsteps steps).  Probes and fields: wave_probe_ready / wave_admit said yes.
+int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int nb_bodies, int nsteps, const WaveWants& w, const WaveGroup& g) {
   Slab& s = c->slabs[0];
   HIPC(hipSetDevice(s.dev));
   const int K = c->time_block;
-  if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
+  const int nb = wave_blocks(c);
   const int q = li & 1, qp = q ^ 1;
   lbm::WaveArgs a;
   a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
   a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = c->p.ny;
-  a.blocked = s.blocked; a.omega = c->p.omega;
+  a.omega = c->p.omega;
   a.accel_row = c->p.ny - 2; a.accel_out = accel_out ? 1 : 0;
-  a.a1 = c->p.density * c->p.accel / 9.f; a.a2 = c->p.density * c->p.accel / 36.f;
+  a.a1 = accel_pair(c).a1; a.a2 = accel_pair(c).a2;
   a.H = c->wave_rows;
   a.y_begin = 0; a.y_end = c->p.ny;
   a.nwc = cdiv(c->p.nx, wave_out_cols(c, K)); a.nchunks = cdiv(c->p.ny, a.H);
   a.nchunks_a = a.nchunks; a.yb_begin = a.yb_end = 0;
-  const int nb = cdiv((long)a.nwc * a.nchunks, lbm::kWaveBlock / 64);
-  if ((long)K * nb > s.partial_cap) return fail(LBM_EINVAL, "lbm_wave: %d blocks exceed the partial-sum buffer (raise wave_rows)", nb);
+  if (!wave_partials_fit(c)) return fail(LBM_EINVAL, "lbm_wave: %d blocks exceed the partial-sum buffer (raise wave_rows)", nb);
   a.partials = s.partials[q]; a.pstride = nb; a.pbase = 0;
   a.prev = nullptr; a.prev_count = 0; a.prev_sum = nullptr;
   if (fold_prev) { a.prev = s.partials[qp]; a.prev_count = nb; a.prev_sum = s.sums + (tt - K); }
   // (development: LBM_WAVE_PAD_LDS = bytes of unused dynamic LDS per block, to hold fewer blocks on a CU than the registers
   // allow -- how the rate depends on the waves per SIMD: profiles/r03_wave_occupancy.log)
   static const int pad_lds = getenv("LBM_WAVE_PAD_LDS") ? atoi(getenv("LBM_WAVE_PAD_LDS")) : 0;
-  const int flavour = (int)(c->variant & (lbm::kFastMath | lbm::kNtStore));
+  const WavePick p = wave_pick(g.driven, nb_bodies > 0, s.fcells_n > 0, w.pout != nullptr, g.pmask != 0u, w.fout != nullptr, g.fmask != 0u, w.win != nullptr);
+  if (p.refused) return fail(LBM_EINVAL, g.driven ? "lbm_wave: the driven flavour runs beside no fields" : "lbm_wave: the field flavour runs beside neither forces nor probes");
+  a.blocked = p.map == WaveMap::fpmap ? s.fpmap : p.map == WaveMap::pmap ? s.pmap : p.map == WaveMap::fmap ? s.fmap : s.blocked;
   a.fidx = nullptr; a.fcells = nullptr; a.contrib = nullptr; a.fcells_n = 0;
+  if (p.forces) { a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n; }
   a.pidx = nullptr; a.pout = nullptr; a.nprobes = 0; a.pmask = 0u; a.prow = 0; a.density = c->p.density;
+  if (g.pmask != 0u) { a.pidx = s.pidx; a.pout = w.pout; a.nprobes = c->nprobes; a.pmask = g.pmask; a.prow = g.prow; }
   a.fmask = 0u; a.fout = nullptr; a.fstride = 0; a.fadd = 0;
   a.win = lbm::WaveWin{0, 0, 0, 1u, 1u, 0u, 0u, 0u, 0u};
-  for (int i = 0; i < 16; ++i) a.drv[i] = (drv && i < 2 * K) ? drv[i] : 0.f;
-  if (drv && wf.out != nullptr) return fail(LBM_EINVAL, "lbm_wave: the driven flavour runs beside no fields");
-  const bool probes = wp.out != nullptr && wp.mask != 0u;
-  const bool fields = wf.out != nullptr && wf.mask != 0u;
-  if (fields && (wp.out != nullptr || nb_bodies > 0)) return fail(LBM_EINVAL, "lbm_wave: the field flavour runs beside neither forces nor probes");
-  if (probes) { a.pidx = s.pidx; a.pout = wp.out; a.nprobes = wp.nprobes; a.pmask = wp.mask; a.prow = wp.row; }
-  // (every launch of a wave kernel goes through here and is counted: info "wave_launches", one per group of K steps)
-  auto launch = [&](wave_fn f) {
-    hipLaunchKernelGGL(f, dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
-    ++c->wave_launches;
-  };
-  if (drv && (nb_bodies > 0 || wp.out != nullptr)) {
-    const bool counted = nb_bodies > 0 && s.fcells_n > 0;
-    a.blocked = wp.out != nullptr ? (counted ? s.fpmap : s.pmap) : (counted ? s.fmap : s.blocked);
-    if (counted) { a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n; }
-    launch(wave_driven_observed_kernel(K, wave_C(c, K), flavour));
-  } else if (drv) launch(wave_driven_kernel(K, wave_C(c, K), flavour));
-  else if (fields) {
-    a.fmask = wf.mask; a.fout = wf.out; a.fstride = wf.stride; a.fadd = wf.add ? 1 : 0;
-    if (wf.win) { a.fadd = 0; a.win = *wf.win; launch(wave_window_kernel(K, wave_C(c, K), flavour)); }
-    else launch(wave_field_kernel(K, wave_C(c, K), flavour));
-  } else if (probes && nb_bodies > 0 && s.fcells_n > 0) {
-    a.blocked = s.fpmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n;
-    launch(wave_probe_kernel<true>(K, wave_C(c, K), flavour));
-  } else if (probes) {
-    a.blocked = s.pmap;
-    launch(wave_probe_kernel<false>(K, wave_C(c, K), flavour));
-  } else if (nb_bodies > 0 && s.fcells_n > 0) {
-    a.blocked = s.fmap; a.fidx = s.fidx; a.fcells = s.fcells; a.contrib = s.fcontrib.p; a.fcells_n = s.fcells_n;
-    launch(wave_force_kernel(K, wave_C(c, K), flavour));
-  } else
-    launch(wave_kernel(K, false, wave_C(c, K), flavour));
+  if (g.fmask != 0u) {
+    a.fmask = g.fmask; a.fout = g.fout; a.fstride = w.fstride; a.fadd = (w.fadd && !w.win) ? 1 : 0;
+    if (w.win) a.win = w.win->wave;
+  }
+  for (int i = 0; i < 16; ++i) a.drv[i] = g.drv[i];
+  // (every launch of a wave kernel on a lattice alone goes through here and is counted: info "wave_launches", one per group of K steps)
+  hipLaunchKernelGGL(wave_kernel(K, false, wave_C(c, K), (int)(c->variant & (lbm::kFastMath | lbm::kNtStore)), p.flavour),
+                     dim3(nb), dim3(lbm::kWaveBlock), pad_lds, s.sc, a);
+  ++c->wave_launches;
   HIPC(hipGetLastError());
   if (nb_bodies > 0) {
     hipLaunchKernelGGL(lbm::lbm_fold_wave_forces, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.fcontrib.p, s.fcells, s.fcells_n, nb_bodies,
@@ -796,9 +690,6 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   }
   c->cur ^= 1;
   return LBM_OK;
-}
-inline int wave_blocks(const lbm_ctx* c) {
-  return cdiv((long)cdiv(c->p.nx, wave_out_cols(c, c->time_block)) * cdiv(c->p.ny, c->wave_rows), lbm::kWaveBlock / 64);
 }
 
 // The blocks of one marching launch must fit the per-block partial sums (K floats per block).  Asked BEFORE anything
@@ -812,16 +703,15 @@ int check_march_partials(lbm_ctx* c, bool slabs_march) {
       if ((long)K * nb > s.partial_cap) return fail(LBM_EINVAL, "marching kernel: %ld blocks exceed the partial-sum buffer (raise wave_rows / march_rows)", nb);
     }
   } else if (march_eligible(c)) {
-    const int K = c->time_block;
     long nb;
-    if (use_wave_kernel(c)) {
-      if (c->wave_rows <= 0 || c->wave_capacity <= 0) wave_plan(c);
-      nb = wave_blocks(c);
-    } else {
+    bool fit;
+    if (use_wave_kernel(c)) { nb = wave_blocks(c); fit = wave_partials_fit(c); }
+    else {
       if (c->march_rows <= 0) c->march_rows = march_pick_rows(c);
       nb = (long)cdiv(c->p.nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
+      fit = c->time_block * nb <= c->slabs[0].partial_cap;
     }
-    if ((long)K * nb > c->slabs[0].partial_cap)
+    if (!fit)
       return fail(LBM_EINVAL, "marching kernel: %ld blocks exceed the partial-sum buffer (raise wave_rows / march_rows)", nb);
   }
   return LBM_OK;

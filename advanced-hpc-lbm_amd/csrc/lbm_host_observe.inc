@@ -339,7 +339,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
   // lbm_wave's field flavour, which stores every delivered cell's fields at the sample levels of a pass; lbm_derive behind
   // the left-over steps that are sample steps.  Device output is written in place, host output goes through one staging of
   // the m snapshots.  Decided here, before anything is queued; a staging that does not fit: the pieces below, the same bits.
-  if (nsteps >= c->time_block && wave_admit(c)) {
+  if (nsteps >= c->time_block && wave_admit(c, false)) {
     Slab& s = c->slabs[0];
     HIPC(hipSetDevice(s.dev));
     DeviceTemp stage, part;
@@ -351,8 +351,8 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
     if (!room) (void)hipGetLastError();
     else {
       RunKind k;
-      k.no_tiles = true; k.wave_fout = on_dev ? fields_out : (float*)stage.p; k.wave_fevery = every; k.wave_fstride = slot;
-      k.wave_fmass = (double*)part.p; k.wave_fpart = (float*)(k.wave_fmass + nblk);
+      k.no_tiles = true; k.wave.fout = on_dev ? fields_out : (float*)stage.p; k.wave.fevery = every; k.wave.fstride = slot;
+      k.wave.fmass = (double*)part.p; k.wave.fpart = (float*)(k.wave.fmass + nblk);
       if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
       if (!on_dev) HIPC(hipMemcpy(fields_out, stage.p, sizeof(float) * (size_t)m * (size_t)slot, hipMemcpyDeviceToHost));
       return LBM_OK;
@@ -475,9 +475,9 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
   // lbm_wave's field flavour, which adds every delivered cell's fields to the slab's sums at the sample levels of a pass, in
   // the order of the steps; lbm_mean_add behind the left-over steps that are sample steps.  The same adds in the same order
   // as below.
-  if (nsteps >= c->time_block && wave_admit(c)) {
+  if (nsteps >= c->time_block && wave_admit(c, false)) {
     RunKind k;
-    k.no_tiles = true; k.wave_fout = mo.sums(0); k.wave_fevery = every; k.wave_fstride = 0; k.wave_fadd = true;
+    k.no_tiles = true; k.wave.fout = mo.sums(0); k.wave.fevery = every; k.wave.fstride = 0; k.wave.fadd = true;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     return mo.finish(m);
   }
@@ -573,7 +573,7 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
   // Decided here, before anything is queued; maps or partials that do not fit: the pieces below, the same bits.
   if (nsteps >= c->time_block && wave_probes_admit(c, false)) {
     RunKind k;
-    k.no_tiles = true; k.wave_pout = po.at(0, 0); k.wave_pevery = every; k.pfirst = every;
+    k.no_tiles = true; k.wave.pout = po.at(0, 0); k.wave.pevery = every; k.pfirst = every;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     return po.to_host();
   }
@@ -796,9 +796,9 @@ extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every,
   // ---- where lbm_run would run lbm_wave (a lattice alone; admission as lbm_run_sampled's): ONE run, the groups of K steps
   // that hold a sample step in lbm_wave's window flavour, lbm_derive_window behind the left-over steps that are sample steps.
   // Device output is written in place, host output goes through the one staging of the m windows.
-  if (staged && wave_exact && nsteps >= c->time_block && wave_admit(c)) {
+  if (staged && wave_exact && nsteps >= c->time_block && wave_admit(c, false)) {
     RunKind k;
-    k.no_tiles = true; k.wave_fout = wo.at(0, 0); k.wave_fevery = every; k.wave_fstride = wo.stride(0); k.win = &plan;
+    k.no_tiles = true; k.wave.fout = wo.at(0, 0); k.wave.fevery = every; k.wave.fstride = wo.stride(0); k.wave.win = &plan;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     return wo.finish();
   }
@@ -898,11 +898,7 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
   // call's table on every slab's device where the tiles would run -- no room: the call keeps off the tiles, nobody fails
   std::vector<float> pairs;
   if (driven) {
-    pairs.resize(2 * (size_t)nsteps);
-    for (int t = 0; t < nsteps; ++t) {
-      pairs[2 * (size_t)t] = c->p.density * accel[t] / 9.f;          // d2q9-bgk.c:230-231
-      pairs[2 * (size_t)t + 1] = c->p.density * accel[t] / 36.f;
-    }
+    pairs = accel_pairs(c, accel, nsteps);
     for (size_t i = 0; i < ns && !rc && tiles; ++i)
       if (!drive_table_room(c->slabs[i], nsteps)) tiles = false;
   }
@@ -950,7 +946,7 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
       k.no_tiles = true;
       if (pwave) {
         // (the probes' phase runs on from the start of the call: the first sample of this piece, and its row of the output)
-        k.wave_pevery = pe; k.pfirst = pe - done % pe; k.wave_pout = po.at(0, jp);
+        k.wave.pevery = pe; k.pfirst = pe - done % pe; k.wave.pout = po.at(0, jp);
         c->probes_in_wave = 0;
       }
       if (driven) c->driven_in_wave = 0;

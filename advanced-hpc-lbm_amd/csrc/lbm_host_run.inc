@@ -41,28 +41,9 @@ struct RunKind {
   bool piece_mid = false, no_tiles = false;
   int pfirst = 0;
   bool* ran = nullptr;
-  // wave_pout (lbm_run_probes / lbm_run_observed on a context wave_probes_admit said yes to; a lattice alone, the register
-  // tiles kept off): the probes' sample steps are pfirst, pfirst + wave_pevery, ... steps into this run, wave_pout is the
-  // output row of the first of them (rows of 4 x nprobes floats).  The groups of K steps take them inside lbm_wave's probe
-  // flavours; behind a left-over step that is a sample step, lbm_probe_gather.
-  float* wave_pout = nullptr;
-  int wave_pevery = 0;
-  // wave_fout (lbm_run_sampled / lbm_run_mean on a context wave_admit said yes to; a lattice alone, the register
-  // tiles kept off): the sample steps are wave_fevery, 2 wave_fevery, ... steps into this run; wave_fout is the first
-  // sample's field, [ny][nx][4] floats on the slab's device, wave_fstride the floats from one sample's field to the next;
-  // wave_fadd: the samples are added into ONE field (wave_fstride = 0), the sums of a mean.  The groups of K steps take them
-  // inside lbm_wave's field flavour; behind a left-over step that is a sample step, lbm_derive into the slot (its sums go to
-  // wave_fpart / wave_fmass, one float / double per block of the kernel, and are not used) or lbm_mean_add into the sums.
-  float* wave_fout = nullptr;
-  int wave_fevery = 0;
-  long wave_fstride = 0;
-  bool wave_fadd = false;
-  float* wave_fpart = nullptr;
-  double* wave_fmass = nullptr;
-  // win (lbm_run_window, with wave_fout on a context wave_admit said yes to): wave_fout and wave_fstride are of windows, the
-  // groups of K steps take them inside lbm_wave's window flavour (win->wave); behind a left-over step that is a sample step,
-  // lbm_derive_window into the slot (no sums, wave_fpart / wave_fmass unused).
-  const struct WinPlan* win = nullptr;
+  // what the run wants from its groups of K steps inside lbm_wave launches (lbm_wave_pick.h; a lattice alone that wave_admit said
+  // yes to, the register tiles kept off): nothing, probes (with pfirst) or fields
+  WaveWants wave;
   // drive (lbm_run_driven): drive[2 t], drive[2 t + 1] = (a1, a2) of the accelerate phase of step t (0-based) of this run, host
   // memory, in place of the context's pair.  The register tiles run their kRegDrive flavour (the slabs' device tables,
   // Slab::dtab, have room: the caller asked); off them, a lattice alone that wave_admit said yes to runs its groups of K
@@ -73,12 +54,6 @@ struct RunKind {
   // step this piece starts at: the launch is handed Slab::dtab advanced by that many pairs, and uploads nothing.  drive
   // itself is the host table advanced likewise, for every path off the tiles.
   long drive_at = 0;
-};
-
-// The window of one lbm_run_window call: as given (validated), and as lbm_wave's window flavour tests it.
-struct WinPlan {
-  lbm_window w;
-  lbm::WaveWin wave;
 };
 
 // End of a run: reduce across ranks (if there is a communicator), fetch the per-step sums and the
@@ -549,7 +524,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
       a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = s.nyl;
       a.blocked = s.blocked; a.omega = c->p.omega;
       a.accel_row = s.accel_row;
-      a.a1 = c->p.density * c->p.accel / 9.f; a.a2 = c->p.density * c->p.accel / 36.f;
+      a.a1 = accel_pair(c).a1; a.a2 = accel_pair(c).a2;
       a.ty = t.ty; a.ntx = t.ntx; a.nty = t.nty;
       a.nsteps = nsteps; a.tag0 = c->rtag;
       a.mail = s.tmail; a.mail_bytes = (unsigned)s.tmail_bytes;
@@ -717,7 +692,7 @@ bool slab_wave_pays(const lbm_ctx* c, int rows, int K) {
 int run_p2p(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (!c->p2p_connected) return fail(LBM_EINVAL, "peer-to-peer halos are not connected (lbm_p2p_connect)");
   const int nx = c->p.nx;
-  const float a1 = c->p.density * c->p.accel / 9.f, a2 = c->p.density * c->p.accel / 36.f;
+  const float a1 = accel_pair(c).a1, a2 = accel_pair(c).a2;
   const bool dr = k.drive != nullptr;                              // lbm_run_driven: one step per launch, each with its own constants
   auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };      // the accelerate constants of step t (0-based) of this run
   auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };

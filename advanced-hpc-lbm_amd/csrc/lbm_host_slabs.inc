@@ -523,7 +523,7 @@ struct Slab;
 int regtile_mail_alloc(lbm_ctx* c, Slab& s);
 size_t regtile_mail_bytes(const lbm_ctx* c);
 typedef void (*wave_fn)(const lbm::WaveArgs);
-wave_fn wave_kernel(int K, bool slab, int C, int flavour);   // the lbm_wave instantiations, below
+wave_fn wave_kernel(int K, bool slab, int C, int math, WaveFlavour f);   // the lbm_wave instantiations, below
 bool march_slabs_setup(lbm_ctx* c);   // marching kernel across slabs, below
 int wave_blocks_per_cu(int K, int C);        // occupancy of lbm_wave<K, ., ., C>, below
 bool p2p_march_pays(const lbm_ctx* c);
