@@ -32,6 +32,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lbm_mi355x.h")
 
 NSPEEDS = 9
 EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, EXCHANGE_P2P = 0, 1, 2, 3
+REFILL_KEEP, REFILL_REST = 0, 1      # lbm_set_obstacles
 
 # every symbol include/lbm_mi355x.h declares
 ABI_SYMBOLS = (
@@ -40,7 +41,7 @@ ABI_SYMBOLS = (
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
     "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows",
     "lbm_set_accel", "lbm_run_driven", "lbm_run_driven_observed",
-    "lbm_last_run_ms", "lbm_read_state",
+    "lbm_last_run_ms", "lbm_read_state", "lbm_set_obstacles", "lbm_write_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
     "lbm_timestep", "lbm_set_option", "lbm_get_info", "lbm_plan_tiles",
 )
@@ -122,6 +123,8 @@ def load_library():
     lib.lbm_run_driven_observed.argtypes = [vp, C.c_int, vp, vp, C.POINTER(Observe)]
     lib.lbm_last_run_ms.argtypes = [vp, dp, dp]
     lib.lbm_read_state.argtypes = [vp, vp]
+    lib.lbm_set_obstacles.argtypes = [vp, vp, C.c_int]
+    lib.lbm_write_state.argtypes = [vp, vp]
     lib.lbm_av_velocity.argtypes = [vp, fp]
     lib.lbm_reynolds.argtypes = [vp, fp]
     lib.lbm_total_density.argtypes = [vp, dp]
@@ -453,6 +456,39 @@ class Lattice:
         out = np.empty((self._local_rows(), self.params.nx, NSPEEDS), dtype=np.float32)
         _check(self._lib.lbm_read_state(self._ctx, out.ctypes.data))
         return out
+
+    def set_obstacles(self, obstacles, refill: int = REFILL_KEEP):
+        """Replaces the obstacle map for every later call (lbm_set_obstacles): obstacles is int[ny, nx] over the global
+        lattice (in rank mode the global array on every rank).  Afterwards the context is, bit for bit, a fresh one made
+        from (obstacles, the lattice as it stands) with the same options, acceleration and probe set; refill =
+        REFILL_REST puts the rest equilibrium into the cells that turn from blocked to fluid (the total density changes),
+        REFILL_KEEP leaves what bounce-back left there.  The body labelling is cleared: set_bodies again before
+        run_forces.  info("refilled_cells") / info("obstacle_updates") count.  Rank contexts: every rank returns from this
+        call before any rank runs."""
+        ob = _as_obstacles(obstacles, self.params)
+        _check(self._lib.lbm_set_obstacles(self._ctx, ob.ctypes.data, int(refill)))
+        self._nbodies = 0
+
+    def write_state(self, cells):
+        """Replaces the lattice (lbm_write_state), the inverse of read_state: cells is (rows, nx, 9) float32 -- a numpy
+        array (or anything np.ascontiguousarray takes), or a contiguous float32 CUDA torch tensor of that size on the
+        context's GPU, or an int device pointer to such memory -- rows = the whole lattice, in rank mode this rank's own.
+        Values are not inspected.  Options, acceleration, probes and bodies are kept."""
+        n = self._local_rows() * self.params.nx * NSPEEDS
+        if isinstance(cells, int):
+            ptr = cells
+        elif type(cells).__module__.split(".")[0] == "torch":
+            import torch
+            if (cells.dtype != torch.float32 or not cells.is_cuda or not cells.is_contiguous() or cells.numel() != n):
+                raise LbmError(f"cells must be a contiguous float32 CUDA tensor of {n} floats")
+            torch.cuda.synchronize(cells.device)      # (the library's streams do not follow torch's)
+            ptr = cells.data_ptr()
+        else:
+            a = np.ascontiguousarray(cells, dtype=np.float32)
+            if a.size != n:
+                raise LbmError(f"cells has {a.size} floats, expected {n}")
+            ptr = a.ctypes.data
+        _check(self._lib.lbm_write_state(self._ctx, ptr))
 
     def final_state(self) -> np.ndarray:
         """(rows, nx, 4) = u_x, u_y, |u|, pressure, computed on the GPU."""

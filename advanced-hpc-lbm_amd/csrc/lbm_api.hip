@@ -36,6 +36,7 @@
 #include "lbm_march.hip.h"
 #include "lbm_wave.hip.h"
 #include "lbm_regtile.hip.h"
+#include "lbm_live.hip.h"
 #include "lbm_tile_table.h"
 #include "lbm_wave_pick.h"
 
@@ -281,6 +282,8 @@ struct lbm_ctx {
   int observed_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
   int nbodies = 0;             // lbm_set_bodies (0: none)
   int nprobes = 0;             // lbm_set_probes (0: none)
+  long obstacle_updates = 0;   // successful lbm_set_obstacles calls on this context
+  long refilled_cells = 0;     // cells the last of them refilled in this process's rows (0 under LBM_REFILL_KEEP)
   // obstacle map of the local rows and one row either side (global rows keep_row0 .. keep_row0 + keep_rows - 1, taken
   // modulo ny), for the bodies' direction masks
   std::vector<uint8_t> obst_keep;
@@ -1084,6 +1087,8 @@ extern "C" int lbm_destroy(lbm_ctx* c) {
   return LBM_OK;
 }
 
+#include "lbm_host_live.inc"
+
 extern "C" int lbm_timestep(const lbm_param* params, float* cells, float* tmp_cells,
                             const int* obstacles, float* av_vel) {
   if (!cells || !tmp_cells) return fail(LBM_EINVAL, "NULL lattice");
@@ -1229,6 +1234,8 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
   if (!strcmp(key, "wave_out_cols")) { *value = wave_out_cols(c, c->time_block); return LBM_OK; }
   if (!strcmp(key, "march_rows")) { *value = c->march_rows > 0 ? c->march_rows : march_pick_rows(c); return LBM_OK; }
   if (!strcmp(key, "fluid_cells")) { *value = (double)c->tot_fluid; return LBM_OK; }
+  if (!strcmp(key, "obstacle_updates")) { *value = (double)c->obstacle_updates; return LBM_OK; }
+  if (!strcmp(key, "refilled_cells")) { *value = (double)c->refilled_cells; return LBM_OK; }
   if (!strcmp(key, "wave_launches")) { *value = (double)c->wave_launches; return LBM_OK; }
   if (!strcmp(key, "accel")) { *value = (double)c->p.accel; return LBM_OK; }
   if (!strcmp(key, "engine_next")) {   // what the next lbm_run will try first

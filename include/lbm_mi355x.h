@@ -378,7 +378,8 @@ int lbm_window_rows(const lbm_window* win, int nx, int ny, int row_begin, int ro
 
 /*
  * The acceleration as an input of the run (a ramp over the first thousand steps instead of an impulsive start, a pulsatile
- * or oscillatory channel, a loop closed on av_vels) -- the one parameter of a context that is not frozen at lbm_create.
+ * or oscillatory channel, a loop closed on av_vels) -- the one PARAMETER of a context that is not frozen at lbm_create (the
+ * obstacle map and the lattice are inputs too: lbm_set_obstacles, lbm_write_state, below).
  */
 /* Replaces the context's acceleration for every later run (lbm_run and all lbm_run_* calls).  Only stores the value: queues
    nothing, rebuilds no table, changes no engine choice (every run makes its accelerate constants from the context's
@@ -478,6 +479,56 @@ int lbm_last_run_ms(const lbm_ctx* ctx, double* gpu_ms, double* wall_ms);
  * Rank contexts: this rank's rows only, float[(row_end-row_begin)*nx*9]. */
 int lbm_read_state(lbm_ctx* ctx, float* cells_out);
 
+/*
+ * Live inputs: the obstacle map and the lattice of a context replaced in place (shape iteration, a valve, a moving body,
+ * a restart from a saved state, a perturbed spun-up flow) without destroying and creating it again.  Code objects,
+ * buffers, tiling, mailboxes, peer handles, options, acceleration and the probe set all stay.  Neither call communicates.
+ */
+#define LBM_REFILL_KEEP 0
+#define LBM_REFILL_REST 1
+/* Replaces the obstacle map for every later call.  obstacles: int[ny*nx] over the GLOBAL lattice, host memory, nonzero =
+   blocked -- whatever lbm_create accepts as a map; in rank mode the global array on every rank (as lbm_create_rank and
+   lbm_set_bodies take theirs).
+   Definition: let S be what lbm_read_state would return just before the call.  Afterwards the context behaves, bit for bit
+   and for every later call (lbm_run, every lbm_run_*, lbm_read_state, lbm_final_state, lbm_av_velocity, lbm_reynolds,
+   lbm_total_density, info "fluid_cells"), like a fresh context created with lbm_create*(params, obstacles, S', ...) on the
+   same slabs, devices and exchange, given the same options, the same acceleration (lbm_set_accel's value) and the same
+   probe set.
+   - LBM_REFILL_KEEP: S' = S.  A cell that turns from blocked to fluid keeps the populations bounce-back left in it.
+   - LBM_REFILL_REST: S' = S, except that every cell blocked under the old map and fluid under the new one holds the rest
+     equilibrium of lbm_create's NULL-cells start: density * 4.f / 9.f, density / 9.f (x 4), density / 36.f (x 4), in float.
+     The total density therefore CHANGES with such a call (by the refilled cells' rest mass less what they held).
+   A cell that turns from fluid to blocked keeps its populations under either mode.
+   What survives: the probe set, the options, the acceleration, the engine choice, the tiling, the mailbox tag sequence of
+   the register tiles.  What does not: the body labelling is cleared, as by lbm_set_bodies(ctx, NULL, 0) -- the library
+   keeps no label array, and labels are validated against the map; label the new map again before lbm_run_forces.
+   One kernel per slab on its compute stream reads the old bytes and the new map, writes the new bytes, refills and counts;
+   the call returns when it is complete.
+   ORDERING: nothing is communicated.  In rank contexts, and wherever peer-to-peer neighbours read each other's obstacle
+   bytes in place, EVERY rank must have returned from this call before ANY rank starts a run (a barrier of the caller's
+   choice, as for lbm_destroy); every rank passes the same map.
+   Info "obstacle_updates": the successful calls on this context.  "refilled_cells": the cells the last call refilled in
+   this process's rows (0 under LBM_REFILL_KEEP).
+   Refusals, with the map unchanged, the lattice untouched and nothing queued -- LBM_EINVAL: NULL ctx or map, a refill value
+   other than the two; LBM_EHIP: a context whose peer-to-peer halo wait failed earlier; LBM_ENOMEM: a staging buffer that
+   does not fit.
+   Not offered: a per-step geometry schedule inside the kernels; maps in device memory; the command-line tool. */
+int lbm_set_obstacles(lbm_ctx* ctx, const int* obstacles, int refill);
+/* The inverse of lbm_read_state, same layout and conventions: single-process contexts take the whole lattice,
+   float[ny*nx*9]; rank contexts take this rank's rows, float[(row_end-row_begin)*nx*9] -- lbm_read_state's buffer goes
+   straight back in.  cells: host memory, or device memory of the device that holds every slab of the context (as the
+   outputs of the lbm_run_* calls); device memory is converted straight from the caller's pointer, nothing is staged through
+   the host (work queued on the caller's own streams that writes `cells` must be complete).
+   Definition: afterwards the context is, bit for bit and for every later call, a fresh context created with the same map
+   and `cells`, given the same options, acceleration, probe set and bodies -- all kept.  Values are not inspected (NaNs,
+   negative zeros and the contents of blocked cells go in as they are, as in lbm_create).  Holds after any number of steps.
+   ORDERING, as for lbm_set_obstacles: nothing is communicated; where neighbouring ranks read each other's rows in place,
+   every rank's last run has returned before any rank writes, and every rank has returned from this call before any runs.
+   Refusals, all with the lattice untouched -- LBM_EINVAL: NULL arguments, a device pointer on another device than the
+   slabs'; LBM_EHIP: a context whose peer-to-peer halo wait failed earlier; LBM_ENOMEM: a staging buffer that does not fit.
+   Not offered: the command-line tool. */
+int lbm_write_state(lbm_ctx* ctx, const float* cells);
+
 /* Replaces: av_velocity() and calc_reynolds(), d2q9-bgk.c:2665-2714, 2893-2898,
  * evaluated on the resident lattice (global value in every mode). */
 int lbm_av_velocity(lbm_ctx* ctx, float* out);
@@ -538,7 +589,7 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * ran its groups of K steps inside lbm_wave launches), "driven_observed_in_kernel", "driven_observed_in_wave",
  * "driven_observed_pieces" (lbm_run_driven_observed), "resident_fallback", "time_block_active", "march_kernel", "wave_rows",
  * "wave_cols_active", "wave_out_cols", "regtile", "regtile_blocks_per_cu", "exchange", "compute_units", "fluid_cells",
- * "pitch", "hbm_bytes". */
+ * "obstacle_updates", "refilled_cells" (lbm_set_obstacles), "pitch", "hbm_bytes". */
 int lbm_set_option(lbm_ctx* ctx, const char* key, long value);  /* e.g. "kernel_variant" */
 int lbm_get_info(const lbm_ctx* ctx, const char* key, double* value);
 
