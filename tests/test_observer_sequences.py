@@ -808,6 +808,16 @@ class Shadow:
                 (np.array(W), np.array(A)) if states else None)
 
 
+def hold_anchor(st_a, ref, av, av_o):
+    """The anchor's bars: the shadow's lattice st_a and av_vels against the strict float oracle's ref and av_o.  Returns the
+    worst deviations as fractions of the bars."""
+    ref = ref.reshape(st_a.shape)
+    bar = 2e-5 * np.abs(ref) + 2e-6 * np.abs(ref).max()
+    assert np.all(np.abs(st_a - ref) <= bar)
+    assert np.allclose(av, av_o, rtol=1e-4, atol=0)
+    return float(np.max(np.abs(st_a - ref) / bar)), float(np.max(np.abs(av - av_o) / (1e-4 * np.abs(av_o))))
+
+
 def _schedule(sched, p, accel, n):
     if sched is None or sched == "const":
         return np.full(n, accel, dtype=np.float32)
@@ -1012,8 +1022,7 @@ def test_observer_sequence(gpu, O, oracle, monkeypatch, name):
             av_o.append(driven_oracle(oracle, op, ref, ob, np.array([a], dtype=np.float32))[0])
         st_a = sh.at_anchor
         assert st_a is not None and len(av_o) == anchor
-        assert np.all(np.abs(st_a - ref.reshape(st_a.shape)) <= 2e-5 * np.abs(ref.reshape(st_a.shape)) + 2e-6 * np.abs(ref).max())
-        assert np.allclose(np.concatenate(sh.av)[:anchor], np.array(av_o), rtol=1e-4, atol=0)
+        hold_anchor(st_a, ref, np.concatenate(sh.av)[:anchor], np.array(av_o))
         if name in REFUSING:
             assert refusals > 0                   # the guard refused cells inside the sequence
     finally:

@@ -29,6 +29,7 @@ U = 2.0 ** -24
 SMOOTH = ("control", "under_relaxed", "omega_one")
 REFUSING = ("light_fluid", "refusal")
 ONE_THIRD = np.float32(1.0 / 3.0)
+ENGINE_AV_RTOL = 2e-6               # av_vels of a multi-step engine against the one-step kernel: summation order
 
 
 def _orc_param(O, point, nx, ny, steps=100):
@@ -137,6 +138,31 @@ SHADOW_CASES = [(64, 40, 31, "guard", "guard"), (33, 20, 32, "perturbed", "rest"
 NSHADOW = 20
 
 
+def one_step_oracle(oracle, o64, prm, ob, x):
+    """One step from the float lattice x by the oracle in double and in float, the accelerate phase in the reference's
+    float arithmetic for both: (t64, rho, e32, av32, av64); e32 = the float oracle's worst error in u rho."""
+    acc = x.copy()
+    oracle.accelerate(prm, acc, ob)
+    a64 = acc.astype(np.float64)
+    t64 = np.empty_like(a64)
+    av64 = o64.sweep(prm, a64, t64, ob)
+    t32 = np.empty_like(acc)
+    av32 = oracle.sweep(prm, acc.copy(), t32, ob)
+    rho = t64.sum(axis=-1, keepdims=True)
+    return t64, rho, float(np.max(np.abs(t32 - t64) / (U * rho))), av32, av64
+
+
+def hold_one_step(st, av, shadow, tag):
+    """The one-step bar (module docstring) on a GPU step (st, av) against shadow = one_step_oracle(...) of the state before
+    it: (worst |gpu - f64| in u rho, |av - av64|)."""
+    t64, rho, e32, av32, av64 = shadow
+    e = float(np.max(np.abs(st - t64) / (U * rho)))
+    assert e <= 8.0 and e <= 2.0 * e32 + 1.0, (tag, e, e32)
+    eav = abs(av - av64)
+    assert eav <= 2.0 * abs(av32 - av64) + 4 * U, (tag, av, av32, av64)
+    return e, eav
+
+
 def _one_gpu_step(L, p, ob, x, V=None, variant=None):
     with L.Lattice(p, ob, x) as lat:
         lat.set_option("time_block", 1)
@@ -174,29 +200,20 @@ def test_one_step_kernel_against_double_oracle(gpu, O, oracle, point, nx, ny, se
         nref += r
         if r and first_refusal is None:
             first_refusal = t
-        acc = x.copy()
-        oracle.accelerate(prm, acc, ob)                   # the reference's float accelerate, for both flavours
-        a64 = acc.astype(np.float64)
-        t64 = np.empty_like(a64)
-        av64 = o64.sweep(prm, a64, t64, ob)
-        t32 = np.empty_like(acc)
-        av32 = oracle.sweep(prm, acc.copy(), t32, ob)
-        rho = t64.sum(axis=-1, keepdims=True)
-        e32 = float(np.max(np.abs(t32 - t64) / (U * rho)))
-        worst["f32"] = max(worst["f32"], e32)
+        shadow = one_step_oracle(oracle, o64, prm, ob, x)  # the reference's float accelerate, for both flavours
+        worst["f32"] = max(worst["f32"], shadow[2])
         runs = [(None, None)] + (combos if t in (1, 2, first_refusal, NSHADOW) else [])
         for V, variant in runs:
             av, st = _one_gpu_step(L, p, ob, x, V, variant)
-            e = float(np.max(np.abs(st - t64) / (U * rho)))
+            e, eav = hold_one_step(st, av, shadow, (point, t, V, variant))
             worst["gpu"] = max(worst["gpu"], e)
-            assert e <= 8.0 and e <= 2.0 * e32 + 1.0, (point, t, V, variant, e, e32)
-            eav = abs(av - av64)
             worst["av"] = max(worst["av"], eav / U)
-            assert eav <= 2.0 * abs(av32 - av64) + 4 * U, (point, t, V, variant, av, av32, av64)
             if V is None and variant is None:
                 nxt = st
         if t == 1:
             # the reference's call shape: the accelerate side effect on the caller's lattice, bit for bit
+            acc = x.copy()
+            oracle.accelerate(prm, acc, ob)
             c, tmp = x.copy(), np.empty_like(x)
             L.timestep_new2(p, c, tmp, ob)
             assert np.array_equal(_bits(c), _bits(acc)) and np.array_equal(_bits(tmp), _bits(nxt))
@@ -306,7 +323,7 @@ def test_engine_equals_one_step_kernel_on_the_grid(gpu, O, oracle, monkeypatch, 
             assert b.info(key) == v, (engine, key, b.info(key))
         st_b = b.read_state()
     assert np.array_equal(_bits(st_a), _bits(st_b)), engine
-    assert np.allclose(av_a, av_b, rtol=2e-6, atol=0), engine
+    assert np.allclose(av_a, av_b, rtol=ENGINE_AV_RTOL, atol=0), engine
 
 
 @pytest.mark.gpu
