@@ -38,7 +38,7 @@ REFILL_KEEP, REFILL_REST = 0, 1      # lbm_set_obstacles
 ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
-    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_set_bodies", "lbm_run_forces",
+    "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_run_stats", "lbm_set_bodies", "lbm_run_forces",
     "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows",
     "lbm_set_accel", "lbm_run_driven", "lbm_run_driven_observed",
     "lbm_last_run_ms", "lbm_read_state", "lbm_set_obstacles", "lbm_write_state",
@@ -111,6 +111,7 @@ def load_library():
     lib.lbm_run.argtypes = [vp, C.c_int, vp]
     lib.lbm_run_sampled.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_run_mean.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    lib.lbm_run_stats.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.lbm_set_bodies.argtypes = [vp, vp, C.c_int]
     lib.lbm_set_probes.argtypes = [vp, vp, C.c_int]
     lib.lbm_run_probes.argtypes = [vp, C.c_int, vp, C.c_int, vp]
@@ -288,6 +289,20 @@ class Lattice:
         mean, ptr = self._output(out, shape, "out")
         _check(self._lib.lbm_run_mean(self._ctx, nsteps, av.ctypes.data, every, ptr))
         return av, mean
+
+    def run_stats(self, nsteps: int, every: int = 1, out=None):
+        """lbm_run with the means and second moments over the sample steps every, 2 every, ...: returns (av_vels[nsteps],
+        stats) where stats is (rows, nx, 8) float32 -- floats 0..3 run_mean's output, bit for bit (the means of u_x, u_y,
+        |u|, pressure), floats 4..7 the means of u_x^2, u_y^2, u_x u_y and (p - p0)^2 with p0 = float32(density) / 3 as a
+        blocked cell reads it -- a numpy array, or `out`, a contiguous float32 torch tensor of that shape on the context's
+        GPU, filled there.  Variances and covariances are the caller's to form, in double, as E[xy] - E[x] E[y].  Where
+        lbm_wave runs the sums ride in its launches (info("stats_in_wave") == 1: av_vels is run()'s bits); elsewhere the
+        steps run in pieces of `every` (on the register tiles where they run) with an add kernel behind each."""
+        shape = (self._local_rows(), self.params.nx, 8)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        stats, ptr = self._output(out, shape, "out")
+        _check(self._lib.lbm_run_stats(self._ctx, nsteps, av.ctypes.data, every, ptr))
+        return av, stats
 
     def set_probes(self, xy):
         """The cells run_probes records: xy is anything np.asarray turns into int32[n, 2] of (column, row) in the global

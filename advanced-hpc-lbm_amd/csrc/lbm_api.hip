@@ -267,6 +267,7 @@ struct lbm_ctx {
   int mean_in_kernel = 0;      // 1: the last lbm_run_mean took its sums inside the register tiles
   int samples_in_wave = 0;     // 1: the last lbm_run_sampled took its snapshots inside lbm_wave launches
   int mean_in_wave = 0;        // 1: the last lbm_run_mean took its sums inside lbm_wave launches
+  int stats_in_wave = 0;       // 1: the last lbm_run_stats took its sums inside lbm_wave launches
   long wave_launches = 0;      // lbm_wave kernels this context has launched so far, every flavour (launch_wave counts them)
   int probes_in_kernel = 0;    // 1: the last lbm_run_probes took its values inside the register tiles
   int probes_in_wave = 0;      // 1: the last lbm_run_probes took its values inside lbm_wave launches
@@ -770,7 +771,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     HIPC(hipSetDevice(sl.dev));
     int rc;
     if (psample(s) && (rc = launch_probe_gather(c, sl, w.pout + 4 * (size_t)w.prow(k.pfirst, s) * (size_t)c->nprobes))) return rc;
-    if (fsample(s) && w.fadd && (rc = launch_mean_add(c, sl, w.fout))) return rc;
+    if (fsample(s) && w.fadd && (rc = w.fstats ? launch_stats_add(c, sl, w.fout) : launch_mean_add(c, sl, w.fout))) return rc;
     if (fsample(s) && w.win && (rc = launch_derive_window(c, sl, w.win->w, 0, w.win->w.ny, w.fslot(s)))) return rc;
     if (fsample(s) && !w.fadd && !w.win) {
       const long ncell = (long)sl.nyl * nx;
@@ -894,7 +895,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (fwave) c->forces_in_wave = 1;
     if (dwave) c->driven_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
-    if (fw && wave) (w.win ? c->window_in_wave : w.fadd ? c->mean_in_wave : c->samples_in_wave) = 1;
+    if (fw && wave) (w.win ? c->window_in_wave : w.fstats ? c->stats_in_wave : w.fadd ? c->mean_in_wave : c->samples_in_wave) = 1;
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -1214,6 +1215,7 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
       {"samples_in_kernel", &lbm_ctx::samples_in_kernel}, {"samples_in_wave", &lbm_ctx::samples_in_wave},
       {"forces_in_kernel", &lbm_ctx::forces_in_kernel}, {"forces_in_wave", &lbm_ctx::forces_in_wave},
       {"mean_in_kernel", &lbm_ctx::mean_in_kernel}, {"mean_in_wave", &lbm_ctx::mean_in_wave},
+      {"stats_in_wave", &lbm_ctx::stats_in_wave},
       {"probes_in_kernel", &lbm_ctx::probes_in_kernel}, {"probes_in_wave", &lbm_ctx::probes_in_wave},
       {"window_in_kernel", &lbm_ctx::window_in_kernel}, {"window_in_wave", &lbm_ctx::window_in_wave},
       {"driven_in_kernel", &lbm_ctx::driven_in_kernel}, {"driven_in_wave", &lbm_ctx::driven_in_wave},

@@ -503,25 +503,26 @@ int launch_band_group(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev
 // The instantiations: a lattice alone (K = 4, 6, 8 with one column per lane, K = 8 with two) in every flavour, and a slab with
 // neighbours (K = 8, one or two columns) in the plain one; math = IEEE or fast rcp / sqrt (bit 0) x nontemporal stores (bit 1).
 // What a flavour (lbm_wave_pick.h) switches on in the kernel, by lbm_wave's template parameters:
-struct WaveTraits { bool FORCE, PROBE, FIELD, WINDOW, DRIVEN; };
-constexpr WaveTraits kWaveTraits[8] = {
-    /* plain           */ {false, false, false, false, false},
-    /* force           */ {true, false, false, false, false},    // lbm_run_forces
-    /* probe           */ {false, true, false, false, false},    // lbm_run_probes
-    /* force_probe     */ {true, true, false, false, false},     // lbm_run_observed's forces and probes
-    /* field           */ {false, false, true, false, false},    // lbm_run_sampled, lbm_run_mean
-    /* window          */ {false, false, false, true, false},    // lbm_run_window
-    /* driven          */ {false, false, false, false, true},    // lbm_run_driven
-    /* driven_observed */ {true, true, false, false, true},      // lbm_run_driven_observed
+struct WaveTraits { bool FORCE, PROBE, FIELD, WINDOW, DRIVEN, STATS; };
+constexpr WaveTraits kWaveTraits[9] = {
+    /* plain           */ {false, false, false, false, false, false},
+    /* force           */ {true, false, false, false, false, false},    // lbm_run_forces
+    /* probe           */ {false, true, false, false, false, false},    // lbm_run_probes
+    /* force_probe     */ {true, true, false, false, false, false},     // lbm_run_observed's forces and probes
+    /* field           */ {false, false, true, false, false, false},    // lbm_run_sampled, lbm_run_mean
+    /* window          */ {false, false, false, true, false, false},    // lbm_run_window
+    /* driven          */ {false, false, false, false, true, false},    // lbm_run_driven
+    /* driven_observed */ {true, true, false, false, true, false},      // lbm_run_driven_observed
+    /* stats           */ {false, false, false, false, false, true},    // lbm_run_stats
 };
 template <int K, bool SLAB, int C, WaveFlavour F>
 wave_fn wave_kernel_m(int math) {
   constexpr WaveTraits t = kWaveTraits[(int)F];
   switch (math & 3) {
-    case 0: return lbm::lbm_wave<K, 0, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
-    case 1: return lbm::lbm_wave<K, 1, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
-    case 2: return lbm::lbm_wave<K, 2, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
-    default: return lbm::lbm_wave<K, 3, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN>;
+    case 0: return lbm::lbm_wave<K, 0, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN, t.STATS>;
+    case 1: return lbm::lbm_wave<K, 1, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN, t.STATS>;
+    case 2: return lbm::lbm_wave<K, 2, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN, t.STATS>;
+    default: return lbm::lbm_wave<K, 3, SLAB, C, t.FORCE, t.PROBE, t.FIELD, t.WINDOW, t.DRIVEN, t.STATS>;
   }
 }
 template <WaveFlavour F>
@@ -543,6 +544,7 @@ wave_fn wave_kernel(int K, bool slab, int C, int math, WaveFlavour f) {
     case WaveFlavour::window: return wave_kernel_kc<WaveFlavour::window>(K, slab, C, math);
     case WaveFlavour::force_probe: return wave_kernel_kc<WaveFlavour::force_probe>(K, slab, C, math);
     case WaveFlavour::probe: return wave_kernel_kc<WaveFlavour::probe>(K, slab, C, math);
+    case WaveFlavour::stats: return wave_kernel_kc<WaveFlavour::stats>(K, slab, C, math);
   }
   return nullptr;
 }
@@ -664,7 +666,8 @@ int launch_wave(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, int 
   // (development: LBM_WAVE_PAD_LDS = bytes of unused dynamic LDS per block, to hold fewer blocks on a CU than the registers
   // allow -- how the rate depends on the waves per SIMD: profiles/r03_wave_occupancy.log)
   static const int pad_lds = getenv("LBM_WAVE_PAD_LDS") ? atoi(getenv("LBM_WAVE_PAD_LDS")) : 0;
-  const WavePick p = wave_pick(g.driven, nb_bodies > 0, s.fcells_n > 0, w.pout != nullptr, g.pmask != 0u, w.fout != nullptr, g.fmask != 0u, w.win != nullptr);
+  const WavePick p = wave_pick(g.driven, nb_bodies > 0, s.fcells_n > 0, w.pout != nullptr, g.pmask != 0u, w.fout != nullptr, g.fmask != 0u, w.win != nullptr,
+                                   w.fstats);
   if (p.refused) return fail(LBM_EINVAL, g.driven ? "lbm_wave: the driven flavour runs beside no fields" : "lbm_wave: the field flavour runs beside neither forces nor probes");
   a.blocked = p.map == WaveMap::fpmap ? s.fpmap : p.map == WaveMap::pmap ? s.pmap : p.map == WaveMap::fmap ? s.fmap : s.blocked;
   a.fidx = nullptr; a.fcells = nullptr; a.contrib = nullptr; a.fcells_n = 0;

@@ -88,9 +88,20 @@ int launch_mean_add(const lbm_ctx* c, Slab& s, float* acc) {
   return LBM_OK;
 }
 
-// the slab's sums of m samples divided into out (which may be the sums themselves)
-int launch_mean_div(const lbm_ctx* c, Slab& s, const float* acc, int m, float* out) {
-  const long ncell = (long)s.nyl * c->p.nx;
+// ... and beside them their products, eight floats per cell (lbm_run_stats)
+int launch_stats_add(const lbm_ctx* c, Slab& s, float* acc) {
+  const int nx = c->p.nx;
+  const long ncell = (long)s.nyl * nx;
+  HIPC(hipSetDevice(s.dev));
+  hipLaunchKernelGGL(lbm::lbm_stats_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
+                     nx, ncell, s.blocked, c->p.density, acc);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// the slab's sums of m samples divided into out (which may be the sums themselves); width: floats per cell, 4 or 8
+int launch_mean_div(const lbm_ctx* c, Slab& s, const float* acc, int m, float* out, int width = 4) {
+  const long ncell = (long)s.nyl * c->p.nx * (width / 4);      // (float4s)
   HIPC(hipSetDevice(s.dev));
   hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, acc, ncell, (float)m, out);
   HIPC(hipGetLastError());
@@ -182,18 +193,20 @@ struct ProbeOut {
   }
 };
 
-// Where one call's means go, [rows][nx][4] floats: one float4 per cell and slab -- the sums of every path but the register
-// tiles', and the staging of host output on every path.  Device output is written in place.
+// Where one call's means go, [rows][nx][width] floats: one record per cell and slab, of 4 floats (lbm_run_mean: the fields)
+// or 8 (lbm_run_stats: the fields and their products) -- the sums of every path but the register tiles', and the staging of
+// host output on every path.  Device output is written in place.
 struct MeanOut {
   lbm_ctx* c;
+  int width;
   float* out = nullptr;
   bool on_dev = false;
   std::vector<DeviceTemp> acc;
 
-  explicit MeanOut(lbm_ctx* ctx) : c(ctx) {}
+  explicit MeanOut(lbm_ctx* ctx, int w = 4) : c(ctx), width(w) {}
   int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
-  size_t bytes(const Slab& s) const { return sizeof(float) * 4 * (size_t)s.nyl * (size_t)c->p.nx; }
-  float* host_rows(const Slab& s) const { return out + 4L * (s.row0 - (c->rank_mode ? c->slabs[0].row0 : 0)) * c->p.nx; }
+  size_t bytes(const Slab& s) const { return sizeof(float) * (size_t)width * (size_t)s.nyl * (size_t)c->p.nx; }
+  float* host_rows(const Slab& s) const { return out + (long)width * (s.row0 - (c->rank_mode ? c->slabs[0].row0 : 0)) * c->p.nx; }
   // the slabs' buffers (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
   int prepare() {
     acc.resize(c->slabs.size());
@@ -223,7 +236,7 @@ struct MeanOut {
   int add() {
     int rc;
     for (size_t i = 0; i < c->slabs.size(); ++i)
-      if ((rc = launch_mean_add(c, c->slabs[i], sums(i)))) return rc;
+      if ((rc = width == 8 ? launch_stats_add(c, c->slabs[i], sums(i)) : launch_mean_add(c, c->slabs[i], sums(i)))) return rc;
     return LBM_OK;
   }
   int to_host() {
@@ -240,7 +253,7 @@ struct MeanOut {
     int rc;
     for (size_t i = 0; i < c->slabs.size(); ++i) {
       Slab& s = c->slabs[i];
-      if ((rc = launch_mean_div(c, s, sums(i), m, at(i)))) return rc;
+      if ((rc = launch_mean_div(c, s, sums(i), m, at(i), width))) return rc;
       HIPC(hipStreamSynchronize(s.sc));
     }
     return to_host();
@@ -483,6 +496,39 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
   }
   // ---- the step loop split at the sample steps: each piece a complete run, then the fields of the stored lattice added to
   // the slab's sums (no snapshot, no host round trip per sample); the same adds in the same order as in the register tiles.
+  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int) { return mo.add(); }))) return rc;
+  return mo.finish(m);
+}
+
+extern "C" int lbm_run_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, float* stats_out) {
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
+  const int m = nsteps / every;
+  if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
+  if (!stats_out) return fail(LBM_EINVAL, "stats_out is NULL");
+  c->stats_in_wave = 0;
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
+  MeanOut mo(c, 8);
+  int rc;
+  if ((rc = mo.locate(stats_out, "stats_out"))) return rc;
+  rc = mo.prepare();
+  bool tiles = false;                              // (no sums inside the register tiles: the ranks agree on room alone)
+  if ((rc = ranks_agree(c, rc, &tiles, "the sums"))) return rc;
+  if ((rc = mo.clear())) return rc;
+  // ---- where lbm_run would run lbm_wave (a lattice alone; admission as lbm_run_mean's): ONE run, the groups of K steps that
+  // hold a sample step in lbm_wave's stats flavour, lbm_stats_add behind the left-over steps that are sample steps.  The
+  // same adds in the same order as below.  (Where lbm_run_mean would keep its sums inside the register tiles, the tiles run
+  // the pieces below: av_vels stays lbm_run's there.)
+  if (!regtile_is_next(c) && nsteps >= c->time_block && wave_admit(c, false)) {
+    RunKind k;
+    k.no_tiles = true; k.wave.fout = mo.sums(0); k.wave.fevery = every; k.wave.fstride = 0; k.wave.fadd = true; k.wave.fstats = true;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    return mo.finish(m);
+  }
+  // ---- the step loop split at the sample steps: each piece a complete plain run (on a register-tile context, on the
+  // tiles), then the fields of the stored lattice and their products added to the slab's sums
   if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int) { return mo.add(); }))) return rc;
   return mo.finish(m);
 }

@@ -1216,7 +1216,41 @@ __global__ __launch_bounds__(kBlock) void lbm_mean_add(const float* lat, long pl
   s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
   *reinterpret_cast<f4a*>(acc4 + 4 * c) = s;
 }
-// ... and after the last piece: out4[cell] = acc4[cell] / m (IEEE division; out4 may be acc4)
+// The eight terms a sample adds to a cell's sums in lbm_run_stats: the four fields, and u_x^2, u_y^2, u_x u_y, (p - p0)^2 with
+// p0 = density * (1.f / 3.f), the pressure a blocked cell reads.  One rounding per operation: callers keep contraction off.
+// Shared by lbm_stats_add and lbm_wave's stats flavour, which must agree bit for bit.
+__device__ __forceinline__ f4a stats_products(const f4a v, float density) {
+#pragma clang fp contract(off)
+  const float d = v.w - density * (1.f / 3.f);
+  f4a q; q.x = v.x * v.x; q.y = v.y * v.y; q.z = v.x * v.y; q.w = d * d;
+  return q;
+}
+// lbm_run_stats on every engine but lbm_wave's stats flavour: lbm_mean_add with records of eight floats -- the fields of the
+// stored lattice added to acc8[cell][0..3], their products (stats_products) to acc8[cell][4..7]; two 16-byte loads and two
+// 16-byte stores per cell, the cell and float indices 64-bit.
+__global__ __launch_bounds__(kBlock) void lbm_stats_add(const float* lat, long plane, int pitch, int nx, long ncell,
+                                                        const uint8_t* blocked, float density, float* acc8) {
+#pragma clang fp contract(off)
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncell) return;
+  const long y = c / nx; const int x = (int)(c - y * nx);
+  const long o = y * pitch + x;
+  float f[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
+  float rho;
+  const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
+  const f4a q = stats_products(v, density);
+  f4a* at = reinterpret_cast<f4a*>(acc8 + 8 * c);
+  f4a s = at[0];
+  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+  at[0] = s;
+  f4a t = at[1];
+  t.x = t.x + q.x; t.y = t.y + q.y; t.z = t.z + q.z; t.w = t.w + q.w;
+  at[1] = t;
+}
+// ... and after the last piece: out4[cell] = acc4[cell] / m (IEEE division; out4 may be acc4).  lbm_run_stats: its sums as
+// 2 ncell float4s.
 __global__ __launch_bounds__(kBlock) void lbm_mean_div(const float* acc4, long ncell, float m, float* out4) {
   const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncell) return;

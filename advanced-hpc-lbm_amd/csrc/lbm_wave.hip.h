@@ -86,6 +86,7 @@ struct WaveArgs {
   float* fout;                 // the output base of the pass's first sample
   long fstride;                // floats between consecutive samples' outputs (snapshots: one field; sums: 0)
   int fadd;                    // 0: stored (snapshots); 1: added to what is there (the sums of lbm_run_mean)
+                               // (the stats flavour, STATS: fmask as above, fout the run's ONE array of sums, [ny][nx][8]; fstride, fadd unread)
   // ---- the window flavour (WINDOW; a lattice alone, lbm_run_window): fmask, fout and fstride as above, but a sample's
   // output is the window, [win.ny][win.nx][4], and only the window's cells are derived and stored (appended: every earlier
   // member keeps its offset)
@@ -149,6 +150,12 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // lane of ONE wave owns a cell at every level of a pass; it reaches levels l and l + 1 of a row in consecutive iterations,
 // in program order; so the adds of one pass into a cell's sums are same-thread accesses to one address (plain loads and
 // stores, not the nontemporal helpers), and the adds of different passes are ordered by the stream.
+// STATS (lbm_run_stats where lbm_wave runs; a lattice alone, a flavour of its own): FIELD's levels, mask, ownership and call
+// site, but a cell's record is eight floats at 8 * (row * nx + column) of the run's one array of sums, a lane's two cells 64
+// contiguous bytes: the four fields are added to the first four as FIELD's fadd = 1 adds them, their products
+// (stats_products: u_x^2, u_y^2, u_x u_y, (p - p0)^2) to the last four -- lbm_stats_add's arithmetic.  The first half's
+// load, adds and store come before the second half's: four sums are live at a time, not eight.  The record index is 64-bit
+// (2^28 cells pass 2^31 floats).  The existing FIELD kernels are not touched: no third fadd value.
 // DRIVEN (lbm_run_driven where lbm_wave runs; a lattice alone, a flavour of its own): level l takes its accelerate constants from
 // the pass's K pairs in the kernel's arguments (scalar registers, the level is a compile-time constant of the unrolled loop)
 // where every other flavour takes a1, a2; both images of the accelerate row that a chunk's fill rows may pass within a level
@@ -159,7 +166,7 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // counted cell: contrib and fidx are not read), the force-and-probe map, or the plain obstacle bytes, whose values 0 and 1
 // are a map that marks nothing.
 template <int K, int MODE, bool SLAB = false, int C = 1, bool FORCE = false, bool PROBE = false, bool FIELD = false, bool WINDOW = false,
-          bool DRIVEN = false>
+          bool DRIVEN = false, bool STATS = false>
 __global__ __launch_bounds__(kWaveBlock) __attribute__((amdgpu_waves_per_eu(wave_min_occupancy(K, C))))
 void lbm_wave(const WaveArgs a) {
   constexpr bool FAST = (MODE & kFastMath) != 0, NTS = (MODE & kNtStore) != 0, NTL = (MODE & kNtLoad) != 0;
@@ -172,6 +179,7 @@ void lbm_wave(const WaveArgs a) {
   static_assert(!(WINDOW && (SLAB || FORCE || PROBE || FIELD)), "the window flavour is for a lattice alone, and a flavour of its own");
   static_assert(!(DRIVEN && (SLAB || FORCE != PROBE || FIELD || WINDOW)), "the driven flavour is for a lattice alone: alone, or with forces and probes");
   static_assert(!DRIVEN || K <= 8, "K pairs of constants in the arguments");
+  static_assert(!(STATS && (SLAB || FORCE || PROBE || FIELD || WINDOW || DRIVEN)), "the stats flavour is for a lattice alone, and a flavour of its own");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -333,6 +341,28 @@ void lbm_wave(const WaveArgs a) {
         }
       }
     };
+    // STATS, at a sample level behind collide_cell(s): every delivered cell of the level's row into its record of the sums
+    [[maybe_unused]] auto store_stats = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
+      if (own_row && ((a.fmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
+        if (out_ok) {                            // (as store_fields: the lane's cells lie inside the chunk's rows and columns)
+#pragma clang fp contract(off)
+          float* o = a.fout + 8 * ((long)(S0 + j - l) * a.nx + (X0 - K + C * lane));
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            float rho;
+            const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
+            f4a* at = reinterpret_cast<f4a*>(o + 8 * c);
+            f4a s = at[0];                       // (one rounding per add, the order of the steps; plain same-thread accesses)
+            s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+            at[0] = s;
+            const f4a q = stats_products(v, a.density);
+            f4a t = at[1];
+            t.x = t.x + q.x; t.y = t.y + q.y; t.z = t.z + q.z; t.w = t.w + q.w;
+            at[1] = t;
+          }
+        }
+      }
+    };
     // WINDOW, at a sample level behind collide_cell(s): the window's cells of the level's row into the sample's window
     [[maybe_unused]] auto store_window = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
       if (own_row && ((a.fmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
@@ -417,6 +447,7 @@ void lbm_wave(const WaveArgs a) {
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
             if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
+            if constexpr (STATS) store_stats(l, j, p, own_row, out_ok);
             if (acc) accelerate_cell(p[0], blk, la1, la2);
             sum[l - 1] += (out_ok && own_row) ? sp : 0.f;
           } else {
@@ -428,6 +459,7 @@ void lbm_wave(const WaveArgs a) {
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
             if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
+            if constexpr (STATS) store_stats(l, j, p, own_row, out_ok);
 #pragma unroll
             for (int c = 0; c < C; ++c)
               if (acc) accelerate_cell(p[c], blk[c], la1, la2);

@@ -200,6 +200,44 @@ int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* 
 int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mean_out);
 
 /*
+ * lbm_run_mean with the second moments beside the means: what Reynolds stresses, r.m.s. velocity and r.m.s. pressure are
+ * formed from.  stats_out: float[rows][nx][8], rows, rank-local convention and memory (host, or the device that holds every
+ * slab) as lbm_run_mean's.  With X_j = (u_x, u_y, |u|, p) = snapshot j of lbm_run_sampled(ctx, nsteps, av_vels, every, ...)
+ * from the same state (sample steps every, 2 every, ..., m every; m = nsteps / every) and p0 = density * (1.f / 3.f), the
+ * float a blocked cell reads as pressure, the definition is, per cell, bit for bit, in float with one rounding per
+ * operation, no fma and no reassociation:
+ *     d   = X_j.w - p0
+ *     Q_j = ( X_j.x * X_j.x,  X_j.y * X_j.y,  X_j.x * X_j.y,  d * d )
+ *     S_0 = T_0 = +0.0f;   S_j = S_(j-1) + X_j;   T_j = T_(j-1) + Q_j      (step order)
+ *     stats_out[cell][0..3] = S_m / (float)m;   stats_out[cell][4..7] = T_m / (float)m
+ * So floats 0..3 of every cell are lbm_run_mean's output with the same arguments, bit for bit, and a blocked cell reads
+ * (0, 0, 0, p0, 0, 0, 0, 0).
+ * Why the pressure is shifted: p sits at about density / 3 with fluctuations orders of magnitude smaller; a float sum of
+ * p^2 loses them in its rounding, a sum of (p - p0)^2 does not.  Variances and covariances are the caller's to form, in
+ * double, as E[xy] - E[x] E[y]: var(u_x) = [4] - [0]^2, var(u_y) = [5] - [1]^2, cov(u_x, u_y) = [6] - [0] [1],
+ * var(p) = [7] - ([3] - p0)^2.
+ * av_vels, the lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels) wherever the
+ * register tiles or lbm_wave ran the steps; on the split path av_vels is equal to rounding of the per-step sum, as for
+ * lbm_run_mean.
+ * LBM_EINVAL when ctx is NULL, nsteps < 0, every <= 0, m = 0, stats_out is NULL or device memory of another device than the
+ * slabs'; LBM_ENOMEM when the sums (32 bytes per cell) do not fit -- the ranks of a rank context agree on that first;
+ * LBM_EHIP after a failed peer-to-peer wait; each with nothing queued and the lattice untouched.
+ * Which kernels take the sums:
+ * - Where lbm_wave runs (admission as lbm_run_mean's: a lattice alone with time_block 4, 6 or 8 and the wave kernel, nsteps
+ *   >= time_block), the sums ride in its launches (info "stats_in_wave" = 1, reset at the start of each call): a stats
+ *   flavour of lbm_wave adds every cell's eight terms into its 32-byte record at the sample levels of a pass, one kernel
+ *   per pass of K steps; a pass without a sample step runs the plain kernel; the steps left over behind the last full pass
+ *   go as lbm_run's do, with the add kernel behind those that are sample steps.
+ * - Everywhere else -- the register tiles, lbm_march, slabs with neighbours, rank contexts, runs shorter than time_block --
+ *   the steps run in pieces of `every` with the add kernel behind each ("stats_in_wave" = 0); pieces on a register-tile
+ *   context stay on the tiles.  The same adds in the same order, the same bits.
+ * Not offered: sums inside the register tiles (their mean flavour keeps three sums per cell in LDS; seven would want about
+ * 112 KB of a CU's 160 KB at 4096 cells per tile, beside the mailboxes: unverified); stats inside lbm_run_observed, whose
+ * struct is frozen; stats under a schedule; stats over a window; higher moments; the command-line tool.
+ */
+int lbm_run_stats(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* stats_out);
+
+/*
  * Drag and lift on labelled bodies, step by step.
  *
  * Directions are the reference's: 1 E, 2 N, 3 W, 4 S, 5 NE, 6 NW, 7 SW, 8 SE. c_i is the lattice vector and opp(i)
@@ -579,6 +617,7 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "mean_in_kernel" (1: the last lbm_run_mean took its sums inside the register tiles),
  * "samples_in_wave" (1: the last lbm_run_sampled took its snapshots inside lbm_wave launches),
  * "mean_in_wave" (1: the last lbm_run_mean took its sums inside lbm_wave launches),
+ * "stats_in_wave" (1: the last lbm_run_stats took its sums inside lbm_wave launches),
  * "wave_launches" (the lbm_wave kernels this context has launched on a lattice alone, every flavour: one per pass of K steps),
  * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles),
  * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches),
