@@ -293,7 +293,7 @@ class Lattice:
     def run_stats(self, nsteps: int, every: int = 1, out=None):
         """lbm_run with the means and second moments over the sample steps every, 2 every, ...: returns (av_vels[nsteps],
         stats) where stats is (rows, nx, 8) float32 -- floats 0..3 run_mean's output, bit for bit (the means of u_x, u_y,
-        |u|, pressure), floats 4..7 the means of u_x^2, u_y^2, u_x u_y and (p - p0)^2 with p0 = float32(density) / 3 as a
+        |u|, pressure), floats 4..7 the means of u_x^2, u_y^2, u_x u_y and (p - p0)^2 with p0 = float32(density) * float32(1/3) as a
         blocked cell reads it -- a numpy array, or `out`, a contiguous float32 torch tensor of that shape on the context's
         GPU, filled there.  Variances and covariances are the caller's to form, in double, as E[xy] - E[x] E[y].  Where
         lbm_wave runs the sums ride in its launches (info("stats_in_wave") == 1: av_vels is run()'s bits); elsewhere the

@@ -514,22 +514,47 @@ extern "C" int lbm_run_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, 
   int rc;
   if ((rc = mo.locate(stats_out, "stats_out"))) return rc;
   rc = mo.prepare();
-  bool tiles = false;                              // (no sums inside the register tiles: the ranks agree on room alone)
+  // (no sums inside the register tiles; their pieces below run in the piece flavour, with the table of -1s for both of its
+  // observers -- no room for that table: plain pieces, nobody fails.  The ranks agree on the room for the sums and on the flavour.)
+  bool tiles = regtile_is_next(c);
+  for (size_t i = 0; i < c->slabs.size() && tiles; ++i)
+    if (empty_table(c->slabs[i], c->tplan.ty, c->tplan.ntx)) tiles = false;
   if ((rc = ranks_agree(c, rc, &tiles, "the sums"))) return rc;
   if ((rc = mo.clear())) return rc;
   // ---- where lbm_run would run lbm_wave (a lattice alone; admission as lbm_run_mean's): ONE run, the groups of K steps that
   // hold a sample step in lbm_wave's stats flavour, lbm_stats_add behind the left-over steps that are sample steps.  The
   // same adds in the same order as below.  (Where lbm_run_mean would keep its sums inside the register tiles, the tiles run
-  // the pieces below: av_vels stays lbm_run's there.)
+  // the pieces below.)
   if (!regtile_is_next(c) && nsteps >= c->time_block && wave_admit(c, false)) {
     RunKind k;
     k.no_tiles = true; k.wave.fout = mo.sums(0); k.wave.fevery = every; k.wave.fstride = 0; k.wave.fadd = true; k.wave.fstats = true;
     if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
     return mo.finish(m);
   }
-  // ---- the step loop split at the sample steps: each piece a complete plain run (on a register-tile context, on the
-  // tiles), then the fields of the stored lattice and their products added to the slab's sums
-  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int) { return mo.add(); }))) return rc;
+  // ---- the step loop split at the sample steps: each piece a complete run, then the fields of the stored lattice and their
+  // products added to the slab's sums.  On a register-tile context the pieces run on the tiles, as lbm_run_observed's do
+  // and for its reason: the piece flavour with neither observer wanted (RegFlavour::piece), which alone folds the last
+  // step's speed sums of a piece that is not the call's last as a whole run folds them there (piece_mid) -- plain launches
+  // would move the last bit of av_vels at every cut.  A flavour that cannot be resident: plain pieces from there on.
+  double gpu_ms = 0.0, wall_ms = 0.0;
+  int done = 0;
+  for (int j = 0; j <= m; ++j) {
+    const int n = (j < m) ? every : nsteps - done;
+    if (n == 0) break;
+    float* av = av_vels ? av_vels + done : nullptr;
+    bool ran = false;
+    if (tiles && regtile_is_next(c)) {
+      RunKind k;
+      k.flavour = RegFlavour::piece; k.piece_mid = done + n < nsteps; k.ran = &ran;
+      if ((rc = run_steps(c, n, av, k))) return rc;
+      tiles = ran;                                    // (nothing stepped: this piece and the rest as plain runs)
+    }
+    if (!ran && (rc = run_steps(c, n, av))) return rc;
+    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
+    done += n;
+    if (j < m && (rc = mo.add())) return rc;
+  }
+  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
   return mo.finish(m);
 }
 

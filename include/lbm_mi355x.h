@@ -142,7 +142,8 @@ int lbm_run(lbm_ctx* ctx, int nsteps, float* av_vels);
  * lbm_run with snapshots of the derived fields taken during the run, after steps every, 2 every, ..., m every
  * (m = nsteps / every; every = 0: none, exactly lbm_run; every < 0: LBM_EINVAL).  fields_out: float[m][rows][nx][4],
  * snapshot j = what lbm_final_state would return after (j+1) every steps (same rows and rank-local convention), bit for
- * bit; NULL only when m = 0.  av_vels, the lattice and everything after are bit-identical to lbm_run(ctx, nsteps, av_vels).
+ * bit (a blocked cell: 0, 0, 0, density * (1.f / 3.f), in float); NULL only when m = 0.  av_vels, the lattice and
+ * everything after are bit-identical to lbm_run(ctx, nsteps, av_vels).
  * fields_out may be host memory, or device memory of the device that holds every slab of the context (then nothing is
  * copied to the host).  The register-tile engines write the snapshots from inside their kernels (info
  * "samples_in_kernel" = 1); the other engines run the steps in pieces with a derive after each.  LBM_ENOMEM /
@@ -171,7 +172,8 @@ int lbm_run_sampled(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* 
  * lbm_run_sampled(ctx, nsteps, av_vels, every, ...), the definition is, per cell and field, bit for bit:
  *     S_0 = +0.0f;  S_j = S_(j-1) + X_j  in float, in step order (one rounding per add, no fma, no reassociation);
  *     mean_out = S_m / (float)m  (a correctly rounded float division).
- * Blocked cells take part like any other (their X_j is the constant 0, 0, 0, density / 3).  mean_out: float[rows][nx][4]
+ * Blocked cells take part like any other (their X_j is the constant 0, 0, 0, density * (1.f / 3.f), in float).
+ * mean_out: float[rows][nx][4]
  * with the rows and the rank-local convention of lbm_final_state; host memory, or device memory of the device that holds
  * every slab of the context (then nothing is copied to the host).  av_vels, the lattice and everything after are
  * bit-identical to lbm_run(ctx, nsteps, av_vels).  The register-tile engines keep the sums inside their kernels (info
@@ -211,8 +213,9 @@ int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mea
  *     S_0 = T_0 = +0.0f;   S_j = S_(j-1) + X_j;   T_j = T_(j-1) + Q_j      (step order)
  *     stats_out[cell][0..3] = S_m / (float)m;   stats_out[cell][4..7] = T_m / (float)m
  * So floats 0..3 of every cell are lbm_run_mean's output with the same arguments, bit for bit, and a blocked cell reads
- * (0, 0, 0, p0, 0, 0, 0, 0).
- * Why the pressure is shifted: p sits at about density / 3 with fluctuations orders of magnitude smaller; a float sum of
+ * (0, 0, 0, p0', 0, 0, 0, 0) with p0' = (p0 + p0 + ... + p0) / (float)m by the sums above: p0 itself where that float sum
+ * does not round (m = 1, 2, 4 always), else within an ulp or two of it.
+ * Why the pressure is shifted: p sits at about p0 with fluctuations orders of magnitude smaller; a float sum of
  * p^2 loses them in its rounding, a sum of (p - p0)^2 does not.  Variances and covariances are the caller's to form, in
  * double, as E[xy] - E[x] E[y]: var(u_x) = [4] - [0]^2, var(u_y) = [5] - [1]^2, cov(u_x, u_y) = [6] - [0] [1],
  * var(p) = [7] - ([3] - p0)^2.
@@ -230,7 +233,9 @@ int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mea
  *   go as lbm_run's do, with the add kernel behind those that are sample steps.
  * - Everywhere else -- the register tiles, lbm_march, slabs with neighbours, rank contexts, runs shorter than time_block --
  *   the steps run in pieces of `every` with the add kernel behind each ("stats_in_wave" = 0); pieces on a register-tile
- *   context stay on the tiles.  The same adds in the same order, the same bits.
+ *   context stay on the tiles, in the flavour lbm_run_observed's pieces run in, which folds a piece's last step sum as a
+ *   whole run folds it there: av_vels does not depend on where the call is cut.  The same adds in the same order, the same
+ *   bits.
  * Not offered: sums inside the register tiles (their mean flavour keeps three sums per cell in LDS; seven would want about
  * 112 KB of a CU's 160 KB at 4096 cells per tile, beside the mailboxes: unverified); stats inside lbm_run_observed, whose
  * struct is frozen; stats under a schedule; stats over a window; higher moments; the command-line tool.
@@ -292,8 +297,8 @@ int lbm_set_probes(lbm_ctx* ctx, const int* xy, int nprobes);
    every, 2 every, ..., m every (m = nsteps / every).
    Definition, bit for bit: probes_out[j][p][:] equals fields_out[j][jj_p][ii_p][:] of
    lbm_run_sampled(ctx, nsteps, av_vels, every, fields_out) from the same state; a blocked cell reads the constant
-   0, 0, 0, density / 3.  Probes keep the order in which they were given.  The lattice and everything after the
-   call are bit-identical to lbm_run(ctx, nsteps, av_vels).  probes_out: host memory, or device memory of the device that holds
+   0, 0, 0, density * (1.f / 3.f) (in float).  Probes keep the order in which they were given.  The lattice and
+   everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels).  probes_out: host memory, or device memory of the device that holds
    every slab of the context (then nothing is copied to the host).
    Rank contexts: xy is global on every rank; each rank fills the entries of the probes that lie in its own rows
    (lbm_slab_rows) and writes +0.0f to the others; no communication is added.  Combining the ranks' arrays is the caller's
@@ -377,9 +382,9 @@ typedef struct { int x0, y0, nx, ny, sx, sy; } lbm_window;
    written, window_out may be NULL).
    Definition, bit for bit: window_out[j][r][c][:] equals fields_out[j][win->y0 + r win->sy][win->x0 + c win->sx][:] of
    lbm_run_sampled(ctx, nsteps, av_vels, every, fields_out) from the same state with the same options; a blocked cell
-   reads 0, 0, 0, density / 3.  av_vels, the lattice and everything after the call are what they are for lbm_run_sampled
-   on the same context: lbm_run's bits wherever the register tiles or lbm_wave took the window, within float rounding of
-   the per-step sum on the split path.  window_out: host memory, or device memory of the device that holds every slab of
+   reads 0, 0, 0, density * (1.f / 3.f) (in float).  av_vels, the lattice and everything after the call are what they are
+   for lbm_run_sampled on the same context: lbm_run's bits wherever the register tiles or lbm_wave took the window, within
+   float rounding of the per-step sum on the split path.  window_out: host memory, or device memory of the device that holds every slab of
    the context (then nothing is copied to the host).  Single-process contexts with several slabs write the whole window.
    Rank contexts: the window is global on every rank and every rank's array has the full window shape; a rank fills the
    window rows that lie in its own lattice rows (lbm_window_rows with lbm_slab_rows tells which) and writes +0.0f to the
@@ -578,7 +583,8 @@ int lbm_total_density(lbm_ctx* ctx, double* out);
 
 /* Replaces: the per-cell arithmetic of write_values(), d2q9-bgk.c:2935-2976.
  * out[4*(ii + jj*nx) + {0,1,2,3}] = u_x, u_y, |u|, pressure, computed on the GPU
- * (blocked cells: 0, 0, 0, density/3).  Same slab-local convention as
+ * (blocked cells: 0, 0, 0, density * (1.f / 3.f), the product in float, as the reference's c_sq = 1.f / 3.f gives
+ * it; at some densities, 0.3 and 0.02 among them, that is one ulp from density / 3.f).  Same slab-local convention as
  * lbm_read_state in rank mode. */
 int lbm_final_state(lbm_ctx* ctx, float* out);
 

@@ -2,7 +2,8 @@
 calls of ONE long-lived context, in the manner of tests/test_observer_sequences.py (a table of programs, a model, a coverage
 check without a GPU, one GPU runner).
 
-New table entries: set_map(name, refill), write(name), refused_live(what).
+New table entries: set_map(name, refill), write(name), refused_live(what).  lbm_run_stats is the tenth kind of running call
+(TEN): on every path family it is the first call behind a map change under either refill, and behind a write.
 
 The shadow never takes a live input.  It stays the one-step kernel (engine 1, time_block 1, a lattice alone; a slab context
 where slabs add up forces off the tiles, as in the older file), and at every live input it is DESTROYED AND CREATED AGAIN by
@@ -52,10 +53,12 @@ from test_driven_run import AV_RTOL, driven_oracle
 from test_live_inputs import KEEP, LBM_EINVAL, REST, refilled, rest_values, s_prime
 from test_observer_sequences import (B3, B5, B9, FP, F, InChunks, M, ObserverModel, P, S, Shadow, _call, _chains, _check_engine,
                                      _is, _probe_sets, _refuse, _same, _schedule, driven, driven_observed, hold_anchor, mean, observed,
-                                     probe_set, probes, refused, window)
+                                     probe_set, probes, refused, stats, window)
+from test_stats_run import p0_of, stats_of
 from test_window_run import cut
 
 NINE = ("run", "sampled", "forces", "probes", "mean", "observed", "window", "driven", "driven_observed")
+TEN = NINE + ("stats",)
 INT_MIN = -2 ** 31
 PATTERNS = ((0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0))      # (A, B, C) in the six stamped cells
 WAVE_ROWS = 24
@@ -82,30 +85,34 @@ def _kind_call(kind, path, K, i):
     return {"run": run(n, path), "sampled": sampled(n, ev, path), "forces": forces(n, path), "probes": probes(n, 2, path),
             "mean": mean(n, ev, path), "observed": observed(n, (F, P, M), 2, ev, 0, path), "window": window(n, ev, "live", path),
             "driven": driven(n, SCHEDS[i % 3], path),
-            "driven_observed": driven_observed(n, SCHEDS[(i + 1) % 3], FP, 2, 0, 0, path)}[kind]
+            "driven_observed": driven_observed(n, SCHEDS[(i + 1) % 3], FP, 2, 0, 0, path), "stats": stats(n, ev, path)}[kind]
 
 
 def _relabel():
     return [refused("forces", 3), bodies("U", 3)]
 
 
-CYCLE = (("B", REST), ("C", KEEP), ("A", REST), ("B", REST), ("C", REST), ("A", KEEP), ("B", REST), ("C", REST), ("A", REST))
+CYCLE = (("B", REST), ("C", KEEP), ("A", REST), ("B", REST), ("C", REST), ("A", KEEP), ("B", REST), ("C", REST), ("A", REST), ("B", REST),
+         ("C", KEEP))
 
 
-def each_kind_behind_a_map(path, K, kinds=NINE):
+def each_kind_behind_a_map(path, K, kinds=TEN):
     """From map A: every kind in turn as the first running call behind a set_map (B, C, A, B, ... : never the map in
-    place); a kind that takes forces follows refused("forces") and a relabel."""
+    place); a kind that takes forces follows refused("forces") and a relabel; stats, the last of the ten, behind a
+    LBM_REFILL_REST and once more behind a LBM_REFILL_KEEP."""
     out = []
     for i, kind in enumerate(kinds):
         out.append(set_map(*CYCLE[i]))
         if kind in ("forces", "observed", "driven_observed"):
             out += _relabel()
         out.append(_kind_call(kind, path, K, i))
+    if kinds is TEN:
+        out += [set_map(*CYCLE[10]), _kind_call("stats", path, K, 10)]
     return out
 
 
 def each_kind_behind_a_write(path, K):
-    return [c for i, kind in enumerate(NINE) for c in (write("W" if i % 2 == 0 else "V"), _kind_call(kind, path, K, i))]
+    return [c for i, kind in enumerate(TEN) for c in (write("W" if i % 2 == 0 else "V"), _kind_call(kind, path, K, i))]
 
 
 def same_tables_across_a_map(path, K, first, second):
@@ -210,7 +217,7 @@ PROGRAMS = {
     ]),
     "never_tiles_tb1_tb2": (_l4, None, [opt("time_block", 1)] + _START + [run(5, "tb1")] + each_kind_behind_a_map("tb1", 1) + [
         opt("time_block", 2), run(4, "tb2")] + each_kind_behind_a_map("tb2", 2, ("probes", "forces", "mean", "driven_observed")) + [
-        write("W"), window(5, 2, "live", "tb2"), refused_live("refill 2"), run(3, "tb2")]),
+        write("W"), window(5, 2, "live", "tb2"), refused_live("refill 2"), run(3, "tb2"), write("V"), stats(5, 2, "tb2")]),
     "wave6_130x37_every_kind_behind_a_map": (_l4, None, [opt("time_block", 6), opt("wave_rows", WAVE_ROWS)] + _START + [run(13, "wave")]
                                              + each_kind_behind_a_map("wave", 6)),
     "wave6_130x37_writes_and_tables": (_l4, None, [opt("time_block", 6), opt("wave_rows", WAVE_ROWS)] + _START + [run(14, "wave"), set_map("B", REST), bodies("U", 3)]
@@ -223,7 +230,8 @@ PROGRAMS = {
     ]),
     "slabs_p2p_tiles_every_kind_behind_a_map": (_l6, ("slabs", 4, "p2p"), _START + [run(5, "slab-tiles")] + each_kind_behind_a_map("slab-tiles", 3)
                                                 + same_tables_across_a_map("slab-tiles", 3, ("B", REST), ("C", REST)) + [
-        bodies("U", 3), write("W"), forces(4, "slab-tiles"), refused_live("refill 2"), set_map("A", KEEP), set_map("B", REST), run(4, "slab-tiles")]),
+        bodies("U", 3), write("W"), forces(4, "slab-tiles"), refused_live("refill 2"), set_map("A", KEEP), set_map("B", REST), run(4, "slab-tiles"),
+        write("V"), stats(7, 3, "slab-tiles")]),
     "slabs_copy_streaming_walk": (_l7, ("slabs", 2, "copy"), [opt("time_block", 2)] + _START + [
         run(5, "tb2"), set_map("B", REST), mean(5, 2, "tb2"), set_map("C", REST), bodies("U", 3), forces(4, "tb2"),
         set_map("A", REST), opt("time_block", 4), probes(9, 4, "march"), set_map("B", KEEP), sampled(9, 4, "march"),
@@ -325,6 +333,8 @@ def found(L, programs):
                 fam, lives = FAMILY[e["path"]], [b for b in e["behind"] if b["op"] != "refused_live"]
                 if lives:
                     out.add(f"{fam}: {e['op']} first behind a {lives[-1]['op']}")
+                    if e["op"] == "stats" and lives[-1]["op"] == "set_map":
+                        out.add(f"{fam}: stats first behind a set_map {'REST' if lives[-1]['refill'] == REST else 'KEEP'}")
                     out.add(f"{fam}: a live input behind an {'odd' if e['steps0'] % 2 else 'even'} step count")
                     before = lives[0]["before"]
                     if before and before["path"] in ("wave", "march") and before["pieces"][-1] % before["tb"]:
@@ -368,8 +378,10 @@ def found(L, programs):
 
 
 DECLARED = (
-    [f"{fam}: {kind} first behind a set_map" for fam in ("tiles", "slab-tiles", "wave", "split") for kind in NINE]
-    + [f"{fam}: {kind} first behind a write" for fam in ("tiles", "wave") for kind in NINE]
+    [f"{fam}: {kind} first behind a set_map" for fam in ("tiles", "slab-tiles", "wave", "split") for kind in TEN]
+    + [f"{fam}: {kind} first behind a write" for fam in ("tiles", "wave") for kind in TEN]
+    + [f"{fam}: stats first behind a set_map {r}" for fam in ("tiles", "slab-tiles", "wave", "split") for r in ("KEEP", "REST")]
+    + [f"{fam}: stats first behind a write" for fam in ("slab-tiles", "split")]
     + [f"lone: {a} -> {b} across a map call, onto a map it never ran with" for a, b in (("tiles", "wave"), ("wave", "march"), ("march", "tiles"), ("tiles", "tb2"))]
     + [f"slabs copy: {a} -> {b} across a map call, onto a map it never ran with" for a, b in (("tb2", "march"), ("march", "slab-tiles"))]
     + [f"{fam}: the same {what} either side of a set_map, cells turning both ways" for fam in ("tiles", "slab-tiles", "wave") for what in ("window", "probe set")]
@@ -449,20 +461,24 @@ def test_the_maps_are_what_they_say(L):
             assert arr.shape == (ny, nx, 9) and arr.dtype == np.float32 and np.all(arr > 0)
 
 
-@pytest.mark.parametrize("drop", [("tiles_128_every_kind_behind_a_map", 21), ("tiles_128_writes_and_pairs", 9), ("tiles_128_writes_and_pairs", 26),
-                                  ("lone_256_retile_and_engine_walk", 9), ("never_tiles_tb1_tb2", 22), ("wave6_130x37_writes_and_tables", 26),
-                                  ("slabs_p2p_tiles_every_kind_behind_a_map", 28), ("slabs_copy_streaming_walk", 9), ("rank_ring_of_one_rccl", None)])
+@pytest.mark.parametrize("drop", [("tiles_128_every_kind_behind_a_map", 21), ("tiles_128_writes_and_pairs", 9), ("tiles_128_writes_and_pairs", 28),
+                                  ("lone_256_retile_and_engine_walk", 9), ("never_tiles_tb1_tb2", 22), ("wave6_130x37_writes_and_tables", 28),
+                                  ("slabs_p2p_tiles_every_kind_behind_a_map", 32), ("slabs_copy_streaming_walk", 9), ("rank_ring_of_one_rccl", None),
+                                  # stats: the map call in front of it (REST, KEEP), the write in front of it, the call itself
+                                  ("tiles_128_every_kind_behind_a_map", 27), ("wave6_130x37_every_kind_behind_a_map", 31),
+                                  ("tiles_128_writes_and_pairs", 23), ("slabs_p2p_tiles_every_kind_behind_a_map", 28),
+                                  ("never_tiles_tb1_tb2", 30), ("never_tiles_tb1_tb2", -1)])
 def test_a_trimmed_table_fails_the_coverage_check(L, drop):
     """Without one live input (the map call in front of a kind, a write, one of a pair, the map call between two engines or
-    between two runs of one window) or one program (a context) the table no longer covers the declared list."""
+    between two runs of one window), one stats call or one program (a context) the table no longer covers the declared list."""
     name, index = drop
     programs = dict(PROGRAMS)
     if index is None:
         del programs[name]
     else:
         setup, ctx, calls = programs[name]
-        assert calls[index][0] in LIVE, calls[index]
-        programs[name] = (setup, ctx, calls[:index] + calls[index + 1:])
+        assert calls[index][0] in LIVE or calls[index][0] == "stats", calls[index]
+        programs[name] = (setup, ctx, calls[:index] + calls[index + 1:] if index != -1 else calls[:-1])
     assert missing(L, programs)
 
 
@@ -547,7 +563,7 @@ def test_live_sequence(gpu, O, oracle, monkeypatch, name):
                 else:
                     n, kinds, tiles = e["n"], e["kinds"], e["fam"] == "tiles"
                     acc = _schedule(e["sched"], p, e["accel"], n)
-                    want_fields = any(k in kinds for k in (P, M, S, "window"))
+                    want_fields = any(k in kinds for k in (P, M, S, "window", "stats"))
                     if kind == "run":
                         av_sh, F_sh, X, numpy_forces = sh.run(n), None, None, None
                     else:
@@ -562,6 +578,8 @@ def test_live_sequence(gpu, O, oracle, monkeypatch, name):
                         exp[S] = X[e["fe"] - 1::e["fe"]]
                     if e["win"]:
                         exp["window"] = cut(X[e["fe"] - 1::e["fe"]], case["windows"][e["win"]])
+                    if "stats" in kinds:
+                        exp["stats"] = stats_of(X[e["ste"] - 1::e["ste"]], p0_of(p.density))
                     assert sorted(out) == sorted(kinds), (where, sorted(out))
                     for k, v in exp.items():
                         _same(out[k], v, where + (k,))

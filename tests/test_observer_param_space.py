@@ -250,14 +250,20 @@ def test_the_table_holds_every_path_at_every_compulsory_point():
 _TRAJECTORY = {}
 
 
-def _trajectory(O, oracle, nx, ny, point, kind, nsteps):
+def _trajectory(O, oracle, nx, ny, point, kind, nsteps, start=None):
     """The float oracle's run of the case: per step t = 1..n (min fluid rho / rho0, max |f| / rho0, the fluid cells of
-    row ny-2 that step's accelerate refused)."""
+    row ny-2 that step's accelerate refused).  start: (obstacles, cells0, (density, accel, omega)) of a point that
+    PARAM_GRID does not hold (tests/test_stats_param_space.py)."""
     key = (nx, ny, point, kind)
     if key not in _TRAJECTORY or len(_TRAJECTORY[key]) < nsteps:
-        ob, cells = param_state(point, nx, ny, _seed(nx, ny), kind)
-        prm = _orc_param(O, point, nx, ny)
-        rho0 = float(np.float32(PARAM_GRID[point][0]))
+        if start is None:
+            ob, cells = param_state(point, nx, ny, _seed(nx, ny), kind)
+            prm = _orc_param(O, point, nx, ny)
+            rho0 = float(np.float32(PARAM_GRID[point][0]))
+        else:
+            ob, cells, triple = start
+            prm = O.OrcParam(nx, ny, 100, 10, *(float(np.float32(v)) for v in triple))
+            rho0 = float(np.float32(triple[0]))
         a, b, out = cells.copy(), np.empty_like(cells), []
         for _ in range(max(nsteps, 21)):
             ref = refused(prm.density, prm.accel, ob, a)
@@ -361,38 +367,43 @@ def _reference(L, O, path, point):
     if key not in _REF:
         nmax = max(_case(q, pt)[3] for q, pt in CASES
                    if pt == point and PATHS[q][:2] == (nx, ny) and dict(PATHS[q][3]).get("kernel_variant") == variant)
-        p = _lparam(L, point, nx, ny)
-        prm = _orc_param(O, point, nx, ny)
-        o64 = O.Oracle("strict")
-        opts = [("engine", 1), ("time_block", 1)] + ([("kernel_variant", variant)] if variant is not None else [])
-        S, X, F64, A, av, worst = [], [], [], [], [], 0.0
-        with L.Lattice(p, ob, cells) as lat:
-            for k, v in opts:
-                lat.set_option(k, v)
-            for t in range(1, nmax + 1):
-                av.append(lat.run(1))
-                st, x = lat.read_state(), lat.final_state()
-                assert lat.info("engine_last") == 1 and lat.info("time_block_active") == 1
-                fo = o64.final_state(prm, st.astype(np.float64), ob).reshape(ny, nx, 4)
-                err, bar = np.abs(x - fo), 2e-6 * np.abs(fo) + 8 * U
-                worst = max(worst, float(np.max(err / bar)))
-                assert np.all(err <= bar), (key, t, float(np.max(err / bar)))
-                f, a = forces_from_state(st, ob, body, NBODIES)
-                S.append(st), X.append(x), F64.append(f), A.append(a)
-        with L.Lattice(p, ob, cells) as lat:
-            for k, v in opts:
-                lat.set_option(k, v)
-            lat.set_bodies(body, NBODIES)
-            av1, F1 = lat.run_forces(nmax)
-            assert lat.info("engine_last") == 1 and lat.info("forces_in_kernel") == 0 and lat.info("forces_in_wave") == 0
-        assert np.array_equal(_bits(av1), _bits(np.concatenate(av)))
-        ref = dict(S=np.stack(S), X=np.stack(X), F64=np.array(F64), A=np.array(A), av=np.concatenate(av), F1=F1)
-        for a in ref.values():
-            a.setflags(write=False)
-        WORST["fields"] = max(WORST["fields"], worst)
-        print(f"reference {nx}x{ny} {point} {kind}: {nmax} steps, worst |X_t - f64| {worst:.3f} of its bar")
-        _REF[key] = ref
+        _REF[key] = _reference_run(L, O, key, ob, cells, body, _lparam(L, point, nx, ny), _orc_param(O, point, nx, ny), nmax)
     return _REF[key]
+
+
+def _reference_run(L, O, key, ob, cells, body, p, prm, nmax):
+    """_reference's run: key = (nx, ny, point, state, maths) names it; p and prm the parameters of the library and the oracle
+    (tests/test_stats_param_space.py runs it at a point that PARAM_GRID does not hold)."""
+    nx, ny, point, kind, variant = key
+    o64 = O.Oracle("strict")
+    opts = [("engine", 1), ("time_block", 1)] + ([("kernel_variant", variant)] if variant is not None else [])
+    S, X, F64, A, av, worst = [], [], [], [], [], 0.0
+    with L.Lattice(p, ob, cells) as lat:
+        for k, v in opts:
+            lat.set_option(k, v)
+        for t in range(1, nmax + 1):
+            av.append(lat.run(1))
+            st, x = lat.read_state(), lat.final_state()
+            assert lat.info("engine_last") == 1 and lat.info("time_block_active") == 1
+            fo = o64.final_state(prm, st.astype(np.float64), ob).reshape(ny, nx, 4)
+            err, bar = np.abs(x - fo), 2e-6 * np.abs(fo) + 8 * U
+            worst = max(worst, float(np.max(err / bar)))
+            assert np.all(err <= bar), (key, t, float(np.max(err / bar)))
+            f, a = forces_from_state(st, ob, body, NBODIES)
+            S.append(st), X.append(x), F64.append(f), A.append(a)
+    with L.Lattice(p, ob, cells) as lat:
+        for k, v in opts:
+            lat.set_option(k, v)
+        lat.set_bodies(body, NBODIES)
+        av1, F1 = lat.run_forces(nmax)
+        assert lat.info("engine_last") == 1 and lat.info("forces_in_kernel") == 0 and lat.info("forces_in_wave") == 0
+    assert np.array_equal(_bits(av1), _bits(np.concatenate(av)))
+    ref = dict(S=np.stack(S), X=np.stack(X), F64=np.array(F64), A=np.array(A), av=np.concatenate(av), F1=F1)
+    for a in ref.values():
+        a.setflags(write=False)
+    WORST["fields"] = max(WORST["fields"], worst)
+    print(f"reference {nx}x{ny} {point} {kind}: {nmax} steps, worst |X_t - f64| {worst:.3f} of its bar")
+    return ref
 
 
 def _expected_info(path, call, K, n, pe, me, se):

@@ -1,5 +1,5 @@
 """One context through windows, schedules and every observer call (lbm_run_probes, lbm_run_mean, lbm_run_observed,
-lbm_run_window, lbm_set_accel, lbm_run_driven, lbm_run_driven_observed beside lbm_run, lbm_run_sampled, lbm_run_forces,
+lbm_run_window, lbm_set_accel, lbm_run_driven, lbm_run_driven_observed, lbm_run_stats beside lbm_run, lbm_run_sampled, lbm_run_forces,
 lbm_set_bodies, lbm_set_probes and lbm_set_option on ONE long-lived context).
 
 tests/test_call_sequences.py drives a context through plain, sampled and forces runs; this file does the same for the calls
@@ -15,7 +15,8 @@ forces across slabs off the register tiles, the same kind of context, because sl
 run(1) when no bodies are set; final_state after each step whose fields an output needs, read_state where forces are
 compared in numpy; behind a driven call it puts the context's own acceleration back.  Everything expected is numpy on those
 per-step fields by the header's definitions: snapshots fields[every - 1::every], probes the snapshots at [:, jj, ii, :],
-windows the snapshots at [:, y0::sy, x0::sx, :] cut to ny x nx, means test_driven_observed.mean_from_fields.
+windows the snapshots at [:, y0::sy, x0::sx, :] cut to ny x nx, means test_driven_observed.mean_from_fields, the eight floats
+of lbm_run_stats test_stats_run.stats_of of the snapshots with p0 = float32(density) x float32(1/3).
 
 After every call: the outputs (snapshots, probes, windows and means bit for bit on every path; forces on the register tiles
 held to the numpy forces of the shadow's lattices by test_body_forces._close, elsewhere the shadow's run_forces(1) bits), the
@@ -30,7 +31,8 @@ The mailbox tag.  lbm_host_run.inc advances the tag once per register-tile LAUNC
 steps of that launch.  A call the tiles run in several pieces (lbm_run_observed with two or more observers, every
 lbm_run_driven_observed: cut at the sample steps of means and snapshots) therefore advances it by n_i + 1 per piece, and the
 wrap (a lattice alone: cleared in front of the piece that would reach TAG_WRAP) and the restart (slabs: behind the piece
-that passes SLAB_TAG_MARK) are tested per piece.  ObserverModel.apply restates exactly that.
+that passes SLAB_TAG_MARK) are tested per piece.  lbm_run_stats off lbm_wave is cut at every sample step, on the tiles too:
+a launch per piece there.  ObserverModel.apply restates exactly that.
 
 The table is checked without a GPU against a declared coverage list (path x kind, contexts, transitions, refused calls), so
 that trimming it fails on CPU."""
@@ -41,17 +43,18 @@ import numpy as np
 import pytest
 
 from test_body_forces import _bits, _close, forces_from_state
-from test_call_sequences import (ANCHOR_STEPS, SLAB_TAG_MARK, TAG_WRAP, TILE_PATHS, Model, _check_derived, _grow, _kept, _labels,
+from test_call_sequences import (ANCHOR_STEPS, SLAB_TAG_MARK, TAG_WRAP, TILE_PATHS, W_EQ, Model, _check_derived, _grow, _kept, _labels,
                                  _open, _p1, _p2, _p3, _p4, _p5, _p6, _p7, _p8, _p9, bodies, clear, forces, opt, run, sampled)
 from test_driven_observed import mean_from_fields, pieces_of
 from test_driven_run import AV_RTOL, driven_oracle, schedules
 from test_probe_run import awkward_set
+from test_stats_run import p0_of, stats_of
 from test_window_run import cut
 
 from make_golden import PARAM_GRID                      # noqa: E402  (test_call_sequences put tests/golden on the path)
 from make_golden import refused as guard_refuses        # noqa: E402
 
-KINDS = ("probes", "mean", "observed", "window", "driven", "driven_observed")
+KINDS = ("probes", "mean", "observed", "window", "driven", "driven_observed", "stats")
 RUNNING = ("run", "sampled", "forces") + KINDS
 PATHS = TILE_PATHS + ("tb1", "tb2", "march", "wave")
 X_ACCEL = 0.0123                                         # what set_accel sets in the programs
@@ -86,6 +89,10 @@ def driven_observed(n, schedule, kinds, pe, me, fe, path):
     return ("driven_observed", n, schedule, kinds, pe, me, fe, path)
 
 
+def stats(n, every, path):
+    return ("stats", n, every, path)
+
+
 def set_accel(x):
     return ("set_accel", x)
 
@@ -101,7 +108,7 @@ def clear_probes():
 def refused(what, *args):
     """A call that must return LBM_EINVAL: "window" (n, every, name of a window outside the lattice), "schedule" (n, index
     of the non-finite entry, its value), "probes" (n, every), "forces" (n), "mean" (n, every > n), "observed mean"
-    (n, mean_every > n)."""
+    (n, mean_every > n), "stats" (n, every > n)."""
     return ("refused", what) + args
 
 
@@ -176,6 +183,21 @@ def _c10(L):      # 256 x 64 at the refusal point, from rest: the accelerate row
     return _case(L, _p9, (2, 1), {"row": (0, 62, 256, 1)})
 
 
+THIRDS = (0.3, 0.01, 1.85)                               # tests/test_stats_param_space.py: the density at which the two forms of p0 differ
+
+
+def _p10(L):      # 256 x 64 at "thirds", every population within +-10 % of the equilibrium at rest
+    nx, ny = 256, 64
+    rng = np.random.default_rng(101)
+    ob = (rng.random((ny, nx)) < 0.1).astype(np.int32)
+    cells = (np.float32(THIRDS[0]) * W_EQ * (1.0 + 0.2 * (rng.random((ny, nx, 9)) - 0.5))).astype(np.float32)
+    return L.Param(nx, ny, 100, 10, *THIRDS), ob, cells, {"blocked": (ob != 0).astype(np.int32)}
+
+
+def _c11(L):      # 256 x 64 at the "thirds" point
+    return _case(L, _p10, (2, 1), {"row": (0, 62, 256, 1)})
+
+
 B3, B5, B9 = ("b", 3), ("b", 5), ("b", 9)
 FP, FM = (F, P), (F, M)
 # ctx as in test_call_sequences: None = a lattice alone; ("slabs", n, exchange); ("rank", exchange) = a rank ring of one
@@ -241,7 +263,7 @@ PROGRAMS = {
         window(6, 3, "top", "slab-tiles"), window(6, 3, "every4th", "slab-tiles"),
         driven(9, B3, "slab-tiles"), driven(8, "const", "slab-tiles"), observed(10, (F, P, M), 2, 5, 0, "slab-tiles"),
         opt("regtile_tag", SLAB_TAG_MARK - 7), driven_observed(12, B5, (F, P, M, S), 1, 4, 6, "slab-tiles"),
-        run(5, "slab-tiles"),
+        run(5, "slab-tiles"), stats(6, 3, "slab-tiles"),
     ]),
     "slabs_copy_streaming": (_c7, ("slabs", 2, "copy"), [
         opt("time_block", 2), bodies("random3", 3), probe_set("A"),
@@ -255,12 +277,12 @@ PROGRAMS = {
         bodies("walls+rest", 2), probe_set("A"),
         probes(6, 2, "slab-tiles"), window(6, 3, "mail", "slab-tiles"), driven(7, B3, "slab-tiles"),
         observed(8, (F, P, M), 2, 4, 0, "slab-tiles"), driven_observed(8, B5, (P, S), 2, 0, 4, "slab-tiles"),
-        mean(6, 3, "slab-tiles"), run(3, "slab-tiles"),
+        mean(6, 3, "slab-tiles"), run(3, "slab-tiles"), stats(6, 2, "slab-tiles"),
     ]),
     "rank_ring_of_one_rccl": (_c8, ("rank", "rccl"), [
         opt("time_block", 2), bodies("walls+rest", 2), probe_set("A"),
         probes(6, 3, "tb2"), window(6, 3, "row", "tb2"), driven(6, B3, "tb2"), observed(8, (F, P, M), 2, 4, 0, "tb2"),
-        driven_observed(8, B5, FP, 2, 0, 0, "tb2"), mean(6, 3, "tb2"), run(3, "tb2"),
+        driven_observed(8, B5, FP, 2, 0, 0, "tb2"), mean(6, 3, "tb2"), run(3, "tb2"), stats(6, 3, "tb2"),
     ]),
     "lone_tag_wrap_in_flavours": (_c9, None, [
         opt("regtile", 44), bodies("random4", 4), probe_set("A"), run(5, "tiles"),
@@ -268,6 +290,7 @@ PROGRAMS = {
         opt("regtile_tag", TAG_WRAP - 5), driven(9, B3, "tiles"),
         opt("regtile_tag", TAG_WRAP - 8), observed(12, (F, P, M), 1, 4, 0, "tiles"),
         driven(8, "const", "tiles"), driven_observed(8, "const", FP, 2, 0, 0, "tiles"), probes(6, 2, "tiles"), run(4, "tiles"),
+        stats(6, 2, "tiles"),
     ]),
     "refusal_point_mixed": (_c10, None, [
         bodies("blocked", 1), probe_set("A"),
@@ -277,6 +300,53 @@ PROGRAMS = {
         opt("time_block", 8), opt("march_kernel", 1), opt("wave_cols", 2),
         driven(10, B9, "wave"), window(10, 5, "row", "wave"), observed(16, (F, P, M), 2, 8, 0, "wave"),
         opt("engine", 3), run(4, "tiles"),
+    ]),
+    # lbm_run_stats beside every other observer call: directly behind and in front of each, on the tiles ...
+    "stats_neighbours_on_tiles_128": (_c1, None, [
+        bodies("A", 4), probe_set("A"),
+        mean(6, 2, "tiles"), stats(7, 3, "tiles"), mean(6, 3, "tiles"),
+        observed(8, (F, P, M), 2, 4, 0, "tiles"), stats(6, 2, "tiles"), observed(8, (P, M), 2, 4, 0, "tiles"),
+        window(6, 3, "A", "tiles"), stats(8, 3, "tiles"), window(6, 2, "B", "tiles"),
+        driven(6, B3, "tiles"), stats(5, 1, "tiles"), driven(6, B5, "tiles"),
+        driven_observed(8, B5, (P, M), 2, 4, 0, "tiles"), stats(9, 4, "tiles"), driven_observed(8, B9, FP, 2, 0, 0, "tiles"),
+        set_accel(X_ACCEL), stats(6, 2, "tiles"), refused("stats", 5, 6), run(4, "tiles"),
+    ]),
+    # ... and inside lbm_wave<6> (every stats call one run of a pass or more: the sums ride in the launches)
+    "stats_neighbours_on_wave6_130x37": (_c4, None, [
+        opt("time_block", 6), bodies("random4", 4), probe_set("A"),
+        mean(12, 6, "wave"), stats(13, 3, "wave"), mean(12, 4, "wave"),
+        observed(14, (F, P, M), 2, 7, 0, "wave"), stats(12, 1, "wave"), observed(14, (F, P, M), 2, 7, 0, "wave"),
+        window(13, 4, "column", "wave"), stats(14, 6, "wave"), window(12, 6, "row", "wave"),
+        driven(13, B3, "wave"), stats(13, 5, "wave"), driven(12, B5, "wave"),
+        driven_observed(14, B5, FP, 2, 0, 0, "wave"), stats(17, 7, "wave"), driven_observed(14, B9, FP, 2, 0, 0, "wave"),
+        set_accel(X_ACCEL), stats(12, 2, "wave"), refused("stats", 5, 6), run(7, "wave"),
+    ]),
+    # the pieces of a stats call are plain register-tile launches: behind a re-tiling, under both loops, across the tag wrap
+    # (three pieces of 4 + 1 from TAG_WRAP - 9: the second would reach the mark, so the wrap falls between two pieces)
+    "stats_tilings_and_tag_wrap_128x16": (_c5, None, [
+        run(3, "tiles"), bodies("random4", 4), probe_set("A"), stats(5, 2, "tiles"),
+        opt("regtile", 82), stats(7, 2, "tiles"), opt("regtile_async", 0), stats(6, 3, "tiles"),
+        opt("regtile_tag", TAG_WRAP - 9), stats(12, 4, "tiles"), mean(6, 3, "tiles"), run(4, "tiles"),
+    ]),
+    # slabs with copies: off the tiles (lbm_stats_add per slab), then on them, the pieces passing the restart mark
+    "stats_slabs_copy_256x32": (_c7, ("slabs", 2, "copy"), [
+        opt("time_block", 2), bodies("random3", 3), probe_set("A"),
+        stats(7, 3, "tb2"), mean(6, 3, "tb2"), opt("time_block", 4), stats(9, 4, "march"),
+        opt("engine", 3), stats(6, 2, "slab-tiles"),
+        opt("regtile_tag", SLAB_TAG_MARK - 7), stats(12, 4, "slab-tiles"), run(5, "slab-tiles"),
+    ]),
+    "stats_never_tiles_tb1": (_c4, None, [
+        opt("time_block", 1), bodies("random4", 4), probe_set("A"),
+        stats(7, 3, "tb1"), mean(6, 2, "tb1"), run(5, "tb1"), opt("time_block", 2), stats(7, 1, "tb2"), run(3, "tb2"),
+    ]),
+    # density 0.3, where density * (1.f / 3.f) and density / 3.f are different floats: every engine kind of a lattice alone
+    "stats_at_thirds_256x64": (_c11, None, [
+        bodies("blocked", 1), probe_set("A"),
+        stats(7, 3, "tiles"), mean(6, 3, "tiles"), window(6, 2, "row", "tiles"),
+        opt("time_block", 8), opt("march_kernel", 1), opt("wave_cols", 2),
+        stats(17, 4, "wave"), mean(16, 8, "wave"), stats(16, 1, "wave"),
+        opt("time_block", 4), opt("march_kernel", 0), stats(9, 4, "march"),
+        opt("engine", 3), stats(6, 2, "tiles"),
     ]),
 }
 REFUSING = {"refusal_point_mixed"}
@@ -351,7 +421,7 @@ class ObserverModel(Model):
     def _run(self, call, e):
         op, n, path = call[0], call[1], call[-1]
         fam = "tiles" if path in TILE_PATHS else "wave" if path == "wave" else "split"
-        kinds, pe, me, fe, sched, win = (), 0, 0, 0, None, None
+        kinds, pe, me, fe, sched, win, ste = (), 0, 0, 0, None, None, 0
         if op == "sampled":
             kinds, fe = (S,), call[2]
         elif op == "forces":
@@ -364,6 +434,8 @@ class ObserverModel(Model):
             kinds, fe, win = ("window",), call[2], call[3]
         elif op == "driven":
             sched = call[2]
+        elif op == "stats":
+            kinds, ste = ("stats",), call[2]
         elif op == "observed":
             kinds, pe, me, fe = call[2:6]
         elif op == "driven_observed":
@@ -372,14 +444,17 @@ class ObserverModel(Model):
         fe = fe if S in kinds or win else 0
         multi = op == "driven_observed" or (op == "observed" and len(kinds) >= 2)
         # the pieces: means and snapshots cut them; probes too where neither the register tiles nor lbm_wave take them
+        # (lbm_run_stats: ONE run where lbm_wave takes the sums; everywhere else, the register tiles too, a plain run per sample)
         if multi:
             cutters = (me, fe) + ((pe,) if fam == "split" else ())
+        elif op == "stats":
+            cutters = () if fam == "wave" else (ste,)
         elif fam == "split" and op not in ("run", "forces", "driven"):
             cutters = (pe, me, fe)                               # the split path of the single calls
         else:
             cutters = ()
         ends = _bounds(n, *cutters)
-        e.update(n=n, path=path, fam=fam, kinds=tuple(kinds), pe=pe, me=me, fe=fe, sched=sched, win=win, multi=multi,
+        e.update(n=n, path=path, fam=fam, kinds=tuple(kinds), pe=pe, me=me, fe=fe, ste=ste, sched=sched, win=win, multi=multi,
                  cutters=cutters, ends=ends, pieces=[b - a for a, b in zip([0] + ends, ends)], restarts=[],
                  sched_name=None if sched is None else sched if sched == "const" else sched[0],
                  labels=self.label(path), lone=self.lone, dtab_grew=False)
@@ -412,6 +487,8 @@ def expected_keys(e):
     single = {"sampled": "samples", "forces": "forces", "probes": "probes", "mean": "mean", "window": "window", "driven": "driven"}
     if op in single:
         return {single[op] + "_in_kernel": int(T), single[op] + "_in_wave": int(W)}
+    if op == "stats":                                            # (the ONE piece on lbm_wave: n >= time_block; no *_in_kernel key)
+        return {"stats_in_wave": int(W)}
     if op == "observed":
         return {"observed_in_kernel": bits if T else 0, "observed_in_wave": bits if W else 0, "observed_pieces": len(e["pieces"])}
     if op == "driven_observed":
@@ -544,8 +621,27 @@ TRANSITIONS = {
     "lone tag restart inside a driven call": _restart("driven", True),
     "lone tag restart between two pieces of an observed call": _restart("observed", True, mid=True),
     "slab tag restart inside a driven_observed call": _restart("driven_observed", False),
+    "lone tag restart between two pieces of a stats call": _restart("stats", True, mid=True),
+    "slab tag restart behind a piece of a stats call": _restart("stats", False),
+    "set_accel, stats on tiles": lambda t: any(
+        r["accel"] == s["accel_after"] != s["accel"] for s, r in _chains(t, [_is("set_accel"), _is("stats", fam="tiles")], _quiet)),
+    "set_accel, stats on wave": lambda t: any(
+        r["accel"] == s["accel_after"] != s["accel"] for s, r in _chains(t, [_is("set_accel"), _is("stats", "wave")], _quiet)),
+    "a stats call, a retile, a stats call": lambda t: any(
+        a["ty"] != b["ty"] for a, _, b in _chains(t, [_is("stats", "tiles"), _is("opt", key="regtile"), _is("stats", "tiles")], _quiet)),
 }
-REFUSALS = ("window", "schedule", "probes", "forces", "mean", "observed mean")
+# lbm_run_stats directly behind and directly in front of each of these, on the tiles and inside lbm_wave
+STATS_NEIGHBOURS = {"mean": {}, "observed": dict(has=(M,)), "window": {}, "driven": {}, "driven_observed": {}}
+for _fam in ("tiles", "wave"):
+    for _k, _kw in STATS_NEIGHBOURS.items():
+        TRANSITIONS[f"{_k}, then stats on {_fam}"] = (
+            lambda t, k=_k, kw=_kw, fam=_fam: bool(_chains(t, [_is(k, fam=fam, **kw), _is("stats", fam=fam)], _quiet)))
+        TRANSITIONS[f"stats, then {_k} on {_fam}"] = (
+            lambda t, k=_k, kw=_kw, fam=_fam: bool(_chains(t, [_is("stats", fam=fam), _is(k, fam=fam, **kw)], _quiet)))
+# (context, path family) in which lbm_run_stats must run; "thirds": a lattice alone at density 0.3
+STATS_AT = ([(c, "tiles") for c in ("lone", "slabs p2p", "slabs copy", "rank p2p")] + [("lone", "wave"), ("lone", "split"), ("slabs copy", "split"),
+            ("rank rccl", "split"), ("thirds", "tiles"), ("thirds", "wave")])
+REFUSALS = ("window", "schedule", "probes", "forces", "mean", "observed mean", "stats")
 COVERAGE_PATHS = ("tiles R1", "tiles R2", "tiles R4", "tiles async0", "tiles async1", "slab-tiles", "tb1", "tb2", "march", "wave")
 COVERAGE_CONTEXTS = ("lone", "slabs p2p", "slabs copy", "rank p2p", "rank rccl")
 WINDOW_SHAPES = ("stride > 1", "a single row", "a single column", "across a tile seam", "across a slab seam", "the whole lattice")
@@ -574,8 +670,9 @@ def _window_shapes(m, case):
 
 
 def coverage(L, programs):
-    """What a table of programs covers: (pairs, contexts, transitions, refusals, window shapes, waves, mixes at the refusal point)."""
-    pairs, contexts, found, refusals, shapes, waves, refusing = set(), set(), set(), set(), set(), set(), False
+    """What a table of programs covers: (pairs, contexts, transitions, refusals, window shapes, waves, mixes at the refusal point,
+    (context, path family) of the stats calls)."""
+    pairs, contexts, found, refusals, shapes, waves, refusing, stats_at = set(), set(), set(), set(), set(), set(), False, set()
     for name, (setup, ctx, calls) in programs.items():
         case = setup(L)
         m = ObserverModel(L, case, ctx)
@@ -583,7 +680,11 @@ def coverage(L, programs):
             m.apply(c)
         assert 5 <= len(calls) <= 25, name
         pairs |= {pk for pk in m.pairs if pk[1] in KINDS}
-        contexts.add("lone" if ctx is None else " ".join(str(v) for v in (ctx[0], ctx[-1])))
+        context = "lone" if ctx is None else " ".join(str(v) for v in (ctx[0], ctx[-1]))
+        contexts.add(context)
+        stats_at |= {(context, e["fam"]) for e in m.trace if e["op"] == "stats"}
+        if ctx is None and np.float32(m.p.density) == np.float32(THIRDS[0]):
+            stats_at |= {("thirds", e["fam"]) for e in m.trace if e["op"] == "stats"}
         found |= {t for t, holds in TRANSITIONS.items() if holds(m.trace)}
         shapes |= _window_shapes(m, case)
         waves |= m.waves
@@ -596,16 +697,17 @@ def coverage(L, programs):
             mix = {(e["op"], e["path"]) for e in m.trace if e["running"]}
             refusing = refusing or (all((k, q) in mix for k in ("driven", "window", "observed") for q in ("tiles", "march", "wave"))
                                     and any(e["op"] == "driven" and e["sched_name"] == "b" for e in m.trace))
-    return pairs, contexts, found, refusals, shapes, waves, refusing
+    return pairs, contexts, found, refusals, shapes, waves, refusing, stats_at
 
 
 def missing(L, programs):
-    pairs, contexts, found, refusals, shapes, waves, refusing = coverage(L, programs)
+    pairs, contexts, found, refusals, shapes, waves, refusing, stats_at = coverage(L, programs)
     out = [(lab, k) for lab in COVERAGE_PATHS for k in KINDS if (lab, k) not in pairs]
     out += [c for c in COVERAGE_CONTEXTS if c not in contexts]
     out += [t for t in TRANSITIONS if t not in found]
     out += ["refused: " + r for r in REFUSALS if r not in refusals]
     out += ["window: " + s for s in WINDOW_SHAPES if s not in shapes]
+    out += ["stats on %s, %s" % at for at in STATS_AT if at not in stats_at]
     if len({k for k, _ in waves if k in (4, 6, 8)}) < 2:
         out.append("lbm_wave at two of K = 4, 6, 8")
     if not any(c == 2 for _, c in waves):
@@ -630,7 +732,8 @@ def test_program_table_covers_every_path_and_transition(L):
             assert (e["fam"] != "wave") or e["n"] >= e["tb"] >= 4, where              # lbm_wave runs: a full pass at least
             if e["op"] == "observed":
                 assert len(e["kinds"]) >= 2, where                                     # (one observer alone is its own call)
-            assert all(k in (F, P, M, S, "window") for k in e["kinds"]), where
+            assert all(k in (F, P, M, S, "window", "stats") for k in e["kinds"]), where
+            assert ("stats" in e["kinds"]) == (e["op"] == "stats") == (e["ste"] > 0) and e["ste"] <= e["n"], where
             for k, ev in ((P, e["pe"]), (M, e["me"]), (S, e["fe"])):
                 assert (k in e["kinds"] or (k == S and bool(e["win"]))) == (ev > 0) and ev <= e["n"], where
             if e["win"]:
@@ -646,10 +749,14 @@ def test_program_table_covers_every_path_and_transition(L):
 
 
 @pytest.mark.parametrize("drop", [("lone_128_flavour_walk", 4), ("wave6_maps_130x37", 6), ("slabs_p2p_tiles_tag_restart", 12),
-                                  ("rank_ring_of_one_rccl", None), ("schedule_table_128x16", 4), ("never_tiles_tb1_tb2", 12)])
+                                  ("rank_ring_of_one_rccl", None), ("schedule_table_128x16", 4), ("never_tiles_tb1_tb2", 12),
+                                  ("stats_neighbours_on_tiles_128", 9), ("stats_neighbours_on_wave6_130x37", 13),
+                                  ("stats_tilings_and_tag_wrap_128x16", 9), ("stats_slabs_copy_256x32", 10), ("stats_at_thirds_256x64", None),
+                                  ("rank_ring_of_one_p2p", 9), ("stats_never_tiles_tb1", 3)])
 def test_a_trimmed_table_fails_the_coverage_check(L, drop):
-    """Without one call (a flavour of the walk, a relabel, the tag option, the long driven call, a refused call) or one
-    program (a context) the table no longer covers the list."""
+    """Without one call (a flavour of the walk, a relabel, the tag option, the long driven call, a refused call; a stats call
+    between two windows or two driven calls, the tag option in front of one, the one whose pieces pass a mark, the one of a
+    context or a path) or one program (a context, the density 0.3) the table no longer covers the list."""
     name, index = drop
     programs = dict(PROGRAMS)
     if index is None:
@@ -674,7 +781,8 @@ def test_model_restates_the_tag_and_capacity_rules(L):
     m, _ = _walk(L, "slabs_p2p_tiles_tag_restart")
     e = m.trace[13]
     assert e["op"] == "driven_observed" and e["pieces"] == [4, 2, 2, 4] and e["restarts"] == [1]
-    assert e["tag"] == 1 + 3 + 5 and m.trace[-1]["tag"] == 9 + 6                   # cleared behind the second piece
+    assert e["tag"] == 1 + 3 + 5 and m.trace[14]["tag"] == 9 + 6                   # cleared behind the second piece
+    assert m.trace[15]["op"] == "stats" and m.trace[15]["pieces"] == [3, 3] and m.trace[15]["tag"] == 15 + 4 + 4
     assert m.trace[11]["pieces"] == [5, 5] and m.trace[11]["tag"] - m.trace[10]["tag"] == 6 + 6
     m, _ = _walk(L, "schedule_table_128x16")
     first, second, third = m.trace[3], m.trace[4], m.trace[5]
@@ -691,6 +799,18 @@ def test_model_restates_the_tag_and_capacity_rules(L):
     e = next(x for x in m.trace if x["op"] == "observed")
     assert e["ends"] == [2, 3, 4, 6, 8, 9] and expected_keys(e)["observed_pieces"] == 6
     assert all(x["tag"] == 1 for x in m.trace)
+    # lbm_run_stats: a plain launch per sample on the tiles, the marks tested per piece; one run inside lbm_wave
+    m, _ = _walk(L, "stats_tilings_and_tag_wrap_128x16")
+    e = m.trace[9]
+    assert e["call"] == stats(12, 4, "tiles") and e["pieces"] == [4, 4, 4] and e["restarts"] == [1] and e["tag"] == 1 + 5 + 5
+    assert m.trace[3]["pieces"] == [2, 2, 1] and m.trace[3]["tag"] == 1 + 4 + 3 + 3 + 2 and expected_keys(e) == {"stats_in_wave": 0}
+    m, _ = _walk(L, "stats_slabs_copy_256x32")
+    e = m.trace[10]
+    assert e["call"] == stats(12, 4, "slab-tiles") and e["pieces"] == [4, 4, 4] and e["restarts"] == [1] and e["tag"] == 1 + 5
+    assert m.trace[3]["pieces"] == [3, 3, 1] and m.trace[3]["tag"] == 1 and expected_keys(m.trace[3]) == {"stats_in_wave": 0}
+    m, _ = _walk(L, "stats_neighbours_on_wave6_130x37")
+    e = m.trace[4]
+    assert e["call"] == stats(13, 3, "wave") and e["pieces"] == [13] and expected_keys(e) == {"stats_in_wave": 1} and e["tag"] == 1
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
@@ -876,6 +996,9 @@ def _call(lat, e, case, acc):
         return av, {"window": out}
     if op == "driven":
         return lat.run_driven(acc), {}
+    if op == "stats":
+        av, out = lat.run_stats(n, e["ste"])
+        return av, {"stats": out}
     res = lat.run_observed(n, **_want(e)) if op == "observed" else lat.run_driven_observed(acc, **_want(e))
     return res.pop("av_vels"), res
 
@@ -914,6 +1037,8 @@ def _refuse(L, lat, e, case):
             lat.run_forces(a[0])
         elif what == "mean":
             lat.run_mean(a[0], a[1])
+        elif what == "stats":
+            lat.run_stats(a[0], a[1])
         else:
             assert what == "observed mean"
             lat.run_observed(a[0], forces=e["nb"] > 0, mean_every=a[1])
@@ -963,7 +1088,7 @@ def test_observer_sequence(gpu, O, oracle, monkeypatch, name):
                 else:
                     n, kinds, tiles = e["n"], e["kinds"], e["fam"] == "tiles"
                     acc = _schedule(e["sched"], p, e["accel"], n)
-                    want_fields = any(k in kinds for k in (P, M, S, "window"))
+                    want_fields = any(k in kinds for k in (P, M, S, "window", "stats"))
                     st0 = lat.read_state() if e["sched"] == "const" else None
                     if kind == "run":
                         av_sh, F_sh, X, numpy_forces = sh.run(n), None, None, None
@@ -980,6 +1105,8 @@ def test_observer_sequence(gpu, O, oracle, monkeypatch, name):
                         exp[S] = X[e["fe"] - 1::e["fe"]]
                     if e["win"]:
                         exp["window"] = cut(X[e["fe"] - 1::e["fe"]], case["windows"][e["win"]])
+                    if "stats" in kinds:
+                        exp["stats"] = stats_of(X[e["ste"] - 1::e["ste"]], p0_of(p.density))
                     assert sorted(out) == sorted(kinds), (where, sorted(out))
                     for k, v in exp.items():
                         _same(out[k], v, where + (k,))
