@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "lbm_last_error", "lbm_device_count", "lbm_create", "lbm_rccl_unique_id", "lbm_create_rank",
     "lbm_create_rank_ex", "lbm_p2p_handle", "lbm_p2p_connect",
     "lbm_slab_rows", "lbm_num_slabs", "lbm_run", "lbm_run_sampled", "lbm_run_mean", "lbm_run_stats", "lbm_set_bodies", "lbm_run_forces",
-    "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows",
+    "lbm_set_probes", "lbm_run_probes", "lbm_run_observed", "lbm_run_window", "lbm_window_rows", "lbm_run_window_stats",
     "lbm_set_accel", "lbm_run_driven", "lbm_run_driven_observed",
     "lbm_last_run_ms", "lbm_read_state", "lbm_set_obstacles", "lbm_write_state",
     "lbm_av_velocity", "lbm_reynolds", "lbm_total_density", "lbm_final_state", "lbm_destroy",
@@ -118,6 +118,7 @@ def load_library():
     lib.lbm_run_forces.argtypes = [vp, C.c_int, vp, vp]
     lib.lbm_run_observed.argtypes = [vp, C.c_int, vp, C.POINTER(Observe)]
     lib.lbm_run_window.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(Window), vp]
+    lib.lbm_run_window_stats.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(Window), vp]
     lib.lbm_window_rows.argtypes = [C.POINTER(Window), C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
     lib.lbm_set_accel.argtypes = [vp, C.c_float]
     lib.lbm_run_driven.argtypes = [vp, C.c_int, vp, vp]
@@ -347,6 +348,23 @@ class Lattice:
         windows, ptr = self._output(out, shape, "out")
         _check(self._lib.lbm_run_window(self._ctx, nsteps, av.ctypes.data, every, C.byref(window), ptr))
         return av, windows
+
+    def run_window_stats(self, nsteps: int, every: int, window: Window, out=None):
+        """run_stats over a window: returns (av_vels[nsteps], stats) where stats is (window.ny, window.nx, 8) float32 -- the
+        eight floats run_stats has in the cells (window.x0 + c window.sx, window.y0 + r window.sy) of the global lattice, bit
+        for bit: the means of u_x, u_y, |u|, pressure and of u_x^2, u_y^2, u_x u_y, (p - p0)^2 over the sample steps every,
+        2 every, ... -- a numpy array, or `out`, a contiguous float32 torch tensor of that shape on the context's GPU, filled
+        there.  A rank context fills the window rows that lie in its own lattice rows and zeroes the others.  Device memory
+        for the sums is 32 bytes per window cell.  Where lbm_wave runs the sums ride in its launches
+        (info("window_stats_in_wave") == 1); the register tiles take the samples inside their kernels, set_option(
+        "window_stats_chunk") sample steps a launch, and a fold kernel adds them up (info("window_stats_in_kernel") == 1;
+        info("window_stats_pieces"): the launches); either way av_vels is run()'s bits.  Elsewhere the steps run in pieces
+        of `every` with a windowed add kernel behind each."""
+        shape = (window.ny, window.nx, 8)
+        av = np.empty(max(nsteps, 0), dtype=np.float32)
+        stats, ptr = self._output(out, shape, "out")
+        _check(self._lib.lbm_run_window_stats(self._ctx, nsteps, av.ctypes.data, every, C.byref(window), ptr))
+        return av, stats
 
     def set_bodies(self, body, nbodies: int):
         """Labels blocked cells 1..nbodies (0: not counted) for run_forces: body is int[ny, nx] over the global lattice

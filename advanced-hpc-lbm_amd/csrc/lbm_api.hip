@@ -273,6 +273,10 @@ struct lbm_ctx {
   int probes_in_wave = 0;      // 1: the last lbm_run_probes took its values inside lbm_wave launches
   int window_in_kernel = 0;    // 1: the last lbm_run_window took its window inside the register tiles
   int window_in_wave = 0;      // 1: the last lbm_run_window took its window inside lbm_wave launches
+  int window_stats_in_wave = 0;    // 1: the last lbm_run_window_stats took its sums inside lbm_wave launches
+  int window_stats_in_kernel = 0;  // 1: ... its samples inside the register tiles (staged there, folded into the sums behind each piece)
+  int window_stats_pieces = 0;     // ... and the step-loop pieces it ran (1: the whole call in one)
+  int window_stats_chunk = 0;      // option: the most sample steps one register-tile piece of lbm_run_window_stats holds (0: automatic)
   int driven_in_kernel = 0;    // 1: the last lbm_run_driven ran inside the register tiles (their kRegDrive flavour)
   int driven_in_wave = 0;      // 1: the last lbm_run_driven ran its groups of K steps inside lbm_wave launches (the driven flavour)
   int driven_observed_in_kernel = 0;  // the last lbm_run_driven_observed: bits 1 forces, 2 probes, 4 means, 8 snapshots taken inside register-tile launches
@@ -729,7 +733,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (done) {
       c->engine_last = 3;
       if (k.flavour == RegFlavour::window) c->window_in_kernel = 1;
-      else if (k.flavour == RegFlavour::probes || (k.flavour == RegFlavour::piece && k.snap)) c->probes_in_kernel = 1;
+      else if (k.flavour == RegFlavour::probes || (k.flavour == RegFlavour::piece && k.snap && !k.win_table)) c->probes_in_kernel = 1;
       else if (k.flavour == RegFlavour::mean) c->mean_in_kernel = 1;
       else if (k.flavour == RegFlavour::snapshots) c->samples_in_kernel = 1;
       if (fo) c->forces_in_kernel = 1;
@@ -771,8 +775,10 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     HIPC(hipSetDevice(sl.dev));
     int rc;
     if (psample(s) && (rc = launch_probe_gather(c, sl, w.pout + 4 * (size_t)w.prow(k.pfirst, s) * (size_t)c->nprobes))) return rc;
-    if (fsample(s) && w.fadd && (rc = w.fstats ? launch_stats_add(c, sl, w.fout) : launch_mean_add(c, sl, w.fout))) return rc;
-    if (fsample(s) && w.win && (rc = launch_derive_window(c, sl, w.win->w, 0, w.win->w.ny, w.fslot(s)))) return rc;
+    const bool wstats = w.win && w.fstats;       // (lbm_run_window_stats: the sums over the window's cells)
+    if (fsample(s) && wstats && (rc = launch_window_stats_add(c, sl, w.win->w, 0, w.win->w.ny, w.fout))) return rc;
+    if (fsample(s) && w.fadd && !wstats && (rc = w.fstats ? launch_stats_add(c, sl, w.fout) : launch_mean_add(c, sl, w.fout))) return rc;
+    if (fsample(s) && w.win && !wstats && (rc = launch_derive_window(c, sl, w.win->w, 0, w.win->w.ny, w.fslot(s)))) return rc;
     if (fsample(s) && !w.fadd && !w.win) {
       const long ncell = (long)sl.nyl * nx;
       hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,
@@ -895,7 +901,7 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (fwave) c->forces_in_wave = 1;
     if (dwave) c->driven_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
-    if (fw && wave) (w.win ? c->window_in_wave : w.fstats ? c->stats_in_wave : w.fadd ? c->mean_in_wave : c->samples_in_wave) = 1;
+    if (fw && wave) (w.win && w.fstats ? c->window_stats_in_wave : w.win ? c->window_in_wave : w.fstats ? c->stats_in_wave : w.fadd ? c->mean_in_wave : c->samples_in_wave) = 1;
     Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
     hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
@@ -1196,6 +1202,11 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
     regtile_set(c, ty, r, c->p.ny / ty);
     return LBM_OK;
   }
+  if (!strcmp(key, "window_stats_chunk")) {   // lbm_run_window_stats on the register tiles: sample steps per piece (0: automatic)
+    if (value < 0 || value > 0x7fffffffL) return fail(LBM_EINVAL, "window_stats_chunk must be 0 (automatic) or a positive number of sample steps");
+    c->window_stats_chunk = (int)value;
+    return LBM_OK;
+  }
   if (!strcmp(key, "kernel_variant")) {
     if (value < 0 || value > 15) return fail(LBM_EINVAL, "kernel_variant must be in [0, 15]");
     c->variant = value;      // (bit 3: the one-step kernel with the reference's speed sum; see t2_eligible / march_eligible / lbm_run)
@@ -1218,6 +1229,8 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
       {"stats_in_wave", &lbm_ctx::stats_in_wave},
       {"probes_in_kernel", &lbm_ctx::probes_in_kernel}, {"probes_in_wave", &lbm_ctx::probes_in_wave},
       {"window_in_kernel", &lbm_ctx::window_in_kernel}, {"window_in_wave", &lbm_ctx::window_in_wave},
+      {"window_stats_in_wave", &lbm_ctx::window_stats_in_wave}, {"window_stats_in_kernel", &lbm_ctx::window_stats_in_kernel},
+      {"window_stats_pieces", &lbm_ctx::window_stats_pieces}, {"window_stats_chunk", &lbm_ctx::window_stats_chunk},
       {"driven_in_kernel", &lbm_ctx::driven_in_kernel}, {"driven_in_wave", &lbm_ctx::driven_in_wave},
       {"driven_observed_in_kernel", &lbm_ctx::driven_observed_in_kernel}, {"driven_observed_in_wave", &lbm_ctx::driven_observed_in_wave},
       {"driven_observed_pieces", &lbm_ctx::driven_observed_pieces},

@@ -504,7 +504,7 @@ int launch_band_group(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev
 // neighbours (K = 8, one or two columns) in the plain one; math = IEEE or fast rcp / sqrt (bit 0) x nontemporal stores (bit 1).
 // What a flavour (lbm_wave_pick.h) switches on in the kernel, by lbm_wave's template parameters:
 struct WaveTraits { bool FORCE, PROBE, FIELD, WINDOW, DRIVEN, STATS; };
-constexpr WaveTraits kWaveTraits[9] = {
+constexpr WaveTraits kWaveTraits[10] = {
     /* plain           */ {false, false, false, false, false, false},
     /* force           */ {true, false, false, false, false, false},    // lbm_run_forces
     /* probe           */ {false, true, false, false, false, false},    // lbm_run_probes
@@ -514,6 +514,7 @@ constexpr WaveTraits kWaveTraits[9] = {
     /* driven          */ {false, false, false, false, true, false},    // lbm_run_driven
     /* driven_observed */ {true, true, false, false, true, false},      // lbm_run_driven_observed
     /* stats           */ {false, false, false, false, false, true},    // lbm_run_stats
+    /* window_stats    */ {false, false, false, true, false, true},     // lbm_run_window_stats
 };
 template <int K, bool SLAB, int C, WaveFlavour F>
 wave_fn wave_kernel_m(int math) {
@@ -545,6 +546,7 @@ wave_fn wave_kernel(int K, bool slab, int C, int math, WaveFlavour f) {
     case WaveFlavour::force_probe: return wave_kernel_kc<WaveFlavour::force_probe>(K, slab, C, math);
     case WaveFlavour::probe: return wave_kernel_kc<WaveFlavour::probe>(K, slab, C, math);
     case WaveFlavour::stats: return wave_kernel_kc<WaveFlavour::stats>(K, slab, C, math);
+    case WaveFlavour::window_stats: return wave_kernel_kc<WaveFlavour::window_stats>(K, slab, C, math);
   }
   return nullptr;
 }

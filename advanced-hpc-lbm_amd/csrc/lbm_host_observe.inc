@@ -1,6 +1,7 @@
 // lbm_host_observe.inc -- part of lbm_api.hip (included there, in front of run_steps): the observer calls -- lbm_run_sampled,
 // lbm_run_forces, lbm_run_mean, lbm_run_probes with lbm_set_bodies / lbm_set_probes, lbm_run_observed, and lbm_run_window
-// with lbm_window_rows (WindowOut, window_tables, launch_derive_window: in front of it) -- and the one copy of what they share:
+// with lbm_window_rows (WindowOut, window_tables, launch_derive_window: in front of it), lbm_run_window_stats behind it
+// (WindowStats) -- and the one copy of what they share:
 //   output_on_device, ranks_agree          where an output lies; a rank context's ranks take the same path and fail together
 //   launch_probe_gather / _mean_add / _mean_div   the one launch site of each small kernel (run_steps' pgather uses them too)
 //   fetch_forces                           a run's forces from behind its per-step sums
@@ -705,6 +706,18 @@ int launch_derive_window(const lbm_ctx* c, Slab& s, const lbm_window& w, int fir
   return LBM_OK;
 }
 
+// ... and, for lbm_run_window_stats, added with their products to acc8 = float[count][w.nx][8], the sums of those rows
+int launch_window_stats_add(const lbm_ctx* c, Slab& s, const lbm_window& w, int first, int count, float* acc8) {
+  if (count <= 0) return LBM_OK;
+  const long ncell = (long)count * w.nx;
+  const long yl0 = (long)w.y0 + (long)first * w.sy - s.row0;
+  HIPC(hipSetDevice(s.dev));
+  hipLaunchKernelGGL(lbm::lbm_window_stats_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
+                     w.x0, w.nx > 1 ? w.sx : 1, w.nx, (int)yl0, count > 1 ? w.sy : 1, ncell, s.blocked, c->p.density, acc8);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
 // The window table of a slab for tiles of ty rows, fed to the probe flavour as the probe set's is: a cell's word is its place
 // among the SLAB's window rows + 1, (r - first) w.nx + c + 1 -- the slab's output pointer is its first window row's.  Kept by
 // (window, tiling); the probe set's table is not touched.  LBM_ENOMEM: nothing queued.
@@ -877,6 +890,222 @@ extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every,
   // derived into sample j on every local slab
   if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int j) { return wo.derive(j); }))) return rc;
   return wo.finish();
+}
+
+// ----------------------------------------------------------------- stats over a window (lbm_run_window_stats; DESIGN.md 3.20)
+namespace {
+
+// The staging bound of the register-tile path: the most bytes of staged samples one slab holds at a time.  Scratch-memory
+// policy, not a tuned number (DESIGN.md 3.20): 64 MiB is four samples of the largest window a register-tile lattice has
+// (1024 x 1024 cells, 16 MiB a sample) and thousands of a wake window's.
+constexpr size_t kWindowStatsStageBytes = 64u << 20;
+
+// Where one call's sums over a window live and go: per slab that holds a window row, the sums of its own window rows,
+// float[count][w.nx][8] -- 32 bytes per window cell of the slab, on every path -- and, on the register tiles, the staging of
+// one piece's samples, float[chunk][count][w.nx][4].  The output is [w.ny][w.nx][8]: device output is written in place by
+// the divide, host output is the sums divided in place and copied out.
+struct WindowStats {
+  lbm_ctx* c;
+  lbm_window w;
+  float* out = nullptr;
+  bool on_dev = false;
+  long local = 0;                          // window rows that the slabs of this context hold
+  std::vector<int> first, count;           // per slab: its window rows
+  std::vector<DeviceTemp> acc, stage;
+
+  WindowStats(lbm_ctx* ctx, const lbm_window& win) : c(ctx), w(win) {
+    for (auto& s : c->slabs) {
+      int f = 0, n = 0;
+      (void)lbm_window_rows(&w, c->p.nx, c->p.ny, s.row0, s.row0 + s.nyl, &f, &n);
+      first.push_back(f); count.push_back(n); local += n;
+    }
+  }
+  int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
+  long cells(size_t i) const { return (long)count[i] * w.nx; }
+  size_t bytes(size_t i) const { return sizeof(float) * 8 * (size_t)cells(i); }
+  // the slabs' sums (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
+  int prepare() {
+    acc.resize(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      HIPC(hipSetDevice(s.dev));
+      if (hipMalloc(&acc[i].p, bytes(i)) != hipSuccess) {
+        (void)hipGetLastError();
+        acc[i].p = nullptr;
+        return fail(LBM_ENOMEM, "no room on device %d for the window sums of slab %zu (%zu bytes)", s.dev, i, bytes(i));
+      }
+    }
+    return LBM_OK;
+  }
+  // the most samples a piece may stage under the bound: at least 1, at most m
+  int auto_chunk(int m) const {
+    size_t per = 0;                          // bytes of one sample of the slab with the most window cells
+    for (size_t i = 0; i < c->slabs.size(); ++i) per = std::max(per, sizeof(float) * 4 * (size_t)cells(i));
+    const size_t fit = per ? kWindowStatsStageBytes / per : (size_t)m;
+    return (int)std::min<size_t>((size_t)m, std::max<size_t>(1, fit));
+  }
+  // the staging of `chunk` samples on every slab that holds a window row; false: no room, nothing kept, nothing queued
+  bool stage_room(int chunk) {
+    stage.clear(); stage.resize(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      if (hipSetDevice(s.dev) != hipSuccess || hipMalloc(&stage[i].p, sizeof(float) * 4 * (size_t)cells(i) * (size_t)chunk) != hipSuccess) {
+        (void)hipGetLastError();
+        stage[i].p = nullptr;
+        stage.clear();
+        return false;
+      }
+    }
+    return true;
+  }
+  int clear() {
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemsetAsync(acc[i].p, 0, bytes(i), s.sc));
+    }
+    return LBM_OK;
+  }
+  // the window rows of other ranks' lattice rows read +0.0f
+  int zero_foreign() {
+    if (local >= w.ny) return LBM_OK;
+    const size_t all = sizeof(float) * 8 * (size_t)w.nx * (size_t)w.ny;
+    if (on_dev) {
+      Slab& s = c->slabs[0];
+      HIPC(hipSetDevice(s.dev));
+      HIPC(hipMemsetAsync(out, 0, all, s.sc));
+      HIPC(hipStreamSynchronize(s.sc));
+    } else memset(out, 0, all);
+    return LBM_OK;
+  }
+  float* sums(size_t i) const { return (float*)acc[i].p; }
+  float* staged(size_t i) const { return stage.empty() ? nullptr : (float*)stage[i].p; }
+  float* out_rows(size_t i) const { return out + 8 * (size_t)first[i] * (size_t)w.nx; }
+  // the window cells of the stored lattice and their products added to the sums, on every slab that holds a window row
+  int add() {
+    int rc;
+    for (size_t i = 0; i < c->slabs.size(); ++i)
+      if ((rc = launch_window_stats_add(c, c->slabs[i], w, first[i], count[i], sums(i)))) return rc;
+    return LBM_OK;
+  }
+  // the n samples a register-tile piece staged, added to the sums in step order, behind the piece on every slab's stream
+  int fold(int n) {
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      HIPC(hipSetDevice(s.dev));
+      hipLaunchKernelGGL(lbm::lbm_window_stats_fold, dim3(cdiv(cells(i), lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, staged(i), cells(i), n,
+                         c->p.density, sums(i));
+      HIPC(hipGetLastError());
+    }
+    return LBM_OK;
+  }
+  // the sums of m samples divided into their place (lbm_mean_div: IEEE division, as lbm_run_stats finishes), every slab's
+  // stream waited for, host output copied out
+  int finish(int m) {
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      HIPC(hipSetDevice(s.dev));
+      if (count[i] > 0) {
+        hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(2 * cells(i), lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, sums(i), 2 * cells(i), (float)m,
+                           on_dev ? out_rows(i) : sums(i));
+        HIPC(hipGetLastError());
+      }
+      HIPC(hipStreamSynchronize(s.sc));
+      if (count[i] > 0 && !on_dev) HIPC(hipMemcpy(out_rows(i), sums(i), bytes(i), hipMemcpyDeviceToHost));
+    }
+    return LBM_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int lbm_run_window_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, const lbm_window* win, float* stats_out) {
+  // (the three pointers first, each on its own: none of them is optional, whatever the other arguments say)
+  if (!win) return fail(LBM_EINVAL, "win is NULL");
+  if (!stats_out) return fail(LBM_EINVAL, "stats_out is NULL");
+  if (!c) return fail(LBM_EINVAL, "ctx is NULL");
+  int rc;
+  if ((rc = window_check(win, c->p.nx, c->p.ny))) return rc;
+  if (nsteps < 0) return fail(LBM_EINVAL, "nsteps < 0");
+  if (every <= 0) return fail(LBM_EINVAL, "every must be positive (got %d)", every);
+  const int m = nsteps / every;
+  if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
+  WinPlan plan;
+  plan.w = *win;
+  const bool wave_exact = window_for_wave(plan.w, &plan.wave);
+  WindowStats ws(c, plan.w);
+  if ((rc = ws.locate(stats_out, "stats_out"))) return rc;
+  c->window_stats_in_wave = 0; c->window_stats_in_kernel = 0; c->window_stats_pieces = 0;
+  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  // ---- everything that can fail for want of room is decided here, before anything is queued.  The sums must fit; the
+  // register tiles' tables or staging that do not: the split path, the same bits, nobody fails.
+  rc = ws.prepare();
+  bool tiles = regtile_is_next(c);
+  const int chunk = c->window_stats_chunk > 0 ? std::min(c->window_stats_chunk, m) : ws.auto_chunk(m);
+  for (size_t i = 0; i < c->slabs.size() && !rc && tiles; ++i)
+    tiles = window_tables(c->slabs[i], c->tplan.ty, c->tplan.ntx, plan.w, ws.first[i], ws.count[i]) == LBM_OK &&
+            empty_table(c->slabs[i], c->tplan.ty, c->tplan.ntx) == LBM_OK;
+  if (!rc && tiles) tiles = ws.stage_room(chunk);
+  if ((rc = ranks_agree(c, rc, &tiles, "the window sums"))) return rc;
+  if ((rc = ws.zero_foreign())) return rc;
+  if ((rc = ws.clear())) return rc;
+  // ---- where lbm_run would run lbm_wave (a lattice alone; admission as lbm_run_stats'): ONE run, the groups of K steps that
+  // hold a sample step in lbm_wave's window-stats flavour, lbm_window_stats_add behind the left-over steps that are sample
+  // steps.  A window whose multiply-high would not be exact: the pieces below, the same bits.
+  if (!regtile_is_next(c) && wave_exact && nsteps >= c->time_block && wave_admit(c, false)) {
+    RunKind k;
+    k.no_tiles = true; k.wave.fout = ws.sums(0); k.wave.fevery = every; k.wave.fstride = 0; k.wave.fadd = true; k.wave.fstats = true;
+    k.wave.win = &plan;
+    if ((rc = run_steps(c, nsteps, av_vels, k))) return rc;
+    c->window_stats_pieces = 1;
+    return ws.finish(m);
+  }
+  // ---- the pieces.  On the register tiles: `chunk` sample steps a piece, in the piece flavour (RegFlavour::piece, which
+  // alone knows a first-sample phase and folds a cut piece's last step sum as a whole run folds it, piece_mid: av_vels is
+  // lbm_run's bits wherever the call is cut) fed the window tables as its probe tables and the table of -1s for forces; it
+  // stores the piece's samples into the slab's staging, lbm_window_stats_fold adds them to the sums behind it; the steps
+  // past m every run as one more piece without samples.  A piece that gives up, or whose flavour is not resident, has
+  // stepped nothing: from the same step on, and everywhere else, pieces of `every` steps with lbm_window_stats_add behind each.
+  double gpu_ms = 0.0, wall_ms = 0.0;
+  int done = 0, taken = 0, pieces = 0;
+  while (done < nsteps) {
+    float* av = av_vels ? av_vels + done : nullptr;
+    if (tiles && regtile_is_next(c)) {
+      const int cc = std::min(chunk, m - taken);            // (0: the tail behind the last sample step)
+      const int n = cc > 0 ? cc * every : nsteps - done;
+      SnapPlan sp;
+      sp.every = every;
+      for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(ws.staged(i)); sp.stride.push_back(4 * ws.cells(i)); }
+      bool ran = false;
+      RunKind k;
+      k.flavour = RegFlavour::piece; k.piece_mid = done + n < nsteps; k.ran = &ran;
+      if (cc > 0) { k.snap = &sp; k.pfirst = every; k.win_table = true; }
+      if ((rc = run_steps(c, n, av, k))) return rc;
+      if (!ran) { tiles = false; continue; }                // (nothing stepped: this piece again, on the split path)
+      if (cc > 0) {
+        if ((rc = ws.fold(cc))) return rc;
+        c->window_stats_in_kernel = 1;
+      }
+      taken += cc; done += n;
+    } else {
+      const int n = taken < m ? every : nsteps - done;
+      if ((rc = run_steps(c, n, av))) return rc;
+      done += n;
+      if (taken < m) {
+        if ((rc = ws.add())) return rc;
+        ++taken;
+      }
+    }
+    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
+    ++pieces;
+  }
+  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  c->window_stats_pieces = pieces;
+  return ws.finish(m);
 }
 
 static_assert(sizeof(lbm_observe) == 48 && offsetof(lbm_observe, forces) == 0 && offsetof(lbm_observe, probes_out) == 8 &&

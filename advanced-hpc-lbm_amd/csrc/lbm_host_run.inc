@@ -28,7 +28,9 @@ struct SnapPlan {
 //              Forces are wanted when nb > 0 (nb, nval, as forces), probes when snap (as probes; pfirst: the first sample
 //              that many steps into the piece, 1 .. every); an observer that is not wanted gets the table of -1s
 //              (Slab::tnone: no tile counts or stores anything).  *ran tells the caller whether the tiles ran the piece
-//              (false with LBM_OK: nothing stepped, nothing of the piece's output is valid).
+//              (false with LBM_OK: nothing stepped, nothing of the piece's output is valid).  win_table
+//              (lbm_run_window_stats): the probes are a window's cells -- the piece is fed the slabs' window tables
+//              (window_tables) where it would be fed the probe set's, which stays untouched.
 // nb > 0 on every path: nb bodies; the run's forces are nval = 2 nb nsteps doubles at sums + nsteps + 1 of every slab (behind
 // the per-step sums and the spare word of the register tiles' "somebody gave up"), reduced and fetched with them.
 // no_tiles: the register tiles are not tried (the flavour is then read by nobody).
@@ -38,7 +40,7 @@ struct RunKind {
   const SnapPlan* snap = nullptr;
   int nb = 0;
   long nval = 0;
-  bool piece_mid = false, no_tiles = false;
+  bool piece_mid = false, no_tiles = false, win_table = false;
   int pfirst = 0;
   bool* ran = nullptr;
   // what the run wants from its groups of K steps inside lbm_wave launches (lbm_wave_pick.h; a lattice alone that wave_admit said
@@ -417,7 +419,7 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
     case RegFlavour::piece:
       flavour |= lbm::kRegForce | lbm::kRegProbe; shm_run = (unsigned)lbm::regtile_lds_bytes_force_probe(t.nw, t.r);
       if (fk) counted = &Slab::tforces;
-      if (k.snap) sampled = &Slab::tprobes;
+      if (k.snap) sampled = k.win_table ? &Slab::twindow : &Slab::tprobes;
       break;
   }
   auto kernel = [&](int fl) {

@@ -1298,6 +1298,54 @@ __global__ __launch_bounds__(kBlock) void lbm_derive_window(const float* lat, lo
   *reinterpret_cast<f4a*>(out4 + 4 * t) = v;
 }
 
+// lbm_run_window_stats on every engine but lbm_wave's window-stats flavour and the register tiles: lbm_derive_window's
+// addressing with lbm_stats_add's arithmetic -- behind each piece of `every` steps one thread per window cell of the slab
+// takes derive_cell of its cell from the stored lattice and adds the four fields to acc8[t][0..3], their products
+// (stats_products) to acc8[t][4..7]; acc8 = the sums of the slab's window rows, float[nrows][wnx][8], zeroed before the run.
+__global__ __launch_bounds__(kBlock) void lbm_window_stats_add(const float* lat, long plane, int pitch, int x0, int sx, int wnx,
+                                                               int yl0, int sy, long ncell, const uint8_t* blocked, float density,
+                                                               float* acc8) {
+#pragma clang fp contract(off)
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ncell) return;
+  const long r = t / wnx; const int cc = (int)(t - r * wnx);
+  const long o = ((long)yl0 + r * sy) * pitch + ((long)x0 + (long)cc * sx);
+  float f[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
+  float rho;
+  const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
+  const f4a q = stats_products(v, density);
+  f4a* at = reinterpret_cast<f4a*>(acc8 + 8 * t);
+  f4a s = at[0];
+  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+  at[0] = s;
+  f4a u = at[1];
+  u.x = u.x + q.x; u.y = u.y + q.y; u.z = u.z + q.z; u.w = u.w + q.w;
+  at[1] = u;
+}
+
+// lbm_run_window_stats on the register tiles: behind a piece that stored its nsamples samples of the slab's window rows
+// into stage4 = float[nsamples][ncell][4] (the probe tables' layout: a cell's place among the slab's window rows), one thread
+// per window cell adds them, in step order, into the cell's record of acc8 = float[ncell][8] -- lbm_stats_add's adds, one
+// rounding each, through stats_products; the record is loaded once and stored once per piece.
+__global__ __launch_bounds__(kBlock) void lbm_window_stats_fold(const float* stage4, long ncell, int nsamples, float density,
+                                                                float* acc8) {
+#pragma clang fp contract(off)
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ncell) return;
+  f4a* at = reinterpret_cast<f4a*>(acc8 + 8 * t);
+  f4a s = at[0], u = at[1];
+  for (int j = 0; j < nsamples; ++j) {
+    const f4a v = *reinterpret_cast<const f4a*>(stage4 + 4 * ((long)j * ncell + t));
+    const f4a q = stats_products(v, density);
+    s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+    u.x = u.x + q.x; u.y = u.y + q.y; u.z = u.z + q.z; u.w = u.w + q.w;
+  }
+  at[0] = s;
+  at[1] = u;
+}
+
 __global__ __launch_bounds__(kBlock) void lbm_fold_double(const double* in, int count, double* out) {
   __shared__ double red_d[kBlock / 64];
   double s = 0.0;

@@ -87,6 +87,7 @@ struct WaveArgs {
   long fstride;                // floats between consecutive samples' outputs (snapshots: one field; sums: 0)
   int fadd;                    // 0: stored (snapshots); 1: added to what is there (the sums of lbm_run_mean)
                                // (the stats flavour, STATS: fmask as above, fout the run's ONE array of sums, [ny][nx][8]; fstride, fadd unread)
+                               // (STATS beside WINDOW: fout the run's ONE array of sums over the window, [win.ny][win.nx][8])
   // ---- the window flavour (WINDOW; a lattice alone, lbm_run_window): fmask, fout and fstride as above, but a sample's
   // output is the window, [win.ny][win.nx][4], and only the window's cells are derived and stored (appended: every earlier
   // member keeps its offset)
@@ -156,6 +157,13 @@ constexpr int wave_min_occupancy(int K, int C = 1) { return C == 2 ? 2 : (K <= 6
 // (stats_products: u_x^2, u_y^2, u_x u_y, (p - p0)^2) to the last four -- lbm_stats_add's arithmetic.  The first half's
 // load, adds and store come before the second half's: four sums are live at a time, not eight.  The record index is 64-bit
 // (2^28 cells pass 2^31 floats).  The existing FIELD kernels are not touched: no third fadd value.
+// WINDOW and STATS together (lbm_run_window_stats where lbm_wave runs; a lattice alone, the one product of the two): WINDOW's
+// levels, row test (wave-uniform) and per-cell column test from WaveWin -- no map, no division -- and then, for a window cell
+// (c, r), what STATS does for a lattice cell, into the record at 8 * ((long)r * win.nx + c) of the run's one array of sums,
+// [win.ny][win.nx][8]: load four sums, add, store, then stats_products and the second four; plain same-thread accesses,
+// contraction off, the index 64-bit.  The step order holds for FIELD's reason above: one lane of one wave owns a lattice
+// cell at every level of a pass, a window cell is one lattice cell, and passes follow each other on one stream.  fstride
+// and fadd are unread.  The WINDOW kernels and the STATS kernels are not touched.
 // DRIVEN (lbm_run_driven where lbm_wave runs; a lattice alone, a flavour of its own): level l takes its accelerate constants from
 // the pass's K pairs in the kernel's arguments (scalar registers, the level is a compile-time constant of the unrolled loop)
 // where every other flavour takes a1, a2; both images of the accelerate row that a chunk's fill rows may pass within a level
@@ -179,7 +187,8 @@ void lbm_wave(const WaveArgs a) {
   static_assert(!(WINDOW && (SLAB || FORCE || PROBE || FIELD)), "the window flavour is for a lattice alone, and a flavour of its own");
   static_assert(!(DRIVEN && (SLAB || FORCE != PROBE || FIELD || WINDOW)), "the driven flavour is for a lattice alone: alone, or with forces and probes");
   static_assert(!DRIVEN || K <= 8, "K pairs of constants in the arguments");
-  static_assert(!(STATS && (SLAB || FORCE || PROBE || FIELD || WINDOW || DRIVEN)), "the stats flavour is for a lattice alone, and a flavour of its own");
+  // (STATS beside WINDOW is the one product there: the window-stats flavour, lbm_run_window_stats)
+  static_assert(!(STATS && (SLAB || FORCE || PROBE || FIELD || DRIVEN)), "the stats flavour is for a lattice alone: alone, or with the window");
   using fC = std::conditional_t<C == 1, float, f2a>;     // a lane's columns of one plane and row: one aligned access
   __shared__ double red_d[kWaveBlock / 64];
   __shared__ float red_f[kWaveBlock / 64][K];
@@ -386,6 +395,35 @@ void lbm_wave(const WaveArgs a) {
         }
       }
     };
+    // WINDOW and STATS, at a sample level behind collide_cell(s): the window's cells of the level's row into their records of the sums
+    [[maybe_unused]] auto store_window_stats = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
+      if (own_row && ((a.fmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
+        const unsigned ry = (unsigned)(S0 + j - l - a.win.y0);  // (a row below the window wraps past ylast)
+        if (ry <= a.win.ylast) {                                // (wave-uniform, as is the rest of the row test)
+          const unsigned r = a.win.sy == 1u ? ry : __umulhi(ry, a.win.my);
+          if (r * a.win.sy == ry && out_ok) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+              const unsigned cx = (unsigned)(X0 - K + C * lane + c - a.win.x0);
+              const unsigned q = a.win.sx == 1u ? cx : __umulhi(cx, a.win.mx);
+              if (cx <= a.win.xlast && q * a.win.sx == cx) {
+                float rho;
+                const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
+                f4a* at = reinterpret_cast<f4a*>(a.fout + 8 * ((long)r * a.win.nx + (long)q));
+                f4a s = at[0];                   // (one rounding per add, the order of the steps; plain same-thread accesses)
+                s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+                at[0] = s;
+                const f4a pr = stats_products(v, a.density);
+                f4a t = at[1];
+                t.x = t.x + pr.x; t.y = t.y + pr.y; t.z = t.z + pr.z; t.w = t.w + pr.w;
+                at[1] = t;
+              }
+            }
+          }
+        }
+      }
+    };
     float nxt[C][9]; unsigned nblk;
     load_row(nxt, nblk);
     // One iteration.  STEADY: past the 2K fill iterations of the chunk every level has its history, the "is this level
@@ -446,8 +484,9 @@ void lbm_wave(const WaveArgs a) {
             const float sp = collide_cell<FAST>(p[0], blk, a.omega);
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
-            if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
-            if constexpr (STATS) store_stats(l, j, p, own_row, out_ok);
+            if constexpr (WINDOW && !STATS) store_window(l, j, p, own_row, out_ok);
+            if constexpr (STATS && !WINDOW) store_stats(l, j, p, own_row, out_ok);
+            if constexpr (WINDOW && STATS) store_window_stats(l, j, p, own_row, out_ok);
             if (acc) accelerate_cell(p[0], blk, la1, la2);
             sum[l - 1] += (out_ok && own_row) ? sp : 0.f;
           } else {
@@ -458,8 +497,9 @@ void lbm_wave(const WaveArgs a) {
             collide_cells<FAST, C>(p, blk, a.omega, sp);      // the lane's cells statement by statement: independent chains
             if constexpr (PROBE) store_probes(l, j, p, own_row, out_ok);
             if constexpr (FIELD) store_fields(l, j, p, own_row, out_ok);
-            if constexpr (WINDOW) store_window(l, j, p, own_row, out_ok);
-            if constexpr (STATS) store_stats(l, j, p, own_row, out_ok);
+            if constexpr (WINDOW && !STATS) store_window(l, j, p, own_row, out_ok);
+            if constexpr (STATS && !WINDOW) store_stats(l, j, p, own_row, out_ok);
+            if constexpr (WINDOW && STATS) store_window_stats(l, j, p, own_row, out_ok);
 #pragma unroll
             for (int c = 0; c < C; ++c)
               if (acc) accelerate_cell(p[c], blk[c], la1, la2);

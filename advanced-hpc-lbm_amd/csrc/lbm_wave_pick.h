@@ -5,7 +5,7 @@
 #include <cstddef>
 
 // The flavours lbm_wave is instantiated in beyond SLAB (lbm_host_march.inc, wave_kernel, names each one's template flags).
-enum class WaveFlavour { plain, force, probe, force_probe, field, window, driven, driven_observed, stats };
+enum class WaveFlavour { plain, force, probe, force_probe, field, window, driven, driven_observed, stats, window_stats };
 
 // The obstacle bytes a launch reads: the slab's own, or with the counted cells (fmap), the probes' cells (pmap) or both
 // (fpmap) marked on them (Slab; wave_force_ready and wave_probe_ready build them).
@@ -22,7 +22,7 @@ struct WavePick {
 // counted (fcells_n > 0) -- with none the kernel that counts nothing runs and the fold writes the zeros.  probes / fields: the
 // run wants them; psample / fsample: this group of K steps holds a sample step of theirs (read only beside its want);
 // window: the fields are a window's (read only beside fields); stats: the fields are the eight sums of lbm_run_stats (read
-// only beside fields, never beside window).
+// only beside fields; beside window: the eight sums over the window's cells, lbm_run_window_stats).
 //   - fields are a flavour of their own: refused beside forces or probes, and under a schedule;
 //   - under a schedule with an observer EVERY group runs driven_observed, a sample step in it or not, on the map that marks
 //     what is wanted (an observer that is not wanted: nothing marked); under a schedule alone, driven;
@@ -38,7 +38,7 @@ inline WavePick wave_pick(bool schedule, bool bodies, bool counted, bool probes,
     p.map = probes ? (f ? WaveMap::fpmap : WaveMap::pmap) : (f ? WaveMap::fmap : WaveMap::blocked);
     p.forces = f;
   } else if (schedule) p.flavour = WaveFlavour::driven;
-  else if (fields && fsample) p.flavour = window ? WaveFlavour::window : stats ? WaveFlavour::stats : WaveFlavour::field;
+  else if (fields && fsample) p.flavour = window ? (stats ? WaveFlavour::window_stats : WaveFlavour::window) : stats ? WaveFlavour::stats : WaveFlavour::field;
   else if (probes && psample) {
     p.flavour = f ? WaveFlavour::force_probe : WaveFlavour::probe;
     p.map = f ? WaveMap::fpmap : WaveMap::pmap;
@@ -58,8 +58,10 @@ inline WavePick wave_pick(bool schedule, bool bodies, bool counted, bool probes,
 //     next; fadd: the samples are added into ONE field (fstride = 0), the sums of a mean; win: fout and fstride are of windows
 //     and the groups run the window flavour (win->wave).  Behind a left-over step that is a sample step: lbm_derive into the
 //     slot (its sums go to fpart / fmass, one float / double per block, unused), lbm_mean_add into the sums, or
-//     lbm_derive_window into the slot.  fstats (lbm_run_stats; beside fadd, never beside win): the ONE field is the run's
+//     lbm_derive_window into the slot.  fstats (lbm_run_stats; beside fadd): the ONE field is the run's
 //     sums of eight floats per cell, [ny][nx][8]; the groups run the stats flavour, lbm_stats_add behind a left-over step.
+//     fstats beside win (lbm_run_window_stats; fadd, fstride = 0): the ONE field is the sums over the window's cells,
+//     [win.ny][win.nx][8]; the groups run the window-stats flavour, lbm_window_stats_add behind a left-over step.
 struct WaveWants {
   float* pout = nullptr;
   int pevery = 0;

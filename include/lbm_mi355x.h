@@ -238,7 +238,8 @@ int lbm_run_mean(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* mea
  *   bits.
  * Not offered: sums inside the register tiles (their mean flavour keeps three sums per cell in LDS; seven would want about
  * 112 KB of a CU's 160 KB at 4096 cells per tile, beside the mailboxes: unverified); stats inside lbm_run_observed, whose
- * struct is frozen; stats under a schedule; stats over a window; higher moments; the command-line tool.
+ * struct is frozen; stats under a schedule; higher moments; the command-line tool.  (Stats over a window are a call of
+ * their own: lbm_run_window_stats.)
  */
 int lbm_run_stats(lbm_ctx* ctx, int nsteps, float* av_vels, int every, float* stats_out);
 
@@ -411,13 +412,57 @@ typedef struct { int x0, y0, nx, ny, sx, sy; } lbm_window;
    every < 0; window_out NULL with m > 0; a device pointer on another device than the slabs'; m x window floats past the
    address space.  LBM_ENOMEM likewise when a staging or table does not fit and no path with the same bits is left.
    Rank contexts agree on room and on the path before anything is queued.
-   Not offered: windows inside lbm_run_observed (its struct layout is frozen), means over a window, block-averaged
-   downsampling, windows that wrap, windows from the command-line tool. */
+   Not offered: windows inside lbm_run_observed (its struct layout is frozen), block-averaged downsampling, windows that
+   wrap, windows from the command-line tool.  (Means and second moments over a window: lbm_run_window_stats.) */
 int lbm_run_window(lbm_ctx* ctx, int nsteps, float* av_vels, int every, const lbm_window* win, float* window_out);
 /* Host arithmetic only (no device needed, as lbm_plan_tiles): validates win against an nx x ny lattice (LBM_EINVAL: not a
    legal window, or row_begin > row_end) and returns which window rows lie in lattice rows [row_begin, row_end): rows
    *first .. *first + *count - 1 of the window (*count may be 0; first and count may be NULL). */
 int lbm_window_rows(const lbm_window* win, int nx, int ny, int row_begin, int row_end, int* first, int* count);
+
+/*
+ * lbm_run_stats over a window: the means and second moments of the window's cells, with device memory, traffic and host
+ * copy that scale with the window, not with the lattice (Reynolds stresses in the wake behind a body without paying for
+ * the whole channel).  stats_out: float[win->ny][win->nx][8], host memory, or device memory of the device that holds every
+ * slab; the rules are those of lbm_run_window (the window, global in every mode; rank contexts) and of lbm_run_stats.
+ * Definition, bit for bit: let W_j[r][c] be sample j of lbm_run_window(ctx, nsteps, av_vels, every, win, ...) from the same
+ * state with the same options, m = nsteps / every, and p0 = density * (1.f / 3.f).  Then stats_out[r][c][0..7] is what
+ * lbm_run_stats defines from X_j = W_j[r][c]: S_j = S_(j-1) + X_j and T_j = T_(j-1) + Q_j with
+ * Q_j = (x * x, y * y, x * y, (w - p0) * (w - p0)), float arithmetic with one rounding per operation, no fma, in step order,
+ * starting from +0.0f; each sum divided by (float)m, correctly rounded.  So stats_out[r][c][:] equals lbm_run_stats'
+ * stats_out[win->y0 + r win->sy][win->x0 + c win->sx][:], and a blocked cell reads as it does there.
+ * av_vels, the lattice and everything after the call are bit-identical to lbm_run(ctx, nsteps, av_vels) wherever the
+ * register tiles or lbm_wave ran the steps; on the split path they are equal within rounding of the per-step sum.
+ * Rank contexts: as lbm_run_window -- every rank's array has the full window shape, a rank fills the window rows that lie
+ * in its own lattice rows and writes +0.0f to the others; no communication is added.
+ * Device memory for the sums: 32 bytes per window cell of a slab, never per lattice cell.
+ * LBM_EINVAL with nothing queued and the lattice untouched: NULL ctx, win or stats_out; a window outside lbm_window's
+ * rules; nsteps < 0; every <= 0; m = 0; a device pointer on another device than the slabs'.  LBM_ENOMEM likewise when the
+ * sums do not fit -- the ranks of a rank context agree on that first; LBM_EHIP after a failed peer-to-peer wait.
+ * Which kernels take the sums (info keys reset at the start of each call):
+ * - Where lbm_wave runs (a lattice alone with time_block 4, 6 or 8 and the wave kernel, nsteps >= time_block), the sums
+ *   ride in its launches ("window_stats_in_wave" = 1): a window-stats flavour of lbm_wave tests a sample level's row and
+ *   then each of a lane's cells against the window as the window flavour does (no map, no division) and adds a window
+ *   cell's eight terms into its 32-byte record as the stats flavour does, the record index 64-bit; one kernel per pass of K
+ *   steps, a pass without a sample step runs the plain kernel; the steps left over behind the last full pass go as
+ *   lbm_run's do, with the add kernel behind those that are sample steps.  A window whose extent times its stride passes
+ *   2^32 takes the split path: the same bits, no error.
+ * - On the register tiles, alone and across slabs ("window_stats_in_kernel" = 1), the call runs in pieces of c every steps:
+ *   each piece is one launch of the flavour lbm_run_observed's pieces run in, fed the window's tables as its probe tables
+ *   (the probe set of lbm_set_probes and its table stay untouched); it stores its c samples of the slab's window rows
+ *   into a device staging, and a fold kernel behind it adds them, in step order, into the sums.  That flavour folds a cut
+ *   piece's last step sum as a whole run folds it, so av_vels is lbm_run's bits wherever the call is cut.  c is the option
+ *   "window_stats_chunk", or automatic (0): as many samples as 64 MiB of staging per slab hold, at least 1, at most m.
+ *   The steps past m every run as one more piece without samples.  A piece that gives up has stepped nothing; the call
+ *   continues from the same step on the split path.
+ * - Everywhere else -- lbm_march, slabs or ranks off the tiles, runs shorter than time_block, a lattice that does not tile
+ *   -- the steps run in pieces of `every` with an add kernel behind each on every slab that holds a window row: one thread
+ *   per window cell of the slab.  The same adds in the same order, the same bits; both keys read 0.
+ * "window_stats_pieces": the step-loop pieces of the last call (1 where lbm_wave took it).
+ * Not offered: window stats inside lbm_run_observed (its struct layout is frozen); window stats under a schedule; windows
+ * that wrap; block averaging (points are sampled); the command-line tool.
+ */
+int lbm_run_window_stats(lbm_ctx* ctx, int nsteps, float* av_vels, int every, const lbm_window* win, float* stats_out);
 
 /*
  * The acceleration as an input of the run (a ramp over the first thousand steps instead of an impulsive start, a pulsatile
@@ -615,7 +660,8 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
 /* Tuning / introspection (never needed for correctness; the table of keys is INTEGRATION.md section 3).
  * Options: "engine" (0 auto, 1 streaming kernels, 3 register tiles -- alone or across slabs -- or fail), "time_block"
  * (1, 2, 4, 6, 8 steps per pass), "march_kernel", "march_rows", "wave_rows", "wave_cols" (1, 2), "regtile" (tiling),
- * "regtile_async" (0, 1), "regtile_tag" (test hook: the next mailbox tag), "kernel_variant" (bits: 1 fast rcp / sqrt, 2 / 4 nontemporal stores / loads, 8 the reference's
+ * "regtile_async" (0, 1), "regtile_tag" (test hook: the next mailbox tag), "window_stats_chunk" (the most sample steps one
+ * register-tile piece of lbm_run_window_stats holds; 0 automatic; below 0: LBM_EINVAL), "kernel_variant" (bits: 1 fast rcp / sqrt, 2 / 4 nontemporal stores / loads, 8 the reference's
  * form of the speed sum, d2q9-bgk.c:1783-1811, 256 one-step kernel only), "vector_width", "t2_threads".
  * Info: "engine_last", "engine_next", "samples_in_kernel" (1: the last lbm_run_sampled's snapshots came from the register
  * tiles), "forces_in_kernel" (1: the last lbm_run_forces took its sums inside the register tiles),
@@ -628,7 +674,10 @@ int lbm_plan_tiles(int nx, int rows, int slabs_per_device, int compute_units, in
  * "probes_in_kernel" (1: the last lbm_run_probes took its values inside the register tiles),
  * "probes_in_wave" (1: the last lbm_run_probes took its values inside lbm_wave launches),
  * "window_in_kernel" (1: the last lbm_run_window took its window inside the register tiles),
- * "window_in_wave" (1: the last lbm_run_window took its window inside lbm_wave launches), "observed_in_kernel",
+ * "window_in_wave" (1: the last lbm_run_window took its window inside lbm_wave launches),
+ * "window_stats_in_wave" (1: the last lbm_run_window_stats took its sums inside lbm_wave launches),
+ * "window_stats_in_kernel" (1: ... its samples inside the register tiles), "window_stats_pieces" (... the step-loop
+ * pieces it ran), "window_stats_chunk" (the option's value), "observed_in_kernel",
  * "observed_in_wave", "observed_pieces" (lbm_run_observed), "accel" (the context's acceleration: lbm_create's, or the last lbm_set_accel's),
  * "driven_in_kernel" (1: the last lbm_run_driven ran inside the register tiles), "driven_in_wave" (1: the last lbm_run_driven
  * ran its groups of K steps inside lbm_wave launches), "driven_observed_in_kernel", "driven_observed_in_wave",
