@@ -720,15 +720,19 @@ int launch_window_stats_add(const lbm_ctx* c, Slab& s, const lbm_window& w, int 
 
 // The window table of a slab for tiles of ty rows, fed to the probe flavour as the probe set's is: a cell's word is its place
 // among the SLAB's window rows + 1, (r - first) w.nx + c + 1 -- the slab's output pointer is its first window row's.  Kept by
-// (window, tiling); the probe set's table is not touched.  LBM_ENOMEM: nothing queued.
+// (window, tiling); the probe set's table is not touched.  LBM_ENOMEM: nothing queued.  The key names a window only once its
+// table stands: tile_table_set can return before it has touched the old table (its hipSetDevice), which would otherwise be
+// left under the new window's key and the old tiling -- a hit for the next call with this window.
 int window_tables(Slab& s, int ty, int ntx, const lbm_window& w, int first, int count) {
   if (s.twindow.ty == ty && memcmp(&s.wkey, &w, sizeof(w)) == 0) return LBM_OK;
   std::vector<TileCell> cells;
   for (int r = 0; r < count; ++r)
     for (int cc = 0; cc < w.nx; ++cc)
       cells.push_back({(int)((long)w.x0 + (long)cc * w.sx), (int)((long)w.y0 + (long)(first + r) * w.sy - s.row0), (uint32_t)((long)r * w.nx + cc) + 1u});
+  const int rc = tile_table_set(s, s.twindow, ty, ntx, cells, "window");
+  if (rc) return rc;
   s.wkey = w;
-  return tile_table_set(s, s.twindow, ty, ntx, cells, "window");
+  return LBM_OK;
 }
 
 // Where one call's windows go, [m][w.ny][w.nx][4] floats.  Device output is written in place; host output goes through one

@@ -75,6 +75,23 @@ def pieces_of(n, *everys):
     return len(cuts)
 
 
+def window_stats_pieces_of(n, every, chunk, kind, cells=0):
+    """The step-loop pieces of lbm_run_window_stats over n steps, restated from lbm_host_observe.inc.  kind "tiles": pieces of
+    c sample steps, c = min(chunk, m) or, at chunk 0, as many samples as 64 MiB of staging hold of the `cells` window cells
+    of the slab with the most (16 bytes a cell and sample; at least 1, at most m), and one piece more for the steps behind
+    the last sample step; "wave": the one run; "split": a piece per sample step, and the tail."""
+    m = n // every
+    assert m >= 1 and chunk >= 0
+    tail = 1 if n > m * every else 0
+    if kind == "wave":
+        return 1
+    if kind == "split":
+        return m + tail
+    assert kind == "tiles"
+    c = min(chunk, m) if chunk > 0 else min(m, max(1, (64 << 20) // (16 * cells))) if cells else m
+    return -(-m // c) + tail
+
+
 def want_for(n, forces=True, pe=PE, me=ME, fe=FE):
     """run_driven_observed's keyword arguments for a run of n steps: a mean whose first sample step lies beyond n is a
     refusal, so a run that short asks for none (snapshots beyond n are legal and write nothing)."""

@@ -4,6 +4,9 @@ check without a GPU, one GPU runner).
 
 New table entries: set_map(name, refill), write(name), refused_live(what).  lbm_run_stats is the tenth kind of running call
 (TEN): on every path family it is the first call behind a map change under either refill, and behind a write.
+lbm_run_window_stats is the eleventh (ELEVEN), in four programs of its own: likewise the first call behind either refill on every
+path family and behind a write, and twice over one window either side of a LBM_REFILL_REST that turns cells of the window both
+ways -- lbm_window_stats_add and the tiles read the live blocked bytes while the window table's key still hits.
 
 The shadow never takes a live input.  It stays the one-step kernel (engine 1, time_block 1, a lattice alone; a slab context
 where slabs add up forces off the tiles, as in the older file), and at every live input it is DESTROYED AND CREATED AGAIN by
@@ -53,12 +56,13 @@ from test_driven_run import AV_RTOL, driven_oracle
 from test_live_inputs import KEEP, LBM_EINVAL, REST, refilled, rest_values, s_prime
 from test_observer_sequences import (B3, B5, B9, FP, F, InChunks, M, ObserverModel, P, S, Shadow, _call, _chains, _check_engine,
                                      _is, _probe_sets, _refuse, _same, _schedule, driven, driven_observed, hold_anchor, mean, observed,
-                                     probe_set, probes, refused, stats, window)
+                                     probe_set, probes, refused, stats, window, window_stats)
 from test_stats_run import p0_of, stats_of
 from test_window_run import cut
 
 NINE = ("run", "sampled", "forces", "probes", "mean", "observed", "window", "driven", "driven_observed")
 TEN = NINE + ("stats",)
+ELEVEN = TEN + ("window_stats",)
 INT_MIN = -2 ** 31
 PATTERNS = ((0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0))      # (A, B, C) in the six stamped cells
 WAVE_ROWS = 24
@@ -85,7 +89,8 @@ def _kind_call(kind, path, K, i):
     return {"run": run(n, path), "sampled": sampled(n, ev, path), "forces": forces(n, path), "probes": probes(n, 2, path),
             "mean": mean(n, ev, path), "observed": observed(n, (F, P, M), 2, ev, 0, path), "window": window(n, ev, "live", path),
             "driven": driven(n, SCHEDS[i % 3], path),
-            "driven_observed": driven_observed(n, SCHEDS[(i + 1) % 3], FP, 2, 0, 0, path), "stats": stats(n, ev, path)}[kind]
+            "driven_observed": driven_observed(n, SCHEDS[(i + 1) % 3], FP, 2, 0, 0, path), "stats": stats(n, ev, path),
+            "window_stats": window_stats(n, ev, "live", path)}[kind]
 
 
 def _relabel():
@@ -247,6 +252,24 @@ PROGRAMS = {
         run(5, "tb2"), set_map("B", REST), refused("forces", 3), bodies("U", 3), forces(5, "tb2"),
         write("W"), mean(6, 3, "tb2"), set_map("A", KEEP), bodies("U", 3), observed(8, (F, P, M), 2, 4, 0, "tb2"), probes(6, 3, "tb2"),
     ]),
+    # lbm_run_window_stats, the eleventh kind (ELEVEN), in programs of its own (the older programs and their indices stay): the
+    # first call behind a map change under either refill on every path family, and behind a write off the lone tiles; the second
+    # call of each pair runs the SAME window behind a LBM_REFILL_REST that turns cells of it from fluid to blocked and others from
+    # blocked to fluid (the stamps), so on the tiles the window table's key hits while the blocked bytes the kernels read changed
+    "window_stats_tiles_128_behind_maps": (_l1s, None, _START + [
+        run(5, "tiles"), set_map("B", KEEP), window_stats(7, 3, "live", "tiles", 1), set_map("C", REST), window_stats(7, 3, "live", "tiles"),
+    ]),
+    "window_stats_wave6_130x37_behind_maps": (_l4, None, [opt("time_block", 6), opt("wave_rows", WAVE_ROWS)] + _START + [
+        run(13, "wave"), set_map("B", KEEP), _kind_call("window_stats", "wave", 6, 0), set_map("C", REST), _kind_call("window_stats", "wave", 6, 0),
+    ]),
+    "window_stats_split_130x37_behind_maps_and_a_write": (_l4, None, [opt("time_block", 1)] + _START + [
+        run(5, "tb1"), set_map("B", KEEP), _kind_call("window_stats", "tb1", 1, 0), set_map("C", REST), _kind_call("window_stats", "tb1", 1, 0),
+        write("W"), window_stats(5, 2, "live", "tb1"), opt("time_block", 2), set_map("A", REST), window_stats(5, 2, "live", "tb2"),
+    ]),
+    "window_stats_slabs_p2p_behind_maps_and_a_write": (_l6, ("slabs", 4, "p2p"), _START + [
+        run(5, "slab-tiles"), set_map("B", KEEP), window_stats(7, 3, "live", "slab-tiles", 2), set_map("C", REST),
+        window_stats(7, 3, "live", "slab-tiles"), write("W"), window_stats(6, 2, "live", "slab-tiles", 1),
+    ]),
 }
 LIVE = ("set_map", "write", "refused_live")
 FAMILY = {"tiles": "tiles", "slab-tiles": "slab-tiles", "wave": "wave", "tb1": "split", "tb2": "split", "march": "split"}
@@ -333,8 +356,8 @@ def found(L, programs):
                 fam, lives = FAMILY[e["path"]], [b for b in e["behind"] if b["op"] != "refused_live"]
                 if lives:
                     out.add(f"{fam}: {e['op']} first behind a {lives[-1]['op']}")
-                    if e["op"] == "stats" and lives[-1]["op"] == "set_map":
-                        out.add(f"{fam}: stats first behind a set_map {'REST' if lives[-1]['refill'] == REST else 'KEEP'}")
+                    if e["op"] in ("stats", "window_stats") and lives[-1]["op"] == "set_map":
+                        out.add(f"{fam}: {e['op']} first behind a set_map {'REST' if lives[-1]['refill'] == REST else 'KEEP'}")
                     out.add(f"{fam}: a live input behind an {'odd' if e['steps0'] % 2 else 'even'} step count")
                     before = lives[0]["before"]
                     if before and before["path"] in ("wave", "march") and before["pieces"][-1] % before["tb"]:
@@ -348,6 +371,9 @@ def found(L, programs):
         for a, s, b in _chains(t, [_is("window"), _is("set_map"), _is("window")], _not_live_or_set):
             if a["wkey"] == b["wkey"] and a["path"] == b["path"] and _both_ways(case, s["old"], s["new"], _window_cells(case, a["win"])):
                 out.add(f"{FAMILY[a['path']]}: the same window either side of a set_map, cells turning both ways")
+        for a, s, b in _chains(t, [_is("window_stats"), _is("set_map", refill=REST), _is("window_stats")], lambda e: False):
+            if a["wkey"] == b["wkey"] and a["path"] == b["path"] and a["ty"] == b["ty"] and _both_ways(case, s["old"], s["new"], _window_cells(case, a["win"])):
+                out.add(f"{FAMILY[a['path']]}: window_stats over one window either side of a set_map REST, cells turning both ways")
         for a, s, b in _chains(t, [_is("probes"), _is("set_map"), _is("probes")], _not_live_or_set):
             if a["pset"] == b["pset"] and a["path"] == b["path"] and _both_ways(case, s["old"], s["new"], (xy[:, 1], xy[:, 0])):
                 out.add(f"{FAMILY[a['path']]}: the same probe set either side of a set_map, cells turning both ways")
@@ -382,6 +408,10 @@ DECLARED = (
     + [f"{fam}: {kind} first behind a write" for fam in ("tiles", "wave") for kind in TEN]
     + [f"{fam}: stats first behind a set_map {r}" for fam in ("tiles", "slab-tiles", "wave", "split") for r in ("KEEP", "REST")]
     + [f"{fam}: stats first behind a write" for fam in ("slab-tiles", "split")]
+    + [f"{fam}: window_stats first behind a set_map" for fam in ("tiles", "slab-tiles", "wave", "split")]
+    + [f"{fam}: window_stats first behind a set_map {r}" for fam in ("tiles", "slab-tiles", "wave", "split") for r in ("KEEP", "REST")]
+    + [f"{fam}: window_stats first behind a write" for fam in ("slab-tiles", "split")]
+    + [f"{fam}: window_stats over one window either side of a set_map REST, cells turning both ways" for fam in ("tiles", "slab-tiles", "wave", "split")]
     + [f"lone: {a} -> {b} across a map call, onto a map it never ran with" for a, b in (("tiles", "wave"), ("wave", "march"), ("march", "tiles"), ("tiles", "tb2"))]
     + [f"slabs copy: {a} -> {b} across a map call, onto a map it never ran with" for a, b in (("tb2", "march"), ("march", "slab-tiles"))]
     + [f"{fam}: the same {what} either side of a set_map, cells turning both ways" for fam in ("tiles", "slab-tiles", "wave") for what in ("window", "probe set")]
@@ -467,17 +497,25 @@ def test_the_maps_are_what_they_say(L):
                                   # stats: the map call in front of it (REST, KEEP), the write in front of it, the call itself
                                   ("tiles_128_every_kind_behind_a_map", 27), ("wave6_130x37_every_kind_behind_a_map", 31),
                                   ("tiles_128_writes_and_pairs", 23), ("slabs_p2p_tiles_every_kind_behind_a_map", 28),
-                                  ("never_tiles_tb1_tb2", 30), ("never_tiles_tb1_tb2", -1)])
+                                  ("never_tiles_tb1_tb2", 30), ("never_tiles_tb1_tb2", -1),
+                                  # window_stats: the KEEP and the REST map call in front of it (the REST one lies between two
+                                  # calls over one window), the write in front of it, the call itself, a program
+                                  ("window_stats_tiles_128_behind_maps", 3), ("window_stats_tiles_128_behind_maps", 5),
+                                  ("window_stats_wave6_130x37_behind_maps", 5), ("window_stats_wave6_130x37_behind_maps", 7),
+                                  ("window_stats_split_130x37_behind_maps_and_a_write", 4), ("window_stats_split_130x37_behind_maps_and_a_write", 8),
+                                  ("window_stats_slabs_p2p_behind_maps_and_a_write", 5), ("window_stats_slabs_p2p_behind_maps_and_a_write", 7),
+                                  ("window_stats_slabs_p2p_behind_maps_and_a_write", 6), ("window_stats_slabs_p2p_behind_maps_and_a_write", None)])
 def test_a_trimmed_table_fails_the_coverage_check(L, drop):
     """Without one live input (the map call in front of a kind, a write, one of a pair, the map call between two engines or
-    between two runs of one window), one stats call or one program (a context) the table no longer covers the declared list."""
+    between two runs of one window), one stats or window_stats call or one program (a context) the table no longer covers the
+    declared list."""
     name, index = drop
     programs = dict(PROGRAMS)
     if index is None:
         del programs[name]
     else:
         setup, ctx, calls = programs[name]
-        assert calls[index][0] in LIVE or calls[index][0] == "stats", calls[index]
+        assert calls[index][0] in LIVE or calls[index][0] in ("stats", "window_stats"), calls[index]
         programs[name] = (setup, ctx, calls[:index] + calls[index + 1:] if index != -1 else calls[:-1])
     assert missing(L, programs)
 
@@ -563,7 +601,7 @@ def test_live_sequence(gpu, O, oracle, monkeypatch, name):
                 else:
                     n, kinds, tiles = e["n"], e["kinds"], e["fam"] == "tiles"
                     acc = _schedule(e["sched"], p, e["accel"], n)
-                    want_fields = any(k in kinds for k in (P, M, S, "window", "stats"))
+                    want_fields = any(k in kinds for k in (P, M, S, "window", "stats", "window_stats"))
                     if kind == "run":
                         av_sh, F_sh, X, numpy_forces = sh.run(n), None, None, None
                     else:
@@ -576,10 +614,12 @@ def test_live_sequence(gpu, O, oracle, monkeypatch, name):
                         exp[M] = mean_from_fields(X, e["me"])
                     if S in kinds:
                         exp[S] = X[e["fe"] - 1::e["fe"]]
-                    if e["win"]:
+                    if "window" in kinds:
                         exp["window"] = cut(X[e["fe"] - 1::e["fe"]], case["windows"][e["win"]])
                     if "stats" in kinds:
                         exp["stats"] = stats_of(X[e["ste"] - 1::e["ste"]], p0_of(p.density))
+                    if "window_stats" in kinds:
+                        exp["window_stats"] = stats_of(cut(X[e["fe"] - 1::e["fe"]], case["windows"][e["win"]]), p0_of(p.density))
                     assert sorted(out) == sorted(kinds), (where, sorted(out))
                     for k, v in exp.items():
                         _same(out[k], v, where + (k,))

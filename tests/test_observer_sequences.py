@@ -32,7 +32,12 @@ steps of that launch.  A call the tiles run in several pieces (lbm_run_observed 
 lbm_run_driven_observed: cut at the sample steps of means and snapshots) therefore advances it by n_i + 1 per piece, and the
 wrap (a lattice alone: cleared in front of the piece that would reach TAG_WRAP) and the restart (slabs: behind the piece
 that passes SLAB_TAG_MARK) are tested per piece.  lbm_run_stats off lbm_wave is cut at every sample step, on the tiles too:
-a launch per piece there.  ObserverModel.apply restates exactly that.
+a launch per piece there.  lbm_run_window_stats (the eighth kind, window_stats(n, every, name, path, chunk)) on the tiles runs
+pieces of c every steps, c = min("window_stats_chunk", m) or automatic (the samples 64 MiB of staging hold of the slab with the
+most window cells), and one piece more for the steps behind the last sample: a launch and n_i + 1 tags per piece, so a call may
+pass a mark between two pieces; ONE run on lbm_wave; elsewhere a piece per sample step.  Its output is
+stats_of(cut(fields[every - 1::every], w), p0).  It shares the per-slab window table and its (tiling, window) key with
+lbm_run_window, and is fed that table where a probes call is fed the probe set's.  ObserverModel.apply restates exactly that.
 
 The table is checked without a GPU against a declared coverage list (path x kind, contexts, transitions, refused calls), so
 that trimming it fails on CPU."""
@@ -45,7 +50,7 @@ import pytest
 from test_body_forces import _bits, _close, forces_from_state
 from test_call_sequences import (ANCHOR_STEPS, SLAB_TAG_MARK, TAG_WRAP, TILE_PATHS, W_EQ, Model, _check_derived, _grow, _kept, _labels,
                                  _open, _p1, _p2, _p3, _p4, _p5, _p6, _p7, _p8, _p9, bodies, clear, forces, opt, run, sampled)
-from test_driven_observed import mean_from_fields, pieces_of
+from test_driven_observed import mean_from_fields, pieces_of, window_stats_pieces_of
 from test_driven_run import AV_RTOL, driven_oracle, schedules
 from test_probe_run import awkward_set
 from test_stats_run import p0_of, stats_of
@@ -54,7 +59,7 @@ from test_window_run import cut
 from make_golden import PARAM_GRID                      # noqa: E402  (test_call_sequences put tests/golden on the path)
 from make_golden import refused as guard_refuses        # noqa: E402
 
-KINDS = ("probes", "mean", "observed", "window", "driven", "driven_observed", "stats")
+KINDS = ("probes", "mean", "observed", "window", "driven", "driven_observed", "stats", "window_stats")
 RUNNING = ("run", "sampled", "forces") + KINDS
 PATHS = TILE_PATHS + ("tb1", "tb2", "march", "wave")
 X_ACCEL = 0.0123                                         # what set_accel sets in the programs
@@ -93,6 +98,11 @@ def stats(n, every, path):
     return ("stats", n, every, path)
 
 
+def window_stats(n, every, name, path, chunk=None):
+    """lbm_run_window_stats over the window `name`; chunk: "window_stats_chunk" is set to it in front of the call (and stays)."""
+    return ("window_stats", n, every, name, chunk, path)
+
+
 def set_accel(x):
     return ("set_accel", x)
 
@@ -108,7 +118,8 @@ def clear_probes():
 def refused(what, *args):
     """A call that must return LBM_EINVAL: "window" (n, every, name of a window outside the lattice), "schedule" (n, index
     of the non-finite entry, its value), "probes" (n, every), "forces" (n), "mean" (n, every > n), "observed mean"
-    (n, mean_every > n), "stats" (n, every > n)."""
+    (n, mean_every > n), "stats" (n, every > n), "window_stats window" (n, every, name of a window outside the lattice),
+    "window_stats every" (n, every > n, name of a window)."""
     return ("refused", what) + args
 
 
@@ -198,6 +209,14 @@ def _c11(L):      # 256 x 64 at the "thirds" point
     return _case(L, _p10, (2, 1), {"row": (0, 62, 256, 1)})
 
 
+def _c12(L):      # 128 x 128 deck as _c1, with a window that leaves the lattice (the programs of lbm_run_window_stats)
+    return _case(L, _p1, (2, 1), {"A": (60, 1, 8, 4), "B": (20, 65, 8, 4), "wake": (3, 2, 40, 30, 3, 4), "outside": (120, 100, 20, 5)})
+
+
+def _c13(L):      # 256 x 64 at the "thirds" point: the accelerate row and the whole lattice
+    return _case(L, _p10, (2, 1), {"row": (0, 62, 256, 1), "all": (0, 0, 256, 64)})
+
+
 B3, B5, B9 = ("b", 3), ("b", 5), ("b", 9)
 FP, FM = (F, P), (F, M)
 # ctx as in test_call_sequences: None = a lattice alone; ("slabs", n, exchange); ("rank", exchange) = a rank ring of one
@@ -277,12 +296,12 @@ PROGRAMS = {
         bodies("walls+rest", 2), probe_set("A"),
         probes(6, 2, "slab-tiles"), window(6, 3, "mail", "slab-tiles"), driven(7, B3, "slab-tiles"),
         observed(8, (F, P, M), 2, 4, 0, "slab-tiles"), driven_observed(8, B5, (P, S), 2, 0, 4, "slab-tiles"),
-        mean(6, 3, "slab-tiles"), run(3, "slab-tiles"), stats(6, 2, "slab-tiles"),
+        mean(6, 3, "slab-tiles"), run(3, "slab-tiles"), stats(6, 2, "slab-tiles"), window_stats(7, 3, "mail", "slab-tiles", 1),
     ]),
     "rank_ring_of_one_rccl": (_c8, ("rank", "rccl"), [
         opt("time_block", 2), bodies("walls+rest", 2), probe_set("A"),
         probes(6, 3, "tb2"), window(6, 3, "row", "tb2"), driven(6, B3, "tb2"), observed(8, (F, P, M), 2, 4, 0, "tb2"),
-        driven_observed(8, B5, FP, 2, 0, 0, "tb2"), mean(6, 3, "tb2"), run(3, "tb2"), stats(6, 3, "tb2"),
+        driven_observed(8, B5, FP, 2, 0, 0, "tb2"), mean(6, 3, "tb2"), run(3, "tb2"), stats(6, 3, "tb2"), window_stats(7, 3, "row", "tb2"),
     ]),
     "lone_tag_wrap_in_flavours": (_c9, None, [
         opt("regtile", 44), bodies("random4", 4), probe_set("A"), run(5, "tiles"),
@@ -348,6 +367,62 @@ PROGRAMS = {
         opt("time_block", 4), opt("march_kernel", 0), stats(9, 4, "march"),
         opt("engine", 3), stats(6, 2, "tiles"),
     ]),
+    # lbm_run_window_stats.  The window table and its key are lbm_run_window's: window(A) then stats over A (a hit), stats over
+    # A then over B then window(B) (a miss, then a hit from the other call); the probe table and the table of -1s either side
+    # of a call that is fed window tables as probe tables; the chunk option between two calls; a changed acceleration; its
+    # whole-lattice cousin on either side; refused between running calls
+    "window_stats_walk_on_tiles_128": (_c12, None, [
+        bodies("A", 4), probe_set("A"),
+        window(6, 2, "A", "tiles"), window_stats(6, 2, "A", "tiles"), window_stats(7, 3, "B", "tiles"), window(6, 3, "B", "tiles"),
+        probes(8, 2, "tiles"), window_stats(9, 2, "wake", "tiles", 2), probes(8, 2, "tiles"),
+        window_stats(9, 2, "wake", "tiles", 1),
+        set_accel(X_ACCEL), window_stats(6, 3, "A", "tiles", 0), run(3, "tiles"),
+        stats(6, 2, "tiles"), window_stats(7, 2, "wake", "tiles"), stats(6, 3, "tiles"),
+        refused("window_stats window", 6, 2, "outside"), run(4, "tiles"),
+    ]),
+    # the same window either side of a re-tiling (the key's ty), under both loops, and its pieces across the tag wrap: three
+    # pieces of 4 + 1 from TAG_WRAP - 9, the second would reach the mark
+    "window_stats_retile_and_tag_wrap_256": (_c2, None, [
+        bodies("walls+rest", 2), probe_set("A"), opt("regtile", 84),
+        window_stats(8, 4, "seam", "tiles"), opt("regtile", 162), window_stats(8, 4, "seam", "tiles"),
+        opt("regtile_async", 0), window_stats(7, 2, "seam", "tiles", 2),
+        opt("regtile_tag", TAG_WRAP - 9), window_stats(12, 4, "seam", "tiles", 1), run(4, "tiles"),
+    ]),
+    "window_stats_on_wave6_130x37": (_c4, None, [
+        opt("time_block", 6), bodies("random4", 4), probe_set("A"),
+        window(13, 4, "column", "wave"), window_stats(13, 4, "column", "wave"),
+        stats(13, 3, "wave"), window_stats(14, 6, "row", "wave"), stats(12, 1, "wave"), run(7, "wave"),
+        set_accel(X_ACCEL), window_stats(12, 1, "column", "wave"),
+        refused("window_stats every", 5, 6, "row"), window_stats(17, 7, "row", "wave"), run(7, "wave"),
+    ]),
+    "window_stats_never_tiles_tb1_tb2": (_c4, None, [
+        opt("time_block", 1), bodies("random4", 4), probe_set("A"),
+        window_stats(7, 3, "row", "tb1"), window(6, 2, "row", "tb1"), run(5, "tb1"),
+        opt("time_block", 2), window_stats(7, 1, "column", "tb2"), run(3, "tb2"),
+    ]),
+    "window_stats_slabs_copy_256x32": (_c7, ("slabs", 2, "copy"), [
+        opt("time_block", 2), bodies("random3", 3), probe_set("A"),
+        window_stats(7, 3, "seam", "tb2"), window(6, 3, "seam", "tb2"), opt("time_block", 4), window_stats(9, 4, "seam", "march"),
+        opt("engine", 3), window_stats(6, 2, "seam", "slab-tiles"), run(5, "slab-tiles"),
+    ]),
+    # four p2p slabs: the shared table per slab (a window without a row in three of them), a piece per sample past the restart mark
+    # (three pieces of 4 + 1 from SLAB_TAG_MARK - 7: cleared behind the second)
+    "window_stats_slabs_p2p_tag_restart": (_c6, ("slabs", 4, "p2p"), [
+        bodies("walls+rest", 2), probe_set("A"),
+        window(8, 4, "A", "slab-tiles"), window_stats(8, 4, "A", "slab-tiles"), window_stats(8, 4, "B", "slab-tiles"), window(8, 4, "B", "slab-tiles"),
+        window_stats(6, 3, "top", "slab-tiles"), window_stats(7, 3, "every4th", "slab-tiles", 1),
+        opt("regtile_tag", SLAB_TAG_MARK - 7), window_stats(12, 4, "A", "slab-tiles"), run(5, "slab-tiles"),
+    ]),
+    # density 0.3: the three places of its own where the density reaches p0 (lbm_window_stats_fold, lbm_wave's WINDOW+STATS
+    # flavour, lbm_window_stats_add)
+    "window_stats_at_thirds_256x64": (_c13, None, [
+        bodies("blocked", 1), probe_set("A"),
+        window_stats(7, 3, "row", "tiles"), window(6, 2, "row", "tiles"), window_stats(6, 2, "all", "tiles", 2),
+        opt("time_block", 8), opt("march_kernel", 1), opt("wave_cols", 2),
+        window_stats(17, 4, "row", "wave"), window_stats(16, 1, "all", "wave"),
+        opt("time_block", 4), opt("march_kernel", 0), window_stats(9, 4, "row", "march"),
+        opt("engine", 3), window_stats(6, 2, "row", "tiles"),
+    ]),
 }
 REFUSING = {"refusal_point_mixed"}
 # (as test_call_sequences: float and double part once a refusal flips on rounding; the first two calls, inside which the
@@ -372,6 +447,8 @@ class ObserverModel(Model):
         self.windows, self.psets = case["windows"], case["psets"]
         self.accel = np.float32(case["p"].accel)
         self.pset, self.tb, self.wave_cols, self.dtab_cap = None, 0, 1, 0
+        self.ws_chunk = 0                                        # the option "window_stats_chunk"
+        self.context = "lone" if ctx is None else " ".join(str(v) for v in (ctx[0], ctx[-1]))
         self.trace, self.waves = [], set()
 
     def window_rows(self, w):
@@ -395,13 +472,15 @@ class ObserverModel(Model):
         """Advances the model over `call`; returns its entry of the trace ("tag": the expected mailbox tag after it)."""
         op = call[0]
         e = dict(i=len(self.trace), op=op, call=call, running=op in RUNNING, ty=self.ty, r=self.r, asy=self.async_,
-                 pset=self.pset, label=self.label_name, nb=self.nb, body=self.body, accel=self.accel, tb=self.tb)
+                 pset=self.pset, label=self.label_name, nb=self.nb, body=self.body, accel=self.accel, tb=self.tb, context=self.context)
         if op == "opt":
             e.update(key=call[1], value=call[2])
             if call[1] == "time_block":
                 self.tb = call[2]
             elif call[1] == "wave_cols":
                 self.wave_cols = call[2]
+            elif call[1] == "window_stats_chunk":
+                self.ws_chunk = call[2]
             super().apply(call)
         elif op == "bodies":
             super().apply(call)
@@ -436,6 +515,10 @@ class ObserverModel(Model):
             sched = call[2]
         elif op == "stats":
             kinds, ste = ("stats",), call[2]
+        elif op == "window_stats":
+            kinds, fe, win = ("window_stats",), call[2], call[3]
+            if call[4] is not None:
+                self.ws_chunk = call[4]
         elif op == "observed":
             kinds, pe, me, fe = call[2:6]
         elif op == "driven_observed":
@@ -454,6 +537,16 @@ class ObserverModel(Model):
         else:
             cutters = ()
         ends = _bounds(n, *cutters)
+        if op == "window_stats":
+            # lbm_host_observe.inc: ONE run where lbm_wave takes the sums; on the tiles a launch per piece of c sample steps --
+            # c = min(chunk, m), or automatic: the samples that 64 MiB of staging hold of the slab with the most window cells,
+            # at least 1, at most m -- and one more for the steps behind the last sample; elsewhere a piece per sample (cutters)
+            w = self.windows[win]
+            m, cells = n // fe, w.nx * max(self.window_rows(w))
+            if fam == "tiles":
+                c = min(self.ws_chunk, m) if self.ws_chunk > 0 else min(m, max(1, (64 << 20) // (16 * cells)))
+                ends = sorted({min(k + c, m) * fe for k in range(0, m, c)} | {n})
+            e.update(chunk=self.ws_chunk, wcells=cells, m=m)
         e.update(n=n, path=path, fam=fam, kinds=tuple(kinds), pe=pe, me=me, fe=fe, ste=ste, sched=sched, win=win, multi=multi,
                  cutters=cutters, ends=ends, pieces=[b - a for a, b in zip([0] + ends, ends)], restarts=[],
                  sched_name=None if sched is None else sched if sched == "const" else sched[0],
@@ -489,6 +582,8 @@ def expected_keys(e):
         return {single[op] + "_in_kernel": int(T), single[op] + "_in_wave": int(W)}
     if op == "stats":                                            # (the ONE piece on lbm_wave: n >= time_block; no *_in_kernel key)
         return {"stats_in_wave": int(W)}
+    if op == "window_stats":
+        return {"window_stats_in_kernel": int(T), "window_stats_in_wave": int(W), "window_stats_pieces": len(e["pieces"])}
     if op == "observed":
         return {"observed_in_kernel": bits if T else 0, "observed_in_wave": bits if W else 0, "observed_pieces": len(e["pieces"])}
     if op == "driven_observed":
@@ -638,20 +733,65 @@ for _fam in ("tiles", "wave"):
             lambda t, k=_k, kw=_kw, fam=_fam: bool(_chains(t, [_is(k, fam=fam, **kw), _is("stats", fam=fam)], _quiet)))
         TRANSITIONS[f"stats, then {_k} on {_fam}"] = (
             lambda t, k=_k, kw=_kw, fam=_fam: bool(_chains(t, [_is("stats", fam=fam), _is(k, fam=fam, **kw)], _quiet)))
+# lbm_run_window_stats: the window table it shares with lbm_run_window, the tables and options around it, its pieces and the tag
+def _same_window(first, second, path):
+    return lambda t: any(a["wkey"] == b["wkey"] and a["ty"] == b["ty"] for a, b in _chains(t, [_is(first, path), _is(second, path)], _quiet))
+
+
+def _ws_a_b_then_window_b(path):
+    return lambda t: any(a["wkey"] != b["wkey"] == c["wkey"]
+                         for a, b, c in _chains(t, [_is("window_stats", path), _is("window_stats", path), _is("window", path)], _quiet))
+
+
+def _ws_restart(context):
+    return lambda t: any(e["op"] == "window_stats" and e["fam"] == "tiles" and e["context"] == context and len(e["pieces"]) >= 3
+                         and any(0 < j < len(e["pieces"]) - 1 for j in e["restarts"]) for e in t if e["running"])
+
+
+TRANSITIONS.update({
+    "window(A), then window_stats(A) on tiles": _same_window("window", "window_stats", "tiles"),
+    "window(A), then window_stats(A) on slab-tiles": _same_window("window", "window_stats", "slab-tiles"),
+    "window(A), then window_stats(A) on wave": _same_window("window", "window_stats", "wave"),
+    "window_stats(A), window_stats(B), window(B) on tiles": _ws_a_b_then_window_b("tiles"),
+    "window_stats(A), window_stats(B), window(B) on slab-tiles": _ws_a_b_then_window_b("slab-tiles"),
+    "a window_stats call, a retile, the same window": lambda t: any(
+        a["wkey"] == b["wkey"] and a["ty"] != b["ty"]
+        for a, _, b in _chains(t, [_is("window_stats", "tiles"), _is("opt", key="regtile"), _is("window_stats", "tiles")], _quiet)),
+    "probes, window_stats, probes with the same set on tiles": lambda t: any(
+        a["pset"] == b["pset"] == c["pset"] and a["ty"] == c["ty"]
+        for a, b, c in _chains(t, [_is("probes", "tiles"), _is("window_stats", "tiles"), _is("probes", "tiles")], lambda e: False)),
+    "set_accel, window_stats on tiles": lambda t: any(
+        r["accel"] == s["accel_after"] != s["accel"] for s, r in _chains(t, [_is("set_accel"), _is("window_stats", fam="tiles")], _quiet)),
+    "set_accel, window_stats on wave": lambda t: any(
+        r["accel"] == s["accel_after"] != s["accel"] for s, r in _chains(t, [_is("set_accel"), _is("window_stats", "wave")], _quiet)),
+    "window_stats_chunk changed between two window_stats calls with one window": lambda t: any(
+        a["chunk"] != b["chunk"] and a["wkey"] == b["wkey"] and a["n"] == b["n"] and a["pieces"] != b["pieces"]
+        for a, b in _chains(t, [_is("window_stats", fam="tiles")] * 2, lambda e: e["op"] != "window_stats")),
+    "the pieces of a window_stats call pass TAG_WRAP on a lattice alone": _ws_restart("lone"),
+    "the pieces of a window_stats call pass SLAB_TAG_MARK across p2p slabs": _ws_restart("slabs p2p"),
+    "a window_stats call on slab-tiles without a window row in some slab": lambda t: any(
+        e["op"] == "window_stats" and e["path"] == "slab-tiles" and 0 in e["wslabs"] for e in t if e["running"]),
+})
+for _fam in ("tiles", "wave"):
+    TRANSITIONS[f"stats, then window_stats on {_fam}"] = (
+        lambda t, fam=_fam: bool(_chains(t, [_is("stats", fam=fam), _is("window_stats", fam=fam)], _quiet)))
+    TRANSITIONS[f"window_stats, then stats on {_fam}"] = (
+        lambda t, fam=_fam: bool(_chains(t, [_is("window_stats", fam=fam), _is("stats", fam=fam)], _quiet)))
 # (context, path family) in which lbm_run_stats must run; "thirds": a lattice alone at density 0.3
 STATS_AT = ([(c, "tiles") for c in ("lone", "slabs p2p", "slabs copy", "rank p2p")] + [("lone", "wave"), ("lone", "split"), ("slabs copy", "split"),
             ("rank rccl", "split"), ("thirds", "tiles"), ("thirds", "wave")])
-REFUSALS = ("window", "schedule", "probes", "forces", "mean", "observed mean", "stats")
+WINDOW_STATS_AT = list(STATS_AT) + [("thirds", "split")]     # ... and lbm_run_window_stats: the three sites of its own that hand on the density
+REFUSALS = ("window", "schedule", "probes", "forces", "mean", "observed mean", "stats", "window_stats window", "window_stats every")
 COVERAGE_PATHS = ("tiles R1", "tiles R2", "tiles R4", "tiles async0", "tiles async1", "slab-tiles", "tb1", "tb2", "march", "wave")
 COVERAGE_CONTEXTS = ("lone", "slabs p2p", "slabs copy", "rank p2p", "rank rccl")
 WINDOW_SHAPES = ("stride > 1", "a single row", "a single column", "across a tile seam", "across a slab seam", "the whole lattice")
 
 
-def _window_shapes(m, case):
-    """Which of WINDOW_SHAPES the window runs of a program hold."""
+def _window_shapes(m, case, op="window"):
+    """Which of WINDOW_SHAPES the window runs (op "window_stats": the window-stats runs) of a program hold."""
     out = set()
     for e in m.trace:
-        if e["op"] != "window":
+        if e["op"] != op:
             continue
         x0, y0, nx, ny, sx, sy = e["wkey"]
         if (sx > 1 and nx > 1) or (sy > 1 and ny > 1):
@@ -671,7 +811,7 @@ def _window_shapes(m, case):
 
 def coverage(L, programs):
     """What a table of programs covers: (pairs, contexts, transitions, refusals, window shapes, waves, mixes at the refusal point,
-    (context, path family) of the stats calls)."""
+    (context, path family) of the stats calls and, as "window_stats at" pairs and "window_stats: " shapes, of the window-stats calls)."""
     pairs, contexts, found, refusals, shapes, waves, refusing, stats_at = set(), set(), set(), set(), set(), set(), False, set()
     for name, (setup, ctx, calls) in programs.items():
         case = setup(L)
@@ -685,8 +825,11 @@ def coverage(L, programs):
         stats_at |= {(context, e["fam"]) for e in m.trace if e["op"] == "stats"}
         if ctx is None and np.float32(m.p.density) == np.float32(THIRDS[0]):
             stats_at |= {("thirds", e["fam"]) for e in m.trace if e["op"] == "stats"}
+        # (the window-stats calls in the same two sets, marked: the tuple this function returns keeps its length)
+        thirds = ctx is None and np.float32(m.p.density) == np.float32(THIRDS[0])
+        stats_at |= {("window_stats", c, e["fam"]) for e in m.trace if e["op"] == "window_stats" for c in ((context, "thirds") if thirds else (context,))}
         found |= {t for t, holds in TRANSITIONS.items() if holds(m.trace)}
-        shapes |= _window_shapes(m, case)
+        shapes |= _window_shapes(m, case) | {"window_stats: " + s for s in _window_shapes(m, case, "window_stats")}
         waves |= m.waves
         for e in m.trace:
             if e["op"] == "refused":                             # in the middle of a program: a running call before and after
@@ -708,6 +851,8 @@ def missing(L, programs):
     out += ["refused: " + r for r in REFUSALS if r not in refusals]
     out += ["window: " + s for s in WINDOW_SHAPES if s not in shapes]
     out += ["stats on %s, %s" % at for at in STATS_AT if at not in stats_at]
+    out += ["window: window_stats: " + s for s in WINDOW_SHAPES if "window_stats: " + s not in shapes]
+    out += ["window_stats on %s, %s" % at for at in WINDOW_STATS_AT if ("window_stats",) + at not in stats_at]
     if len({k for k, _ in waves if k in (4, 6, 8)}) < 2:
         out.append("lbm_wave at two of K = 4, 6, 8")
     if not any(c == 2 for _, c in waves):
@@ -732,31 +877,56 @@ def test_program_table_covers_every_path_and_transition(L):
             assert (e["fam"] != "wave") or e["n"] >= e["tb"] >= 4, where              # lbm_wave runs: a full pass at least
             if e["op"] == "observed":
                 assert len(e["kinds"]) >= 2, where                                     # (one observer alone is its own call)
-            assert all(k in (F, P, M, S, "window", "stats") for k in e["kinds"]), where
+            assert all(k in (F, P, M, S, "window", "stats", "window_stats") for k in e["kinds"]), where
             assert ("stats" in e["kinds"]) == (e["op"] == "stats") == (e["ste"] > 0) and e["ste"] <= e["n"], where
             for k, ev in ((P, e["pe"]), (M, e["me"]), (S, e["fe"])):
                 assert (k in e["kinds"] or (k == S and bool(e["win"]))) == (ev > 0) and ev <= e["n"], where
             if e["win"]:
                 assert 0 < e["fe"] <= e["n"], where
             assert (P not in e["kinds"] or e["pset"]) and (F not in e["kinds"] or e["nb"] > 0), where
-            assert len(e["pieces"]) == pieces_of(e["n"], *e["cutters"]) and sum(e["pieces"]) == e["n"], where
+            assert sum(e["pieces"]) == e["n"] and all(k > 0 for k in e["pieces"]), where
+            if e["op"] == "window_stats":
+                assert ("window_stats" in e["kinds"]) and e["m"] >= 1 and 0 <= e["chunk"] <= 2, where
+                assert len(e["pieces"]) == window_stats_pieces_of(e["n"], e["fe"], e["chunk"], e["fam"], e["wcells"]), where
+                if e["fam"] == "tiles":                          # every piece but the tail ends on a sample step
+                    assert all(b % e["fe"] == 0 for b in e["ends"][:-1]) and e["ends"][-1] == e["n"], where
+            else:
+                assert len(e["pieces"]) == pieces_of(e["n"], *e["cutters"]), where
         for e in m.trace:                                        # the windows the programs run are windows; the refused one is not
-            if e["op"] == "window":
+            if e["op"] in ("window", "window_stats"):
                 L.window_rows(case["windows"][e["win"]], m.p.nx, m.p.ny, 0, m.p.ny)
-            if e["op"] == "refused" and e["what"] == "window":
+            if e["op"] == "refused" and e["what"] in ("window", "window_stats window"):
                 with pytest.raises(L.LbmError):
                     L.window_rows(case["windows"][e["args"][2]], m.p.nx, m.p.ny, 0, m.p.ny)
+            if e["op"] == "refused" and e["what"] == "window_stats every":
+                assert e["args"][1] > e["args"][0] > 0
+                L.window_rows(case["windows"][e["args"][2]], m.p.nx, m.p.ny, 0, m.p.ny)
 
 
 @pytest.mark.parametrize("drop", [("lone_128_flavour_walk", 4), ("wave6_maps_130x37", 6), ("slabs_p2p_tiles_tag_restart", 12),
                                   ("rank_ring_of_one_rccl", None), ("schedule_table_128x16", 4), ("never_tiles_tb1_tb2", 12),
                                   ("stats_neighbours_on_tiles_128", 9), ("stats_neighbours_on_wave6_130x37", 13),
                                   ("stats_tilings_and_tag_wrap_128x16", 9), ("stats_slabs_copy_256x32", 10), ("stats_at_thirds_256x64", None),
-                                  ("rank_ring_of_one_p2p", 9), ("stats_never_tiles_tb1", 3)])
+                                  ("rank_ring_of_one_p2p", 9), ("stats_never_tiles_tb1", 3),
+                                  # lbm_run_window_stats: the window call in front of one over the same window; the second of
+                                  # A, B, window(B); the retile between two; the probes behind one; set_accel in front of one;
+                                  # the second of two chunks; the tag option in front of the wrap and of the restart; the stats
+                                  # call behind and in front of one; the two refused ones; a context, a path, the split path at
+                                  # density 0.3; the 0.3 program
+                                  ("window_stats_walk_on_tiles_128", 2), ("window_stats_slabs_p2p_tag_restart", 4),
+                                  ("window_stats_retile_and_tag_wrap_256", 4), ("window_stats_walk_on_tiles_128", 8),
+                                  ("window_stats_on_wave6_130x37", 9), ("window_stats_walk_on_tiles_128", 9),
+                                  ("window_stats_retile_and_tag_wrap_256", 8), ("window_stats_slabs_p2p_tag_restart", 8),
+                                  ("window_stats_walk_on_tiles_128", 15), ("window_stats_on_wave6_130x37", 5),
+                                  ("window_stats_walk_on_tiles_128", 16), ("window_stats_on_wave6_130x37", 11),
+                                  ("rank_ring_of_one_rccl", 11), ("rank_ring_of_one_p2p", 10), ("window_stats_never_tiles_tb1_tb2", 3),
+                                  ("window_stats_slabs_copy_256x32", 8), ("window_stats_at_thirds_256x64", 12),
+                                  ("window_stats_at_thirds_256x64", None)])
 def test_a_trimmed_table_fails_the_coverage_check(L, drop):
     """Without one call (a flavour of the walk, a relabel, the tag option, the long driven call, a refused call; a stats call
     between two windows or two driven calls, the tag option in front of one, the one whose pieces pass a mark, the one of a
-    context or a path) or one program (a context, the density 0.3) the table no longer covers the list."""
+    context or a path; the calls around a window-stats call listed above) or one program (a context, the density 0.3) the
+    table no longer covers the list."""
     name, index = drop
     programs = dict(PROGRAMS)
     if index is None:
@@ -811,6 +981,31 @@ def test_model_restates_the_tag_and_capacity_rules(L):
     m, _ = _walk(L, "stats_neighbours_on_wave6_130x37")
     e = m.trace[4]
     assert e["call"] == stats(13, 3, "wave") and e["pieces"] == [13] and expected_keys(e) == {"stats_in_wave": 1} and e["tag"] == 1
+    # lbm_run_window_stats: pieces of `chunk` sample steps and the tail on the tiles, n_i + 1 tags a piece, the marks per piece
+    m, _ = _walk(L, "window_stats_walk_on_tiles_128")
+    t = {e["i"]: e for e in m.trace}
+    assert t[2]["tag"] == 1 + 7 and t[3]["pieces"] == [6] and t[3]["tag"] == 8 + 7              # automatic: one piece of three samples
+    assert t[4]["pieces"] == [6, 1] and t[4]["tag"] == 15 + 7 + 2                               # ... and the tail
+    assert t[7]["call"] == window_stats(9, 2, "wake", "tiles", 2) and t[7]["pieces"] == [4, 4, 1] and t[7]["tag"] - t[6]["tag"] == 5 + 5 + 2
+    assert t[9]["pieces"] == [2, 2, 2, 2, 1] and t[9]["tag"] - t[8]["tag"] == 4 * 3 + 2 and t[9]["chunk"] == 1
+    assert expected_keys(t[9]) == {"window_stats_in_kernel": 1, "window_stats_in_wave": 0, "window_stats_pieces": 5}
+    assert t[11]["chunk"] == 0 and t[11]["pieces"] == [6] and t[14]["chunk"] == 0 and t[14]["pieces"] == [6, 1]
+    m, _ = _walk(L, "window_stats_retile_and_tag_wrap_256")
+    e = m.trace[9]
+    assert e["call"] == window_stats(12, 4, "seam", "tiles", 1) and e["pieces"] == [4, 4, 4] and e["restarts"] == [1] and e["tag"] == 1 + 5 + 5
+    assert m.trace[7]["pieces"] == [4, 2, 1] and m.trace[7]["chunk"] == 2                       # three samples in chunks of two: a cut piece
+    m, _ = _walk(L, "window_stats_slabs_p2p_tag_restart")
+    e = m.trace[9]
+    assert e["call"] == window_stats(12, 4, "A", "slab-tiles") and e["chunk"] == 1 and e["pieces"] == [4, 4, 4] and e["restarts"] == [1] and e["tag"] == 1 + 5
+    assert m.trace[6]["wslabs"] == [0, 0, 0, 6] and m.trace[3]["wslabs"] == [2, 3, 0, 0]        # in one slab; across the first seam
+    m, _ = _walk(L, "window_stats_on_wave6_130x37")
+    e = m.trace[4]
+    assert e["pieces"] == [13] and e["tag"] == 1 and expected_keys(e) == {"window_stats_in_kernel": 0, "window_stats_in_wave": 1, "window_stats_pieces": 1}
+    m, _ = _walk(L, "window_stats_slabs_copy_256x32")
+    e = m.trace[3]
+    assert e["pieces"] == [3, 3, 1] and e["tag"] == 1 and expected_keys(e) == {"window_stats_in_kernel": 0, "window_stats_in_wave": 0, "window_stats_pieces": 3}
+    # the automatic chunk where the bound bites: 16 MiB a sample of a 1024 x 1024 window, four to a piece
+    assert window_stats_pieces_of(9, 1, 0, "tiles", cells=1024 * 1024) == 3
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
@@ -999,6 +1194,12 @@ def _call(lat, e, case, acc):
     if op == "stats":
         av, out = lat.run_stats(n, e["ste"])
         return av, {"stats": out}
+    if op == "window_stats":
+        if e["call"][4] is not None:
+            lat.set_option("window_stats_chunk", e["call"][4])
+        assert lat.info("window_stats_chunk") == e["chunk"]
+        av, out = lat.run_window_stats(n, e["fe"], case["windows"][e["win"]])
+        return av, {"window_stats": out}
     res = lat.run_observed(n, **_want(e)) if op == "observed" else lat.run_driven_observed(acc, **_want(e))
     return res.pop("av_vels"), res
 
@@ -1039,6 +1240,8 @@ def _refuse(L, lat, e, case):
             lat.run_mean(a[0], a[1])
         elif what == "stats":
             lat.run_stats(a[0], a[1])
+        elif what in ("window_stats window", "window_stats every"):
+            lat.run_window_stats(a[0], a[1], case["windows"][a[2]])
         else:
             assert what == "observed mean"
             lat.run_observed(a[0], forces=e["nb"] > 0, mean_every=a[1])
@@ -1088,7 +1291,7 @@ def test_observer_sequence(gpu, O, oracle, monkeypatch, name):
                 else:
                     n, kinds, tiles = e["n"], e["kinds"], e["fam"] == "tiles"
                     acc = _schedule(e["sched"], p, e["accel"], n)
-                    want_fields = any(k in kinds for k in (P, M, S, "window", "stats"))
+                    want_fields = any(k in kinds for k in (P, M, S, "window", "stats", "window_stats"))
                     st0 = lat.read_state() if e["sched"] == "const" else None
                     if kind == "run":
                         av_sh, F_sh, X, numpy_forces = sh.run(n), None, None, None
@@ -1103,10 +1306,12 @@ def test_observer_sequence(gpu, O, oracle, monkeypatch, name):
                         exp[M] = mean_from_fields(X, e["me"])
                     if S in kinds:
                         exp[S] = X[e["fe"] - 1::e["fe"]]
-                    if e["win"]:
+                    if "window" in kinds:
                         exp["window"] = cut(X[e["fe"] - 1::e["fe"]], case["windows"][e["win"]])
                     if "stats" in kinds:
                         exp["stats"] = stats_of(X[e["ste"] - 1::e["ste"]], p0_of(p.density))
+                    if "window_stats" in kinds:
+                        exp["window_stats"] = stats_of(cut(X[e["fe"] - 1::e["fe"]], case["windows"][e["win"]]), p0_of(p.density))
                     assert sorted(out) == sorted(kinds), (where, sorted(out))
                     for k, v in exp.items():
                         _same(out[k], v, where + (k,))

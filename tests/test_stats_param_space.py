@@ -272,10 +272,21 @@ def _reference(L, O, path, point):
 def _outside_bounds(O, prm, ob, S, X, stats, p0):
     """(worst |stats[4..7] - mean Q| / bQ, worst |V - W| / its bound) by the module docstring; S, X: the sampled steps'
     lattices and fields (m, ny, nx, .); asserts both bounds and the exact zeros of the blocked cells."""
+    return bounds_from_fields(double_oracle_fields(O, prm, ob, S), ob != 0, X, stats, p0)
+
+
+def double_oracle_fields(O, prm, ob, S):
+    """fo_j: the DOUBLE oracle's fields of the lattices S (m, ny, nx, 9), (m, ny, nx, 4) float64"""
     o64 = O.Oracle("strict")
-    m, ny, nx = X.shape[:3]
-    blocked = ob != 0
-    fo = np.stack([o64.final_state(prm, s.astype(np.float64), ob).reshape(ny, nx, 4) for s in S])
+    ny, nx = ob.shape
+    return np.stack([o64.final_state(prm, s.astype(np.float64), ob).reshape(ny, nx, 4) for s in S])
+
+
+def bounds_from_fields(fo, blocked, X, stats, p0):
+    """_outside_bounds from the double oracle's fields fo, on any set of cells: fo, X (m, rows, cols, 4), blocked
+    (rows, cols) and stats (rows, cols, 8) of the same cells (tests/test_window_stats_param_space.py hands it a window's)."""
+    m = X.shape[0]
+    assert fo.shape == X.shape and blocked.shape == X.shape[1:3] and stats.shape == X.shape[1:3] + (8,)
     dx = 2e-6 * np.abs(fo) + 8 * U
     x, y, d = fo[..., 0], fo[..., 1], fo[..., 3] - float(p0)
     ex, ey, ep = dx[..., 0], dx[..., 1], dx[..., 3]

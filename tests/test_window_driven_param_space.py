@@ -127,9 +127,10 @@ def _straddle(path):
     return c, sorted(pairs, key=lambda r: abs(pairs.index(r) - mid))
 
 
-def _windows(L, path, ob):
+def windows_of(L, path, ob):
     """The three windows of a case: strided whole extent, accelerate row, 7 x 7 cells across a column edge and the first
-    of the row edges that leaves a blocked cell inside (every lattice here is at least 64 x 12)."""
+    of the row edges that leaves a blocked cell inside (every lattice here is at least 64 x 12).  ob: the case's obstacles
+    (tests/test_window_stats_param_space.py builds its windows here too, at "thirds" from that point's own map)."""
     nx, ny = PATHS[path][:2]
     W = L.Window
     c, rows = _straddle(path)
@@ -214,7 +215,7 @@ def test_windows_hold_what_they_claim(L, path, point):
     """Three legal windows, blocked and fluid cells in each; the rectangle at least 5 x 5 cells with cells on both sides of
     the path's first column edge and of one of its row edges (of the middle of the lattice where it has none)."""
     nx, ny, K, n, (pe, me, se), kind, ob, cells, _, _ = _case(path, point)
-    ws = _windows(L, path, ob)
+    ws = windows_of(L, path, ob)
     assert len(ws) == 3 and n // se >= 1 and (pe, me, se) == _periods(K, n)
     for w in ws:
         assert w.nx >= 1 and w.ny >= 1 and 0 <= w.x0 and 0 <= w.y0
@@ -370,7 +371,7 @@ def test_windows_on_the_parameter_grid(gpu, O, monkeypatch, path, point):
     assert np.array_equal(_bits(st0), _bits(ref["S"][n - 1])), (path, point, "the lattice of the one-step kernel")
     fields = ref["X"][se - 1:n:se][:n // se]
     const = np.array([0.0, 0.0, 0.0, np.float32(_lparam(L, point, nx, ny).density) * ONE_THIRD], dtype=np.float32)
-    for w in _windows(L, path, ob):
+    for w in windows_of(L, path, ob):
         where = (path, point, n, se, w)
         with _context(L, path, point, monkeypatch) as lat:
             av, out = lat.run_window(n, se, w)

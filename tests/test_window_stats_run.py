@@ -9,7 +9,15 @@ is cut); every other engine here runs the steps in pieces of `every` with lbm_wi
 tests/test_wave_window_stats.py).  Every comparison is on bit patterns unless it says otherwise.
 
 The expected value is always stats_of(cut(snaps, w), p0), snaps the snapshots of the split path (engine 1, time_block 1,
-run_sampled at every = 1) computed once per case and sliced."""
+run_sampled at every = 1) computed once per case and sliced.
+
+Everything here runs at density 0.1, omega 1.85 and the decks' acceleration, and all but test_one_context_through_mixed_calls on
+a fresh context per call.  Away from that point -- the other densities, density 0.3 where density * (1.f / 3.f) is not
+density / 3.f, the refusing accelerate row, chunk cuts on every path -- tests/test_window_stats_param_space.py (100 GPU cases;
+second moments at most 0.053 and variances 0.034 of the double oracle's bounds; nothing found); on one long-lived context --
+the window table shared with lbm_run_window, re-tilings, the chunk option, the pieces across TAG_WRAP and SLAB_TAG_MARK, live
+maps and written lattices in front -- the window_stats entries of tests/test_observer_sequences.py and
+tests/test_live_sequences.py."""
 import ctypes as C
 
 import numpy as np
