@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -775,10 +776,9 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     HIPC(hipSetDevice(sl.dev));
     int rc;
     if (psample(s) && (rc = launch_probe_gather(c, sl, w.pout + 4 * (size_t)w.prow(k.pfirst, s) * (size_t)c->nprobes))) return rc;
-    const bool wstats = w.win && w.fstats;       // (lbm_run_window_stats: the sums over the window's cells)
-    if (fsample(s) && wstats && (rc = launch_window_stats_add(c, sl, w.win->w, 0, w.win->w.ny, w.fout))) return rc;
-    if (fsample(s) && w.fadd && !wstats && (rc = w.fstats ? launch_stats_add(c, sl, w.fout) : launch_mean_add(c, sl, w.fout))) return rc;
-    if (fsample(s) && w.win && !wstats && (rc = launch_derive_window(c, sl, w.win->w, 0, w.win->w.ny, w.fslot(s)))) return rc;
+    // (a window: into the sample's slot, or -- lbm_run_window_stats, one slot -- the sums over the window's cells)
+    if (fsample(s) && w.win && (rc = launch_window(c, sl, w.win->w, 0, w.win->w.ny, w.fslot(s), w.fstats))) return rc;
+    if (fsample(s) && w.fadd && !w.win && (rc = launch_cell_add(c, sl, w.fstats ? 8 : 4, w.fout))) return rc;
     if (fsample(s) && !w.fadd && !w.win) {
       const long ncell = (long)sl.nyl * nx;
       hipLaunchKernelGGL(lbm::lbm_derive, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.sc, sl.lat[c->cur], sl.plane, sl.pitch,

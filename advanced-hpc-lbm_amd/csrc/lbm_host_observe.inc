@@ -1,13 +1,23 @@
 // lbm_host_observe.inc -- part of lbm_api.hip (included there, in front of run_steps): the observer calls -- lbm_run_sampled,
-// lbm_run_forces, lbm_run_mean, lbm_run_probes with lbm_set_bodies / lbm_set_probes, lbm_run_observed, and lbm_run_window
-// with lbm_window_rows (WindowOut, window_tables, launch_derive_window: in front of it), lbm_run_window_stats behind it
-// (WindowStats) -- and the one copy of what they share:
+// lbm_run_forces, lbm_run_mean, lbm_run_stats, lbm_run_probes with lbm_set_bodies / lbm_set_probes, lbm_run_observed, and
+// lbm_run_window with lbm_window_rows (WindowOut, window_tables: in front of it), lbm_run_window_stats behind it -- and the
+// one copy of what they share:
 //   output_on_device, ranks_agree          where an output lies; a rank context's ranks take the same path and fail together
-//   launch_probe_gather / _mean_add / _mean_div   the one launch site of each small kernel (run_steps' pgather uses them too)
+//   device_room, wait_slabs, zero_output   an allocation whose refusal the caller words; every slab's stream waited for; an
+//                                          output of which other ranks hold rows, zeroed first
+//   launch_probe_gather, launch_cell_add (lbm_mean_add / lbm_stats_add), launch_window (lbm_derive_window /
+//   lbm_window_stats_add), launch_mean_div the one launch site of each small kernel (run_steps' pgather uses them too);
+//                                          lbm_window_stats_fold is launched by CellSums::fold alone
 //   fetch_forces                           a run's forces from behind its per-step sums
-//   ProbeOut, MeanOut                      where one call's probe values / means go: device output in place, host output
+//   SlabRows                               which rows of an output each slab owns: of the lattice, or of a window (the one
+//                                          caller of lbm_window_rows)
+//   ProbeOut, WindowOut                    where one call's probe values / windows go: device output in place, host output
 //                                          through per-slab staging (snapshots keep derive_all and their two staging shapes)
-//   run_split                              the step loop cut at the sample steps, plain run_steps pieces (the single calls)
+//   CellSums                               a record of 4 or 8 floats per cell and slab, over the lattice or a window, divided
+//                                          at the end: lbm_run_mean, lbm_run_stats, lbm_run_window_stats, lbm_run_observed
+//   run_split, TilePieces                  the step loop cut at the sample steps (the single calls): plain run_steps pieces,
+//                                          or register-tile pieces of `chunk` samples first, with the give-up rule, the
+//                                          times and the piece count
 //   observers_free                         everything a slab holds for these calls, released in one place (slab_free)
 // Each call keeps its own refusals, the order in which it decides things before anything is queued, and its choice of path; it
 // names what the register tiles would run in RunKind::flavour, and hands its cells to the one table builder (tile_table_set).
@@ -66,6 +76,34 @@ static int ranks_agree(lbm_ctx* c, int rc, bool* in_kernel, const char* what) {
 
 namespace {
 
+// room for `bytes` on the current device; false: none -- the HIP error cleared, *p NULL (the caller words the refusal)
+bool device_room(void** p, size_t bytes) {
+  if (hipMalloc(p, bytes) == hipSuccess) return true;
+  (void)hipGetLastError();
+  *p = nullptr;
+  return false;
+}
+
+// every slab's stream waited for
+int wait_slabs(lbm_ctx* c) {
+  for (auto& s : c->slabs) {
+    HIPC(hipSetDevice(s.dev));
+    HIPC(hipStreamSynchronize(s.sc));
+  }
+  return LBM_OK;
+}
+
+// an output of which this context's slabs hold only a part: what other ranks' rows hold reads +0.0f
+int zero_output(lbm_ctx* c, float* out, size_t bytes, bool on_dev) {
+  if (on_dev) {
+    Slab& s = c->slabs[0];
+    HIPC(hipSetDevice(s.dev));
+    HIPC(hipMemsetAsync(out, 0, bytes, s.sc));
+    HIPC(hipStreamSynchronize(s.sc));
+  } else memset(out, 0, bytes);
+  return LBM_OK;
+}
+
 // ---- the small kernels behind a stored lattice, each launched from here alone (on the slab's stream)
 
 // the slab's probes' cells of the stored lattice into their places of out_row, one sample's row of 4 x nprobes floats
@@ -78,33 +116,37 @@ int launch_probe_gather(const lbm_ctx* c, Slab& s, float* out_row) {
   return LBM_OK;
 }
 
-// the fields of the slab's stored lattice added to its sums, one float4 per cell
-int launch_mean_add(const lbm_ctx* c, Slab& s, float* acc) {
+// the fields of the slab's stored lattice added to its sums, one record per cell: of 4 floats (lbm_mean_add), or of 8 with
+// their products beside them (lbm_stats_add)
+int launch_cell_add(const lbm_ctx* c, Slab& s, int width, float* acc) {
   const int nx = c->p.nx;
   const long ncell = (long)s.nyl * nx;
   HIPC(hipSetDevice(s.dev));
-  hipLaunchKernelGGL(lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
-                     nx, ncell, s.blocked, c->p.density, acc);
+  hipLaunchKernelGGL(width == 8 ? lbm::lbm_stats_add : lbm::lbm_mean_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
+                     s.lat[c->cur], s.plane, s.pitch, nx, ncell, s.blocked, c->p.density, acc);
   HIPC(hipGetLastError());
   return LBM_OK;
 }
 
-// ... and beside them their products, eight floats per cell (lbm_run_stats)
-int launch_stats_add(const lbm_ctx* c, Slab& s, float* acc) {
-  const int nx = c->p.nx;
-  const long ncell = (long)s.nyl * nx;
+// the slab's sums of m samples, nf4 float4s, divided into out (which may be the sums themselves)
+int launch_mean_div(Slab& s, const float* acc, long nf4, int m, float* out) {
   HIPC(hipSetDevice(s.dev));
-  hipLaunchKernelGGL(lbm::lbm_stats_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
-                     nx, ncell, s.blocked, c->p.density, acc);
+  hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(nf4, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, acc, nf4, (float)m, out);
   HIPC(hipGetLastError());
   return LBM_OK;
 }
 
-// the slab's sums of m samples divided into out (which may be the sums themselves); width: floats per cell, 4 or 8
-int launch_mean_div(const lbm_ctx* c, Slab& s, const float* acc, int m, float* out, int width = 4) {
-  const long ncell = (long)s.nyl * c->p.nx * (width / 4);      // (float4s)
+// the window cells of a slab's stored lattice, the slab's window rows first .. first + count - 1: into out = float[count][w.nx][4]
+// (lbm_derive_window), or -- stats -- added with their products to out = float[count][w.nx][8], the sums of those rows
+// (lbm_window_stats_add)
+int launch_window(const lbm_ctx* c, Slab& s, const lbm_window& w, int first, int count, float* out, bool stats) {
+  if (count <= 0) return LBM_OK;
+  const long ncell = (long)count * w.nx;
+  const long yl0 = (long)w.y0 + (long)first * w.sy - s.row0;
   HIPC(hipSetDevice(s.dev));
-  hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, acc, ncell, (float)m, out);
+  hipLaunchKernelGGL(stats ? lbm::lbm_window_stats_add : lbm::lbm_derive_window, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc,
+                     s.lat[c->cur], s.plane, s.pitch, w.x0, w.nx > 1 ? w.sx : 1, w.nx, (int)yl0, count > 1 ? w.sy : 1, ncell, s.blocked,
+                     c->p.density, out);
   HIPC(hipGetLastError());
   return LBM_OK;
 }
@@ -139,25 +181,13 @@ struct ProbeOut {
       local += s.pcells_host.size();
       if (on_dev || s.pcells_host.empty()) continue;
       HIPC(hipSetDevice(s.dev));
-      if (hipMalloc(&stage[i].p, sizeof(float) * nfloat) != hipSuccess) {
-        (void)hipGetLastError();
-        stage[i].p = nullptr;
+      if (!device_room(&stage[i].p, sizeof(float) * nfloat))
         return fail(LBM_ENOMEM, "no room on device %d for %d sample(s) of %d probe(s) of slab %zu (%zu bytes)", s.dev, m, np, i, sizeof(float) * nfloat);
-      }
     }
     return LBM_OK;
   }
   // the probes of other ranks' rows read +0.0f
-  int zero_foreign() {
-    if (local >= (size_t)np) return LBM_OK;
-    if (on_dev) {
-      Slab& s = c->slabs[0];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(out, 0, sizeof(float) * nfloat, s.sc));
-      HIPC(hipStreamSynchronize(s.sc));
-    } else memset(out, 0, sizeof(float) * nfloat);
-    return LBM_OK;
-  }
+  int zero_foreign() { return local >= (size_t)np ? LBM_OK : zero_output(c, out, sizeof(float) * nfloat, on_dev); }
   // row `row` of what slab i stores into (a slab without a probe stores nothing: NULL)
   float* at(size_t i, int row) const {
     float* base = on_dev ? out : (float*)stage[i].p;
@@ -194,88 +224,189 @@ struct ProbeOut {
   }
 };
 
-// Where one call's means go, [rows][nx][width] floats: one record per cell and slab, of 4 floats (lbm_run_mean: the fields)
-// or 8 (lbm_run_stats: the fields and their products) -- the sums of every path but the register tiles', and the staging of
-// host output on every path.  Device output is written in place.
-struct MeanOut {
+// The staging bound of lbm_run_window_stats' register-tile path: the most bytes of staged samples one slab holds at a time.  Scratch-memory
+// policy, not a tuned number (DESIGN.md 3.20): 64 MiB is four samples of the largest window a register-tile lattice has
+// (1024 x 1024 cells, 16 MiB a sample) and thousands of a wake window's.
+constexpr size_t kWindowStatsStageBytes = 64u << 20;
+
+// Which rows of an output each slab of the context owns: slab i the rows first[i] .. first[i] + count[i] - 1 of `nx` cells,
+// `local` rows between them.  Of a window: its window rows (lbm_window_rows) of w.nx cells; of the whole lattice: the
+// slab's nyl rows of nx cells, counted from the context's first row.
+struct SlabRows {
+  std::vector<int> first, count;
+  long local = 0;
+  int nx;
+
+  SlabRows(const lbm_ctx* c, const lbm_window* w) : nx(w ? w->nx : c->p.nx) {
+    for (auto& s : c->slabs) {
+      int f = s.row0 - (c->rank_mode ? c->slabs[0].row0 : 0), n = s.nyl;
+      if (w) (void)lbm_window_rows(w, c->p.nx, c->p.ny, s.row0, s.row0 + s.nyl, &f, &n);
+      first.push_back(f); count.push_back(n); local += n;
+    }
+  }
+};
+
+// Where one call's sums live and its means go, [rows][nx][width] floats: one record per cell and slab, of 4 floats
+// (lbm_run_mean: the fields) or 8 (lbm_run_stats, lbm_run_window_stats: the fields and their products), over the whole
+// lattice or over a window's cells (win) -- the sums of every path but the register tiles' mean flavour, and the staging of
+// host output on every path.  A slab that owns no row allocates nothing and launches nothing.  Device output is written in
+// place by the divide, host output is the sums divided in place and copied out.  lbm_run_window_stats on the register
+// tiles has, beside the sums, the staging of one piece's samples, float[chunk][count][w.nx][4] per slab (stage_room, fold).
+struct CellSums : SlabRows {
   lbm_ctx* c;
   int width;
+  const lbm_window* win;
   float* out = nullptr;
   bool on_dev = false;
-  std::vector<DeviceTemp> acc;
+  std::vector<DeviceTemp> acc, stage;
 
-  explicit MeanOut(lbm_ctx* ctx, int w = 4) : c(ctx), width(w) {}
+  CellSums(lbm_ctx* ctx, int w, const lbm_window* window = nullptr) : SlabRows(ctx, window), c(ctx), width(w), win(window) {}
   int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
-  size_t bytes(const Slab& s) const { return sizeof(float) * (size_t)width * (size_t)s.nyl * (size_t)c->p.nx; }
-  float* host_rows(const Slab& s) const { return out + (long)width * (s.row0 - (c->rank_mode ? c->slabs[0].row0 : 0)) * c->p.nx; }
-  // the slabs' buffers (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
+  long cells(size_t i) const { return (long)count[i] * nx; }
+  size_t bytes(size_t i) const { return sizeof(float) * (size_t)width * (size_t)cells(i); }
+  float* sums(size_t i) const { return (float*)acc[i].p; }
+  float* out_rows(size_t i) const { return out + (size_t)width * (size_t)first[i] * (size_t)nx; }
+  // where slab i's means go
+  float* at(size_t i) const { return on_dev ? out_rows(i) : sums(i); }
+  // the slabs' sums (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
   int prepare() {
     acc.resize(c->slabs.size());
     for (size_t i = 0; i < c->slabs.size(); ++i) {
       Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
       HIPC(hipSetDevice(s.dev));
-      if (hipMalloc(&acc[i].p, bytes(s)) != hipSuccess) {
-        (void)hipGetLastError();
-        acc[i].p = nullptr;
-        return fail(LBM_ENOMEM, "no room on device %d for the sums of slab %zu (%zu bytes)", s.dev, i, bytes(s));
-      }
+      if (!device_room(&acc[i].p, bytes(i)))
+        return fail(LBM_ENOMEM, "no room on device %d for the %s of slab %zu (%zu bytes)", s.dev, win ? "window sums" : "sums", i, bytes(i));
     }
     return LBM_OK;
   }
   int clear() {
     for (size_t i = 0; i < c->slabs.size(); ++i) {
       Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
       HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(acc[i].p, 0, bytes(s), s.sc));
+      HIPC(hipMemsetAsync(acc[i].p, 0, bytes(i), s.sc));
     }
     return LBM_OK;
   }
-  float* sums(size_t i) const { return (float*)acc[i].p; }
-  // where slab i's means go
-  float* at(size_t i) const { return on_dev ? host_rows(c->slabs[i]) : sums(i); }
-  // the fields of the stored lattice added to the sums, on every slab
+  // the window rows of other ranks' lattice rows read +0.0f (the whole lattice: a context's output is its own rows, none is foreign)
+  int zero_foreign() {
+    if (!win || local >= win->ny) return LBM_OK;
+    return zero_output(c, out, sizeof(float) * (size_t)width * (size_t)nx * (size_t)win->ny, on_dev);
+  }
+  // the fields of the stored lattice (and their products) added to the sums, on every slab that owns a row
   int add() {
     int rc;
     for (size_t i = 0; i < c->slabs.size(); ++i)
-      if ((rc = width == 8 ? launch_stats_add(c, c->slabs[i], sums(i)) : launch_mean_add(c, c->slabs[i], sums(i)))) return rc;
+      if ((rc = win ? launch_window(c, c->slabs[i], *win, first[i], count[i], sums(i), true) : launch_cell_add(c, c->slabs[i], width, sums(i))))
+        return rc;
     return LBM_OK;
   }
   int to_host() {
     if (on_dev) return LBM_OK;
     for (size_t i = 0; i < c->slabs.size(); ++i) {
       Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
       HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemcpy(host_rows(s), acc[i].p, bytes(s), hipMemcpyDeviceToHost));
+      HIPC(hipMemcpy(out_rows(i), acc[i].p, bytes(i), hipMemcpyDeviceToHost));
     }
     return LBM_OK;
   }
-  // the sums of m samples divided into their place, every slab's stream waited for, host output copied out
+  // the sums of m samples divided into their place (lbm_mean_div: IEEE division), every slab's stream waited for, host
+  // output copied out
   int finish(int m) {
     int rc;
     for (size_t i = 0; i < c->slabs.size(); ++i) {
       Slab& s = c->slabs[i];
-      if ((rc = launch_mean_div(c, s, sums(i), m, at(i), width))) return rc;
+      if (count[i] > 0 && (rc = launch_mean_div(s, sums(i), cells(i) * (width / 4), m, at(i)))) return rc;
+      HIPC(hipSetDevice(s.dev));
       HIPC(hipStreamSynchronize(s.sc));
     }
     return to_host();
   }
+  // ---- lbm_run_window_stats on the register tiles
+  // the most samples a piece may stage under the bound: at least 1, at most m
+  int auto_chunk(int m) const {
+    size_t per = 0;                          // bytes of one sample of the slab with the most window cells
+    for (size_t i = 0; i < c->slabs.size(); ++i) per = std::max(per, sizeof(float) * 4 * (size_t)cells(i));
+    const size_t fit = per ? kWindowStatsStageBytes / per : (size_t)m;
+    return (int)std::min<size_t>((size_t)m, std::max<size_t>(1, fit));
+  }
+  // the staging of `chunk` samples on every slab that holds a window row; false: no room, nothing kept, nothing queued
+  bool stage_room(int chunk) {
+    stage.clear(); stage.resize(c->slabs.size());
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      if (hipSetDevice(s.dev) != hipSuccess || !device_room(&stage[i].p, sizeof(float) * 4 * (size_t)cells(i) * (size_t)chunk)) {
+        (void)hipGetLastError();
+        stage.clear();
+        return false;
+      }
+    }
+    return true;
+  }
+  float* staged(size_t i) const { return stage.empty() ? nullptr : (float*)stage[i].p; }
+  // the n samples a register-tile piece staged, added to the sums in step order, behind the piece on every slab's stream
+  int fold(int n) {
+    for (size_t i = 0; i < c->slabs.size(); ++i) {
+      Slab& s = c->slabs[i];
+      if (count[i] == 0) continue;
+      HIPC(hipSetDevice(s.dev));
+      hipLaunchKernelGGL(lbm::lbm_window_stats_fold, dim3(cdiv(cells(i), lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, staged(i), cells(i), n,
+                         c->p.density, sums(i));
+      HIPC(hipGetLastError());
+    }
+    return LBM_OK;
+  }
 };
 
-// The step loop split at the sample steps every, 2 every, ... m every: each piece a complete plain run_steps (the register
-// tiles may run it), after_sample(j) behind piece j < m on the stored lattice, then the tail.  Correct, not fast.
-template <class F>
-int run_split(lbm_ctx* c, int nsteps, float* av_vels, int every, int m, F after_sample) {
+// The tile pieces of run_split, for a call that tries each piece on the register tiles first, in the piece flavour
+// (RegFlavour::piece, which alone folds the last step's speed sum of a piece that is not the call's last as a whole run
+// folds it there, piece_mid -- av_vels is lbm_run's bits wherever the call is cut): a piece takes `chunk` samples, cc of
+// them where fewer are left (0: the tail).
+struct TilePieces {
+  bool on = false;                                 // would the tiles run the pieces (decided with ranks_agree)
+  int chunk = 1;
+  std::function<void(int cc, RunKind& k)> fill;    // completes the RunKind of a piece of cc samples (none: nothing to add)
+  std::function<int(int cc)> behind;               // behind a piece of cc > 0 samples that ran (none: after_sample, chunk 1)
+  int pieces = 0;                                  // on return: the pieces that ran, on the tiles or off them
+};
+
+// The step loop split at the sample steps every, 2 every, ... m every, then the tail: each piece a complete plain run_steps
+// (the register tiles may run it) with after_sample(j) behind piece j < m on the stored lattice.  Correct, not fast.
+// With tile pieces (tp) each piece is tried on the tiles first; one that gives up, or whose flavour is not resident, has
+// stepped nothing: the plain piece from the same `done`, and plain pieces for the rest of the call.
+template <class After>
+int run_split(lbm_ctx* c, int nsteps, float* av_vels, int every, int m, After after_sample, TilePieces* tp = nullptr) {
   double gpu_ms = 0.0, wall_ms = 0.0;
-  int done = 0, rc;
-  for (int j = 0; j <= m; ++j) {
-    const int n = (j < m) ? every : nsteps - done;
-    if (n == 0) break;
-    if ((rc = run_steps(c, n, av_vels ? av_vels + done : nullptr))) return rc;
+  int done = 0, taken = 0, pieces = 0, rc;
+  bool tiles = tp && tp->on;
+  while (done < nsteps) {
+    float* av = av_vels ? av_vels + done : nullptr;
+    bool ran = false;
+    if (tiles && regtile_is_next(c)) {
+      const int cc = std::min(tp->chunk, m - taken);
+      const int n = cc > 0 ? cc * every : nsteps - done;
+      RunKind k;
+      k.flavour = RegFlavour::piece; k.piece_mid = done + n < nsteps; k.ran = &ran;
+      if (tp->fill) tp->fill(cc, k);
+      if ((rc = run_steps(c, n, av, k))) return rc;
+      tiles = ran;
+      if (ran && cc > 0 && (rc = tp->behind ? tp->behind(cc) : after_sample(taken))) return rc;
+      if (ran) { taken += cc; done += n; }
+    }
+    if (!ran) {
+      const int n = taken < m ? every : nsteps - done;
+      if ((rc = run_steps(c, n, av))) return rc;
+      done += n;
+      if (taken < m && (rc = after_sample(taken++))) return rc;
+    }
     gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
-    done += n;
-    if (j < m && (rc = after_sample(j))) return rc;
+    ++pieces;
   }
   c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  if (tp) tp->pieces = pieces;
   return LBM_OK;
 }
 
@@ -326,11 +457,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
       if (on_dev) { sp.at.push_back(fields_out + 4L * (s.row0 - base_row) * nx); sp.stride.push_back(slot); continue; }
       HIPC(hipSetDevice(s.dev));
       const size_t bytes = sizeof(float) * 4 * (size_t)m * (size_t)s.nyl * (size_t)nx;
-      if (hipMalloc(&stage[i].p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        stage[i].p = nullptr;
-        return fail(LBM_ENOMEM, "no room on device %d for %d snapshot(s) of slab %zu (%zu bytes)", s.dev, m, i, bytes);
-      }
+      if (!device_room(&stage[i].p, bytes)) return fail(LBM_ENOMEM, "no room on device %d for %d snapshot(s) of slab %zu (%zu bytes)", s.dev, m, i, bytes);
       sp.at.push_back((float*)stage[i].p); sp.stride.push_back((long)s.nyl * nx * 4);
     }
     RunKind k;
@@ -358,12 +485,11 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
     HIPC(hipSetDevice(s.dev));
     DeviceTemp stage, part;
     bool room = true;
-    if (!on_dev && hipMalloc(&stage.p, sizeof(float) * (size_t)m * (size_t)slot) != hipSuccess) { stage.p = nullptr; room = false; }
+    if (!on_dev && !device_room(&stage.p, sizeof(float) * (size_t)m * (size_t)slot)) room = false;
     // (lbm_derive leaves a float and a double per block, unused here; the partial-sum buffers are busy during a run)
     const size_t nblk = (size_t)cdiv((long)s.nyl * nx, lbm::kBlock);
-    if (room && hipMalloc(&part.p, (sizeof(double) + sizeof(float)) * nblk) != hipSuccess) { part.p = nullptr; room = false; }
-    if (!room) (void)hipGetLastError();
-    else {
+    if (room && !device_room(&part.p, (sizeof(double) + sizeof(float)) * nblk)) room = false;
+    if (room) {
       RunKind k;
       k.no_tiles = true; k.wave.fout = on_dev ? fields_out : (float*)stage.p; k.wave.fevery = every; k.wave.fstride = slot;
       k.wave.fmass = (double*)part.p; k.wave.fpart = (float*)(k.wave.fmass + nblk);
@@ -417,9 +543,8 @@ extern "C" int lbm_set_bodies(lbm_ctx* c, const int* body, int nbodies) {
     std::vector<int2> dev(s.fcells_host.size());
     for (size_t j = 0; j < dev.size(); ++j)
       dev[j] = int2{s.fcells_host[j].y * s.pitch + s.fcells_host[j].x, s.fcells_host[j].z};
-    if (hipMalloc((void**)&s.fcells, sizeof(int2) * dev.size()) != hipSuccess) {
-      (void)hipGetLastError();
-      s.fcells = nullptr; s.fcells_host.clear(); c->nbodies = 0;
+    if (!device_room((void**)&s.fcells, sizeof(int2) * dev.size())) {
+      s.fcells_host.clear(); c->nbodies = 0;
       return fail(LBM_ENOMEM, "no room on device %d for %zu body cells", s.dev, dev.size());
     }
     HIPC(hipMemcpy(s.fcells, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
@@ -467,7 +592,7 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
   c->mean_in_kernel = 0; c->mean_in_wave = 0;
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
-  MeanOut mo(c);
+  CellSums mo(c, 4);
   int rc;
   if ((rc = mo.locate(mean_out, "mean_out"))) return rc;
   rc = mo.prepare();
@@ -511,7 +636,7 @@ extern "C" int lbm_run_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, 
   c->stats_in_wave = 0;
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
-  MeanOut mo(c, 8);
+  CellSums mo(c, 8);
   int rc;
   if ((rc = mo.locate(stats_out, "stats_out"))) return rc;
   rc = mo.prepare();
@@ -537,25 +662,9 @@ extern "C" int lbm_run_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, 
   // and for its reason: the piece flavour with neither observer wanted (RegFlavour::piece), which alone folds the last
   // step's speed sums of a piece that is not the call's last as a whole run folds them there (piece_mid) -- plain launches
   // would move the last bit of av_vels at every cut.  A flavour that cannot be resident: plain pieces from there on.
-  double gpu_ms = 0.0, wall_ms = 0.0;
-  int done = 0;
-  for (int j = 0; j <= m; ++j) {
-    const int n = (j < m) ? every : nsteps - done;
-    if (n == 0) break;
-    float* av = av_vels ? av_vels + done : nullptr;
-    bool ran = false;
-    if (tiles && regtile_is_next(c)) {
-      RunKind k;
-      k.flavour = RegFlavour::piece; k.piece_mid = done + n < nsteps; k.ran = &ran;
-      if ((rc = run_steps(c, n, av, k))) return rc;
-      tiles = ran;                                    // (nothing stepped: this piece and the rest as plain runs)
-    }
-    if (!ran && (rc = run_steps(c, n, av))) return rc;
-    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
-    done += n;
-    if (j < m && (rc = mo.add())) return rc;
-  }
-  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
+  TilePieces tp;
+  tp.on = tiles;
+  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int) { return mo.add(); }, &tp))) return rc;
   return mo.finish(m);
 }
 
@@ -590,11 +699,7 @@ extern "C" int lbm_set_probes(lbm_ctx* c, const int* xy, int nprobes) {
     std::vector<int2> dev(lists[k].size());
     for (size_t j = 0; j < dev.size(); ++j) dev[j] = int2{lists[k][j].y * s.pitch + lists[k][j].x, lists[k][j].z};
     HIPC(hipSetDevice(s.dev));
-    if (hipMalloc(&fresh[k].p, sizeof(int2) * dev.size()) != hipSuccess) {
-      (void)hipGetLastError();
-      fresh[k].p = nullptr;
-      return fail(LBM_ENOMEM, "no room on device %d for %zu probe cells", s.dev, dev.size());
-    }
+    if (!device_room(&fresh[k].p, sizeof(int2) * dev.size())) return fail(LBM_ENOMEM, "no room on device %d for %zu probe cells", s.dev, dev.size());
     HIPC(hipMemcpy(fresh[k].p, dev.data(), sizeof(int2) * dev.size(), hipMemcpyHostToDevice));
   }
   for (size_t k = 0; k < ns; ++k) {
@@ -652,10 +757,7 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
   // ---- the step loop split at the sample steps: each piece a complete run, then the probes' cells of the stored lattice
   // gathered into row j
   if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int j) { return po.gather(j); }))) return rc;
-  for (auto& s : c->slabs) {
-    HIPC(hipSetDevice(s.dev));
-    HIPC(hipStreamSynchronize(s.sc));
-  }
+  if ((rc = wait_slabs(c))) return rc;
   return po.to_host();
 }
 
@@ -694,30 +796,6 @@ extern "C" int lbm_window_rows(const lbm_window* w, int nx, int ny, int row_begi
 
 namespace {
 
-// the window cells of a slab's stored lattice into out4 = float[count][w.nx][4]: the slab's window rows first .. first + count - 1
-int launch_derive_window(const lbm_ctx* c, Slab& s, const lbm_window& w, int first, int count, float* out4) {
-  if (count <= 0) return LBM_OK;
-  const long ncell = (long)count * w.nx;
-  const long yl0 = (long)w.y0 + (long)first * w.sy - s.row0;
-  HIPC(hipSetDevice(s.dev));
-  hipLaunchKernelGGL(lbm::lbm_derive_window, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
-                     w.x0, w.nx > 1 ? w.sx : 1, w.nx, (int)yl0, count > 1 ? w.sy : 1, ncell, s.blocked, c->p.density, out4);
-  HIPC(hipGetLastError());
-  return LBM_OK;
-}
-
-// ... and, for lbm_run_window_stats, added with their products to acc8 = float[count][w.nx][8], the sums of those rows
-int launch_window_stats_add(const lbm_ctx* c, Slab& s, const lbm_window& w, int first, int count, float* acc8) {
-  if (count <= 0) return LBM_OK;
-  const long ncell = (long)count * w.nx;
-  const long yl0 = (long)w.y0 + (long)first * w.sy - s.row0;
-  HIPC(hipSetDevice(s.dev));
-  hipLaunchKernelGGL(lbm::lbm_window_stats_add, dim3(cdiv(ncell, lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, s.lat[c->cur], s.plane, s.pitch,
-                     w.x0, w.nx > 1 ? w.sx : 1, w.nx, (int)yl0, count > 1 ? w.sy : 1, ncell, s.blocked, c->p.density, acc8);
-  HIPC(hipGetLastError());
-  return LBM_OK;
-}
-
 // The window table of a slab for tiles of ty rows, fed to the probe flavour as the probe set's is: a cell's word is its place
 // among the SLAB's window rows + 1, (r - first) w.nx + c + 1 -- the slab's output pointer is its first window row's.  Kept by
 // (window, tiling); the probe set's table is not touched.  LBM_ENOMEM: nothing queued.  The key names a window only once its
@@ -738,25 +816,16 @@ int window_tables(Slab& s, int ty, int ntx, const lbm_window& w, int first, int 
 // Where one call's windows go, [m][w.ny][w.nx][4] floats.  Device output is written in place; host output goes through one
 // staging buffer per slab that holds a window row, of the slab's own window rows only -- [m][count][w.nx][4], copied out by
 // to_host -- or, where that does not fit, of ONE sample (`single`: the split path alone, copied out behind each sample).
-struct WindowOut {
+struct WindowOut : SlabRows {             // (per slab: its window rows)
   lbm_ctx* c;
   lbm_window w;
   float* out = nullptr;
   bool on_dev = false, single = false;
   int m = 0;
-  size_t wfloats = 0;                      // floats of one window
-  long local = 0;                          // window rows that the slabs of this context hold
-  std::vector<int> first, count;           // per slab: its window rows
+  size_t wfloats;                          // floats of one window
   std::vector<DeviceTemp> stage;
 
-  WindowOut(lbm_ctx* ctx, const lbm_window& win) : c(ctx), w(win) {
-    wfloats = 4 * (size_t)w.nx * (size_t)w.ny;
-    for (auto& s : c->slabs) {
-      int f = 0, n = 0;
-      (void)lbm_window_rows(&w, c->p.nx, c->p.ny, s.row0, s.row0 + s.nyl, &f, &n);
-      first.push_back(f); count.push_back(n); local += n;
-    }
-  }
+  WindowOut(lbm_ctx* ctx, const lbm_window& win) : SlabRows(ctx, &win), c(ctx), w(win), wfloats(4 * (size_t)win.nx * (size_t)win.ny) {}
   int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
   size_t slab_floats(size_t i) const { return 4 * (size_t)w.nx * (size_t)count[i]; }
   // the staging of m_ samples, or of one (LBM_ENOMEM: nothing queued, nothing kept)
@@ -768,25 +837,12 @@ struct WindowOut {
       if (on_dev || count[i] == 0) continue;
       const size_t bytes = sizeof(float) * slab_floats(i) * (size_t)(one ? 1 : m);
       HIPC(hipSetDevice(s.dev));
-      if (hipMalloc(&stage[i].p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        stage[i].p = nullptr;
-        return fail(LBM_ENOMEM, "no room on device %d for %d window(s) of slab %zu (%zu bytes)", s.dev, one ? 1 : m, i, bytes);
-      }
+      if (!device_room(&stage[i].p, bytes)) return fail(LBM_ENOMEM, "no room on device %d for %d window(s) of slab %zu (%zu bytes)", s.dev, one ? 1 : m, i, bytes);
     }
     return LBM_OK;
   }
   // the window rows of other ranks' lattice rows read +0.0f
-  int zero_foreign() {
-    if (local >= w.ny) return LBM_OK;
-    if (on_dev) {
-      Slab& s = c->slabs[0];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(out, 0, sizeof(float) * wfloats * (size_t)m, s.sc));
-      HIPC(hipStreamSynchronize(s.sc));
-    } else memset(out, 0, sizeof(float) * wfloats * (size_t)m);
-    return LBM_OK;
-  }
+  int zero_foreign() { return local >= w.ny ? LBM_OK : zero_output(c, out, sizeof(float) * wfloats * (size_t)m, on_dev); }
   // where slab i's first window row of sample j goes (a slab without a window row stores nothing: NULL), and the floats
   // from one sample to the next there
   long stride(size_t i) const { return on_dev ? (long)wfloats : (long)slab_floats(i); }
@@ -800,7 +856,7 @@ struct WindowOut {
   int derive(int j) {
     int rc;
     for (size_t i = 0; i < c->slabs.size(); ++i)
-      if ((rc = launch_derive_window(c, c->slabs[i], w, first[i], count[i], at(i, j)))) return rc;
+      if ((rc = launch_window(c, c->slabs[i], w, first[i], count[i], at(i, j), false))) return rc;
     if (!single || on_dev) return LBM_OK;
     for (size_t i = 0; i < c->slabs.size(); ++i) {
       Slab& s = c->slabs[i];
@@ -813,11 +869,11 @@ struct WindowOut {
   }
   // every slab's stream waited for, and what was staged into the caller's array
   int finish() {
+    int rc;
+    if ((rc = wait_slabs(c))) return rc;
     for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipStreamSynchronize(s.sc));
       if (on_dev || single || count[i] == 0) continue;
+      HIPC(hipSetDevice(c->slabs[i].dev));
       const size_t wbytes = sizeof(float) * slab_floats(i);
       if (count[i] == w.ny) HIPC(hipMemcpy(out, stage[i].p, wbytes * (size_t)m, hipMemcpyDeviceToHost));
       else HIPC(hipMemcpy2D(host_at(i, 0), sizeof(float) * wfloats, stage[i].p, wbytes, wbytes, (size_t)m, hipMemcpyDeviceToHost));
@@ -897,136 +953,6 @@ extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every,
 }
 
 // ----------------------------------------------------------------- stats over a window (lbm_run_window_stats; DESIGN.md 3.20)
-namespace {
-
-// The staging bound of the register-tile path: the most bytes of staged samples one slab holds at a time.  Scratch-memory
-// policy, not a tuned number (DESIGN.md 3.20): 64 MiB is four samples of the largest window a register-tile lattice has
-// (1024 x 1024 cells, 16 MiB a sample) and thousands of a wake window's.
-constexpr size_t kWindowStatsStageBytes = 64u << 20;
-
-// Where one call's sums over a window live and go: per slab that holds a window row, the sums of its own window rows,
-// float[count][w.nx][8] -- 32 bytes per window cell of the slab, on every path -- and, on the register tiles, the staging of
-// one piece's samples, float[chunk][count][w.nx][4].  The output is [w.ny][w.nx][8]: device output is written in place by
-// the divide, host output is the sums divided in place and copied out.
-struct WindowStats {
-  lbm_ctx* c;
-  lbm_window w;
-  float* out = nullptr;
-  bool on_dev = false;
-  long local = 0;                          // window rows that the slabs of this context hold
-  std::vector<int> first, count;           // per slab: its window rows
-  std::vector<DeviceTemp> acc, stage;
-
-  WindowStats(lbm_ctx* ctx, const lbm_window& win) : c(ctx), w(win) {
-    for (auto& s : c->slabs) {
-      int f = 0, n = 0;
-      (void)lbm_window_rows(&w, c->p.nx, c->p.ny, s.row0, s.row0 + s.nyl, &f, &n);
-      first.push_back(f); count.push_back(n); local += n;
-    }
-  }
-  int locate(float* o, const char* what) { out = o; return output_on_device(c, o, what, &on_dev); }
-  long cells(size_t i) const { return (long)count[i] * w.nx; }
-  size_t bytes(size_t i) const { return sizeof(float) * 8 * (size_t)cells(i); }
-  // the slabs' sums (LBM_ENOMEM: nothing queued; the caller hands it to ranks_agree)
-  int prepare() {
-    acc.resize(c->slabs.size());
-    for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      if (count[i] == 0) continue;
-      HIPC(hipSetDevice(s.dev));
-      if (hipMalloc(&acc[i].p, bytes(i)) != hipSuccess) {
-        (void)hipGetLastError();
-        acc[i].p = nullptr;
-        return fail(LBM_ENOMEM, "no room on device %d for the window sums of slab %zu (%zu bytes)", s.dev, i, bytes(i));
-      }
-    }
-    return LBM_OK;
-  }
-  // the most samples a piece may stage under the bound: at least 1, at most m
-  int auto_chunk(int m) const {
-    size_t per = 0;                          // bytes of one sample of the slab with the most window cells
-    for (size_t i = 0; i < c->slabs.size(); ++i) per = std::max(per, sizeof(float) * 4 * (size_t)cells(i));
-    const size_t fit = per ? kWindowStatsStageBytes / per : (size_t)m;
-    return (int)std::min<size_t>((size_t)m, std::max<size_t>(1, fit));
-  }
-  // the staging of `chunk` samples on every slab that holds a window row; false: no room, nothing kept, nothing queued
-  bool stage_room(int chunk) {
-    stage.clear(); stage.resize(c->slabs.size());
-    for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      if (count[i] == 0) continue;
-      if (hipSetDevice(s.dev) != hipSuccess || hipMalloc(&stage[i].p, sizeof(float) * 4 * (size_t)cells(i) * (size_t)chunk) != hipSuccess) {
-        (void)hipGetLastError();
-        stage[i].p = nullptr;
-        stage.clear();
-        return false;
-      }
-    }
-    return true;
-  }
-  int clear() {
-    for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      if (count[i] == 0) continue;
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(acc[i].p, 0, bytes(i), s.sc));
-    }
-    return LBM_OK;
-  }
-  // the window rows of other ranks' lattice rows read +0.0f
-  int zero_foreign() {
-    if (local >= w.ny) return LBM_OK;
-    const size_t all = sizeof(float) * 8 * (size_t)w.nx * (size_t)w.ny;
-    if (on_dev) {
-      Slab& s = c->slabs[0];
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipMemsetAsync(out, 0, all, s.sc));
-      HIPC(hipStreamSynchronize(s.sc));
-    } else memset(out, 0, all);
-    return LBM_OK;
-  }
-  float* sums(size_t i) const { return (float*)acc[i].p; }
-  float* staged(size_t i) const { return stage.empty() ? nullptr : (float*)stage[i].p; }
-  float* out_rows(size_t i) const { return out + 8 * (size_t)first[i] * (size_t)w.nx; }
-  // the window cells of the stored lattice and their products added to the sums, on every slab that holds a window row
-  int add() {
-    int rc;
-    for (size_t i = 0; i < c->slabs.size(); ++i)
-      if ((rc = launch_window_stats_add(c, c->slabs[i], w, first[i], count[i], sums(i)))) return rc;
-    return LBM_OK;
-  }
-  // the n samples a register-tile piece staged, added to the sums in step order, behind the piece on every slab's stream
-  int fold(int n) {
-    for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      if (count[i] == 0) continue;
-      HIPC(hipSetDevice(s.dev));
-      hipLaunchKernelGGL(lbm::lbm_window_stats_fold, dim3(cdiv(cells(i), lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, staged(i), cells(i), n,
-                         c->p.density, sums(i));
-      HIPC(hipGetLastError());
-    }
-    return LBM_OK;
-  }
-  // the sums of m samples divided into their place (lbm_mean_div: IEEE division, as lbm_run_stats finishes), every slab's
-  // stream waited for, host output copied out
-  int finish(int m) {
-    for (size_t i = 0; i < c->slabs.size(); ++i) {
-      Slab& s = c->slabs[i];
-      HIPC(hipSetDevice(s.dev));
-      if (count[i] > 0) {
-        hipLaunchKernelGGL(lbm::lbm_mean_div, dim3(cdiv(2 * cells(i), lbm::kBlock)), dim3(lbm::kBlock), 0, s.sc, sums(i), 2 * cells(i), (float)m,
-                           on_dev ? out_rows(i) : sums(i));
-        HIPC(hipGetLastError());
-      }
-      HIPC(hipStreamSynchronize(s.sc));
-      if (count[i] > 0 && !on_dev) HIPC(hipMemcpy(out_rows(i), sums(i), bytes(i), hipMemcpyDeviceToHost));
-    }
-    return LBM_OK;
-  }
-};
-
-}  // namespace
-
 extern "C" int lbm_run_window_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, const lbm_window* win, float* stats_out) {
   // (the three pointers first, each on its own: none of them is optional, whatever the other arguments say)
   if (!win) return fail(LBM_EINVAL, "win is NULL");
@@ -1041,7 +967,7 @@ extern "C" int lbm_run_window_stats(lbm_ctx* c, int nsteps, float* av_vels, int 
   WinPlan plan;
   plan.w = *win;
   const bool wave_exact = window_for_wave(plan.w, &plan.wave);
-  WindowStats ws(c, plan.w);
+  CellSums ws(c, 8, &plan.w);
   if ((rc = ws.locate(stats_out, "stats_out"))) return rc;
   c->window_stats_in_wave = 0; c->window_stats_in_kernel = 0; c->window_stats_pieces = 0;
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
@@ -1074,41 +1000,15 @@ extern "C" int lbm_run_window_stats(lbm_ctx* c, int nsteps, float* av_vels, int 
   // stores the piece's samples into the slab's staging, lbm_window_stats_fold adds them to the sums behind it; the steps
   // past m every run as one more piece without samples.  A piece that gives up, or whose flavour is not resident, has
   // stepped nothing: from the same step on, and everywhere else, pieces of `every` steps with lbm_window_stats_add behind each.
-  double gpu_ms = 0.0, wall_ms = 0.0;
-  int done = 0, taken = 0, pieces = 0;
-  while (done < nsteps) {
-    float* av = av_vels ? av_vels + done : nullptr;
-    if (tiles && regtile_is_next(c)) {
-      const int cc = std::min(chunk, m - taken);            // (0: the tail behind the last sample step)
-      const int n = cc > 0 ? cc * every : nsteps - done;
-      SnapPlan sp;
-      sp.every = every;
-      for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(ws.staged(i)); sp.stride.push_back(4 * ws.cells(i)); }
-      bool ran = false;
-      RunKind k;
-      k.flavour = RegFlavour::piece; k.piece_mid = done + n < nsteps; k.ran = &ran;
-      if (cc > 0) { k.snap = &sp; k.pfirst = every; k.win_table = true; }
-      if ((rc = run_steps(c, n, av, k))) return rc;
-      if (!ran) { tiles = false; continue; }                // (nothing stepped: this piece again, on the split path)
-      if (cc > 0) {
-        if ((rc = ws.fold(cc))) return rc;
-        c->window_stats_in_kernel = 1;
-      }
-      taken += cc; done += n;
-    } else {
-      const int n = taken < m ? every : nsteps - done;
-      if ((rc = run_steps(c, n, av))) return rc;
-      done += n;
-      if (taken < m) {
-        if ((rc = ws.add())) return rc;
-        ++taken;
-      }
-    }
-    gpu_ms += c->gpu_ms; wall_ms += c->wall_ms;
-    ++pieces;
-  }
-  c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
-  c->window_stats_pieces = pieces;
+  SnapPlan sp;
+  sp.every = every;
+  for (size_t i = 0; i < c->slabs.size(); ++i) { sp.at.push_back(ws.staged(i)); sp.stride.push_back(4 * ws.cells(i)); }
+  TilePieces tp;
+  tp.on = tiles; tp.chunk = chunk;
+  tp.fill = [&](int cc, RunKind& k) { if (cc > 0) { k.snap = &sp; k.pfirst = every; k.win_table = true; } };
+  tp.behind = [&](int cc) { const int r = ws.fold(cc); if (!r) c->window_stats_in_kernel = 1; return r; };
+  if ((rc = run_split(c, nsteps, av_vels, every, m, [&](int) { return ws.add(); }, &tp))) return rc;
+  c->window_stats_pieces = tp.pieces;
   return ws.finish(m);
 }
 
@@ -1144,7 +1044,7 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
   if (msn == 0) ws = false;                               // (no snapshot is due: legal, nothing written, as lbm_run_sampled)
   if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
   ProbeOut po(c);
-  MeanOut mo(c);
+  CellSums mo(c, 4);
   bool s_dev = false;
   int rc;
   if (wp && (rc = po.locate(what->probes_out, "probes_out"))) return rc;
@@ -1271,12 +1171,7 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
     }
   }
   // ---- the means, and what was staged for the host
-  if (wm) { if ((rc = mo.finish(mm))) return rc; }
-  else
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      HIPC(hipStreamSynchronize(s.sc));
-    }
+  if ((rc = wm ? mo.finish(mm) : wait_slabs(c))) return rc;
   if (wp && (rc = po.to_host())) return rc;
   c->gpu_ms = gpu_ms; c->wall_ms = wall_ms;
   // (under a schedule the three keys read 0 where the whole call took the one-step path)

@@ -1086,6 +1086,38 @@ __device__ __forceinline__ f4a derive_cell(const float (&f)[9], bool blocked, fl
   return v;
 }
 
+// The eight terms a sample adds to a cell's sums in lbm_run_stats: the four fields, and u_x^2, u_y^2, u_x u_y, (p - p0)^2 with
+// p0 = density * (1.f / 3.f), the pressure a blocked cell reads.  One rounding per operation: callers keep contraction off.
+// Shared by lbm_stats_add and lbm_wave's stats flavour, which must agree bit for bit.
+__device__ __forceinline__ f4a stats_products(const f4a v, float density) {
+#pragma clang fp contract(off)
+  const float d = v.w - density * (1.f / 3.f);
+  f4a q; q.x = v.x * v.x; q.y = v.y * v.y; q.z = v.x * v.y; q.w = d * d;
+  return q;
+}
+
+// What the observer kernels share, so that the sums of every engine agree bit for bit from ONE copy of the arithmetic (the
+// small kernels below, lbm_wave's field, stats and window flavours; the register tiles keep their own mean adds).
+// rec += v, a record of four floats in registers or in memory (one 16-byte load, one 16-byte store): one rounding per add
+__device__ __forceinline__ void add4(f4a& rec, const f4a v) {
+#pragma clang fp contract(off)
+  f4a s = rec;
+  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
+  rec = s;
+}
+// a sample added to a record of eight floats: the fields to its first half, then their products (stats_products) to its second
+__device__ __forceinline__ void stats_add8(f4a& fields, f4a& products, const f4a v, float density) {
+#pragma clang fp contract(off)
+  add4(fields, v);
+  add4(products, stats_products(v, density));
+}
+// the plane offset of cell t of a slab's window rows: nrows rows of wnx cells, cell (r, c) at row yl0 + r sy (the slab's
+// numbering), column x0 + c sx
+__device__ __forceinline__ long window_offset(long t, int wnx, int x0, int sx, int yl0, int sy, int pitch) {
+  const long r = t / wnx; const int cc = (int)(t - r * wnx);
+  return ((long)yl0 + r * sy) * pitch + ((long)x0 + (long)cc * sx);
+}
+
 // Momentum a blocked cell takes from the fluid in one step (lbm_run_forces), halved: sum over the directions i of the mask
 // (bit i-1: the source cell B - c_i is fluid) of c_i f~_i, where f~_i, the population B pulled along i, sits in p[opp(i)]
 // once collide_cell has mirrored it -- and in plane opp(i) of the stored lattice.  Shared by the register tiles and
@@ -1212,18 +1244,7 @@ __global__ __launch_bounds__(kBlock) void lbm_mean_add(const float* lat, long pl
   for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
   float rho;
   const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
-  f4a s = *reinterpret_cast<const f4a*>(acc4 + 4 * c);
-  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-  *reinterpret_cast<f4a*>(acc4 + 4 * c) = s;
-}
-// The eight terms a sample adds to a cell's sums in lbm_run_stats: the four fields, and u_x^2, u_y^2, u_x u_y, (p - p0)^2 with
-// p0 = density * (1.f / 3.f), the pressure a blocked cell reads.  One rounding per operation: callers keep contraction off.
-// Shared by lbm_stats_add and lbm_wave's stats flavour, which must agree bit for bit.
-__device__ __forceinline__ f4a stats_products(const f4a v, float density) {
-#pragma clang fp contract(off)
-  const float d = v.w - density * (1.f / 3.f);
-  f4a q; q.x = v.x * v.x; q.y = v.y * v.y; q.z = v.x * v.y; q.w = d * d;
-  return q;
+  add4(*reinterpret_cast<f4a*>(acc4 + 4 * c), v);
 }
 // lbm_run_stats on every engine but lbm_wave's stats flavour: lbm_mean_add with records of eight floats -- the fields of the
 // stored lattice added to acc8[cell][0..3], their products (stats_products) to acc8[cell][4..7]; two 16-byte loads and two
@@ -1240,14 +1261,8 @@ __global__ __launch_bounds__(kBlock) void lbm_stats_add(const float* lat, long p
   for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
   float rho;
   const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
-  const f4a q = stats_products(v, density);
   f4a* at = reinterpret_cast<f4a*>(acc8 + 8 * c);
-  f4a s = at[0];
-  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-  at[0] = s;
-  f4a t = at[1];
-  t.x = t.x + q.x; t.y = t.y + q.y; t.z = t.z + q.z; t.w = t.w + q.w;
-  at[1] = t;
+  stats_add8(at[0], at[1], v, density);
 }
 // ... and after the last piece: out4[cell] = acc4[cell] / m (IEEE division; out4 may be acc4).  lbm_run_stats: its sums as
 // 2 ncell float4s.
@@ -1288,8 +1303,7 @@ __global__ __launch_bounds__(kBlock) void lbm_derive_window(const float* lat, lo
 #pragma clang fp contract(off)
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ncell) return;
-  const long r = t / wnx; const int cc = (int)(t - r * wnx);
-  const long o = ((long)yl0 + r * sy) * pitch + ((long)x0 + (long)cc * sx);
+  const long o = window_offset(t, wnx, x0, sx, yl0, sy, pitch);
   float f[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
@@ -1308,21 +1322,14 @@ __global__ __launch_bounds__(kBlock) void lbm_window_stats_add(const float* lat,
 #pragma clang fp contract(off)
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ncell) return;
-  const long r = t / wnx; const int cc = (int)(t - r * wnx);
-  const long o = ((long)yl0 + r * sy) * pitch + ((long)x0 + (long)cc * sx);
+  const long o = window_offset(t, wnx, x0, sx, yl0, sy, pitch);
   float f[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) f[k] = lat[k * plane + o];
   float rho;
   const f4a v = derive_cell(f, blocked[o] != 0, density, rho);
-  const f4a q = stats_products(v, density);
   f4a* at = reinterpret_cast<f4a*>(acc8 + 8 * t);
-  f4a s = at[0];
-  s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-  at[0] = s;
-  f4a u = at[1];
-  u.x = u.x + q.x; u.y = u.y + q.y; u.z = u.z + q.z; u.w = u.w + q.w;
-  at[1] = u;
+  stats_add8(at[0], at[1], v, density);
 }
 
 // lbm_run_window_stats on the register tiles: behind a piece that stored its nsamples samples of the slab's window rows
@@ -1338,9 +1345,9 @@ __global__ __launch_bounds__(kBlock) void lbm_window_stats_fold(const float* sta
   f4a s = at[0], u = at[1];
   for (int j = 0; j < nsamples; ++j) {
     const f4a v = *reinterpret_cast<const f4a*>(stage4 + 4 * ((long)j * ncell + t));
-    const f4a q = stats_products(v, density);
-    s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-    u.x = u.x + q.x; u.y = u.y + q.y; u.z = u.z + q.z; u.w = u.w + q.w;
+    const f4a q = stats_products(v, density);      // (the record's adds, the products taken first: the order this kernel is built from)
+    add4(s, v);
+    add4(u, q);
   }
   at[0] = s;
   at[1] = u;

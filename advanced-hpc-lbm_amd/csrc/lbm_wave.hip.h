@@ -33,6 +33,13 @@ struct WaveWin {
   unsigned sx, sy, xlast, ylast, mx, my;
 };
 
+// is lattice column x a window column (q: which)?  A column left of the window wraps past xlast.
+__device__ __forceinline__ bool window_col(const WaveWin& w, int x, unsigned& q) {
+  const unsigned cx = (unsigned)(x - w.x0);
+  q = w.sx == 1u ? cx : __umulhi(cx, w.mx);
+  return cx <= w.xlast && q * w.sx == cx;
+}
+
 struct WaveArgs {
   const float* src;            // lattice at step t (accelerate phase of step t+1 already applied)
   float* dst;                  // lattice at step t+K
@@ -339,13 +346,8 @@ void lbm_wave(const WaveArgs a) {
             float rho;
             const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
             f4a* at = reinterpret_cast<f4a*>(o + 4 * c);
-            if (a.fadd != 0) {                   // (wave-uniform) the sums of a mean: one rounding per add, the order of the steps
-              f4a s = *at;
-              s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-              *at = s;
-            } else {
-              *at = v;
-            }
+            if (a.fadd != 0) add4(*at, v);       // (wave-uniform) the sums of a mean: one rounding per add, the order of the steps
+            else *at = v;
           }
         }
       }
@@ -361,13 +363,7 @@ void lbm_wave(const WaveArgs a) {
             float rho;
             const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
             f4a* at = reinterpret_cast<f4a*>(o + 8 * c);
-            f4a s = at[0];                       // (one rounding per add, the order of the steps; plain same-thread accesses)
-            s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-            at[0] = s;
-            const f4a q = stats_products(v, a.density);
-            f4a t = at[1];
-            t.x = t.x + q.x; t.y = t.y + q.y; t.z = t.z + q.z; t.w = t.w + q.w;
-            at[1] = t;
+            stats_add8(at[0], at[1], v, a.density);   // (one rounding per add, the order of the steps; plain same-thread accesses)
           }
         }
       }
@@ -381,21 +377,21 @@ void lbm_wave(const WaveArgs a) {
           if (r * a.win.sy == ry && out_ok) {
 #pragma clang fp contract(off)
             float* o = a.fout + (long)__builtin_popcount(a.fmask & ((1u << (l - 1)) - 1u)) * a.fstride + 4 * (long)r * a.win.nx;
+            unsigned q;
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-              const unsigned cx = (unsigned)(X0 - K + C * lane + c - a.win.x0);
-              const unsigned q = a.win.sx == 1u ? cx : __umulhi(cx, a.win.mx);
-              if (cx <= a.win.xlast && q * a.win.sx == cx) {
+            for (int c = 0; c < C; ++c)
+              if (window_col(a.win, X0 - K + C * lane + c, q)) {
                 float rho;
                 const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
                 *reinterpret_cast<f4a*>(o + 4 * (long)q) = v;
               }
-            }
           }
         }
       }
     };
-    // WINDOW and STATS, at a sample level behind collide_cell(s): the window's cells of the level's row into their records of the sums
+    // WINDOW and STATS, at a sample level behind collide_cell(s): the window's cells of the level's row into their records of
+    // the sums.  (The row test stands here a second time: written once, as a function beside window_col, it moves the
+    // instruction text of every window flavour.)
     [[maybe_unused]] auto store_window_stats = [&](int l, int j, const float (&p)[C][9], bool own_row, bool out_ok) {
       if (own_row && ((a.fmask >> (l - 1)) & 1u) != 0u) {       // (wave-uniform)
         const unsigned ry = (unsigned)(S0 + j - l - a.win.y0);  // (a row below the window wraps past ylast)
@@ -403,23 +399,15 @@ void lbm_wave(const WaveArgs a) {
           const unsigned r = a.win.sy == 1u ? ry : __umulhi(ry, a.win.my);
           if (r * a.win.sy == ry && out_ok) {
 #pragma clang fp contract(off)
+            unsigned q;
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-              const unsigned cx = (unsigned)(X0 - K + C * lane + c - a.win.x0);
-              const unsigned q = a.win.sx == 1u ? cx : __umulhi(cx, a.win.mx);
-              if (cx <= a.win.xlast && q * a.win.sx == cx) {
+            for (int c = 0; c < C; ++c)
+              if (window_col(a.win, X0 - K + C * lane + c, q)) {
                 float rho;
                 const f4a v = derive_cell(p[c], ((mreg[c] >> l) & 1u) != 0u, a.density, rho);
                 f4a* at = reinterpret_cast<f4a*>(a.fout + 8 * ((long)r * a.win.nx + (long)q));
-                f4a s = at[0];                   // (one rounding per add, the order of the steps; plain same-thread accesses)
-                s.x = s.x + v.x; s.y = s.y + v.y; s.z = s.z + v.z; s.w = s.w + v.w;
-                at[0] = s;
-                const f4a pr = stats_products(v, a.density);
-                f4a t = at[1];
-                t.x = t.x + pr.x; t.y = t.y + pr.y; t.z = t.z + pr.z; t.w = t.w + pr.w;
-                at[1] = t;
+                stats_add8(at[0], at[1], v, a.density);   // (one rounding per add, the order of the steps; plain same-thread accesses)
               }
-            }
           }
         }
       }

@@ -9,7 +9,7 @@ p0_apart), but 0.02 is "light_fluid" alone, which runs from rest for 16 steps at
 smooth, perturbed run of the grid can tell a kernel that divides from one that multiplies.  At 0.3 the two differ by one ulp,
 which changes the bits of every (p - p0)^2 and makes a blocked cell's float 7 non-zero
 (test_thirds_tells_the_two_forms_of_p0_and_the_densities_apart).
-The density itself reaches p0 through WaveArgs::density and the argument of launch_stats_add: a site that kept 0.1 passes
+The density itself reaches p0 through WaveArgs::density and the argument of launch_cell_add: a site that kept 0.1 passes
 every stats test at the control point, and none of the four densities here.  "thirds" is not a point of PARAM_GRID and has
 no golden file: its state is param_state's "perturbed" recipe from the local triple (thirds_state; held to param_state bit
 for bit at a grid point).  On the strict float oracle, seed 7, it stays far inside the tameness condition over 30 steps

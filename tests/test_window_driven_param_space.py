@@ -3,7 +3,7 @@ the 80 (path, point) cases of tests/test_observer_param_space.py -- every observ
 density is not 0.1 and where the accelerate guard refuses part of row ny-2 inside a pass.
 
 Until this module every test of these calls ran at density 0.1 and omega 1.85.  The density reaches a window through
-launch_derive_window, the window flavour of lbm_wave and the register tiles' probe flavour fed window tables; a schedule
+launch_window, the window flavour of lbm_wave and the register tiles' probe flavour fed window tables; a schedule
 reaches the lattice through accel_pair(density, accel[t]), once per call for the register tiles, per pass for lbm_wave and
 per step behind the last pass.  A site that kept 0.1 passes every test at the control point; a flavour that reads pair
 t +- 1, or the context's own pair, changes lattice bits only where the guard's decision flips ("refusal", "light_fluid").

@@ -4,7 +4,7 @@ tests/test_window_driven_param_space.py (windows_of: the whole extent at strides
 across a column edge and a row edge of the path).
 
 What the call's own files cannot see (they run at density 0.1, omega 1.85 and the decks' acceleration).  The density reaches
-p0 in three places of its own: the argument of launch_window_stats_add (the split paths), the argument of
+p0 in three places of its own: the argument of launch_window (the split paths), the argument of
 lbm_window_stats_fold (the register tiles) and WaveArgs::density of lbm_wave's WINDOW+STATS flavour.  A site that kept 0.1
 passes every test at the control point; one that formed p0 as density / 3.f passes wherever that is the float
 density * (1.f / 3.f), which is every density of the grid that a smooth run has.  At "thirds" the two differ by one ulp:
