@@ -12,8 +12,14 @@
 //     the interior launch it overlaps (events join the streams); peer copies
 //     inside one process; or peer-to-peer -- the edge tiles of ONE launch per
 //     group store straight into the neighbour's halo block over xGMI and hand
-//     off through flags polled in-kernel (run_p2p: no events, no host-side
-//     exchange, no collective in the loop);
+//     off through flags polled in-kernel (no events, no host-side exchange,
+//     no collective in the loop);
+//   * ONE step loop, run_steps, for all of them: prologue, groups of K steps,
+//     pairs, single steps, the fold of the last launch's sums.  The transport
+//     is a branch inside each launch group (lbm_host_march.inc), and the parts
+//     every group needs -- kernel arguments, the accelerate and fold launches,
+//     the layout of slabs and halo blocks -- stand once (lbm_host_slabs.inc,
+//     lbm_host_march.inc);
 //   * no host synchronisation inside the step loop; per-step speed sums stay
 //     on the device (one double per step and slab, folded from per-block
 //     partials by block 0 of the NEXT launch) and are reduced once at the end
@@ -335,6 +341,22 @@ static std::vector<float> accel_pairs(const lbm_ctx* c, const float* accel, int 
   }
   return pairs;
 }
+// The accelerate constants of one run of the step loop: the context's pair, or under a schedule (RunKind::drive; nullptr:
+// none) every step's own.
+struct AccelRun {
+  AccelPair ctx;
+  const float* drive;
+  AccelPair pair(int t) const { return drive ? AccelPair{drive[2 * t], drive[2 * t + 1]} : ctx; }   // of step t (0-based) of the run
+  // what the launch of step t hands its kernel: the rows a step writes carry the NEXT step's accelerate phase; behind the
+  // run's last step there is none (and no entry: the context's pair, which the kernel does not apply)
+  AccelPair after(int t, int nsteps) const { return t == nsteps - 1 ? ctx : pair(t + 1); }
+};
+
+// A context whose peer-to-peer halo wait timed out holds no defined lattice: every call that would step, read or write it
+// refuses through here.
+static int refuse_failed(const lbm_ctx* c) {
+  return c->p2p_failed ? fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined") : LBM_OK;
+}
 
 #include "lbm_host_slabs.inc"
 
@@ -426,9 +448,8 @@ int p2p_connect_ipc(lbm_ctx* c, const char* handles, int nranks) {
   char* blocks[2] = {s.peer_s, s.peer_n};
   for (int side = 0; side < 2; ++side) {
     const int r = nbr[side];
-    const int r0 = (int)((long)r * c->p.ny / nranks), nyl = (int)((long)(r + 1) * c->p.ny / nranks) - r0;
-    s.nb_nyl[side] = nyl;
-    s.nb_plane[side] = (long)nyl * s.pitch + 5184;       // (slab_alloc's rule)
+    s.nb_nyl[side] = slab_rows(c->p.ny, nranks, r).nyl;
+    s.nb_plane[side] = slab_plane(s.nb_nyl[side], s.pitch);
     if (r == c->rank) {
       s.nb_lat[side][0] = s.lat[0]; s.nb_lat[side][1] = s.lat[1]; s.nb_blocked[side] = s.blocked;
     } else if (side == 1 && north == south) {
@@ -436,7 +457,7 @@ int p2p_connect_ipc(lbm_ctx* c, const char* handles, int nranks) {
       s.nb_lat[1][0] = s.nb_lat[0][0]; s.nb_lat[1][1] = s.nb_lat[0][1]; s.nb_blocked[1] = s.nb_blocked[0];
     } else {
       hipIpcMemHandle_t h[3];
-      HIPC(hipMemcpy(h, blocks[side] + 4 * s.halo_bytes + 512, sizeof(h), hipMemcpyDeviceToHost));
+      HIPC(hipMemcpy(h, blocks[side] + comm_layout(s).lattice_handles(), sizeof(h), hipMemcpyDeviceToHost));
       for (int i = 0; i < 3; ++i) {
         void* ptr = nullptr;
         hipError_t e = hipIpcOpenMemHandle(&ptr, h[i], hipIpcMemLazyEnablePeerAccess);
@@ -452,7 +473,7 @@ int p2p_connect_ipc(lbm_ctx* c, const char* handles, int nranks) {
       else {
         hipIpcMemHandle_t h, zero;
         memset(&zero, 0, sizeof(zero));
-        HIPC(hipMemcpy(&h, blocks[side] + 4 * s.halo_bytes + 512 + 192, sizeof(h), hipMemcpyDeviceToHost));
+        HIPC(hipMemcpy(&h, blocks[side] + comm_layout(s).mail_handle(), sizeof(h), hipMemcpyDeviceToHost));
         void* ptr = nullptr;
         if (memcmp(&h, &zero, sizeof(h)) != 0 && hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess) == hipSuccess) {
           s.tmail_nb[side] = (char*)ptr; s.tmail_nb_bytes[side] = regtile_mail_bytes(c); s.tmail_nb_ipc[side] = true;
@@ -474,6 +495,32 @@ int p2p_export(lbm_ctx* c, char* handle64) {
   return LBM_OK;
 }
 
+// What lbm_create and lbm_create_rank_ex ask alike, in the order in which they ask: the arguments every context needs ...
+int create_args(const lbm_param* params, const int* obstacles, lbm_ctx** out) {
+  if (!out) return fail(LBM_EINVAL, "out is NULL");
+  *out = nullptr;
+  const int rc = check_params(params);
+  if (rc) return rc;
+  if (!obstacles) return fail(LBM_EINVAL, "obstacles is NULL");
+  return LBM_OK;
+}
+// ... behind their own checks of slabs, ranks and transport: a device at all ...
+int visible_devices(int* ndev) {
+  lbm_device_count(ndev);
+  if (*ndev < 1) return fail(LBM_ENODEV, "no HIP device visible; this library has no CPU path");
+  return LBM_OK;
+}
+// ... whether a ring of one trades halos with itself (tests) ...
+bool exchange_forced() {
+  const char* force = getenv("LBM_FORCE_EXCHANGE");
+  return force && atoi(force);
+}
+// ... and, of a peer-to-peer context of n slabs: the rows its halo pushes need
+int p2p_rows_check(const lbm_param* params, int n) {
+  return params->ny / n < 2 ? fail(LBM_EINVAL, "peer-to-peer halos need at least 2 rows per slab") : LBM_OK;
+}
+
+// Every failure of a create call once the context exists: the context freed, the failure's text kept.
 int create_fail(lbm_ctx* c, int rc) {
   std::string keep = g_err;
   lbm_destroy(c);
@@ -485,51 +532,40 @@ int create_fail(lbm_ctx* c, int rc) {
 
 extern "C" int lbm_create(const lbm_param* params, const int* obstacles, const float* cells,
                           int nslabs, const int* devices, int exchange, lbm_ctx** out) {
-  if (!out) return fail(LBM_EINVAL, "out is NULL");
-  *out = nullptr;
-  int rc = check_params(params);
+  int rc = create_args(params, obstacles, out);
   if (rc) return rc;
-  if (!obstacles) return fail(LBM_EINVAL, "obstacles is NULL");
   if (nslabs < 1 || nslabs > params->ny) return fail(LBM_EINVAL, "nslabs must be in [1, ny] (got %d)", nslabs);
   if (exchange < 0 || exchange > LBM_EXCHANGE_P2P) return fail(LBM_EINVAL, "unknown exchange mode %d", exchange);
   int ndev = 0;
-  lbm_device_count(&ndev);
-  if (ndev < 1) return fail(LBM_ENODEV, "no HIP device visible; this library has no CPU path");
-
-  lbm_ctx* c = new lbm_ctx();
-  c->p = *params;
-  c->nranks = nslabs;
-  const char* force = getenv("LBM_FORCE_EXCHANGE");
-  if (nslabs == 1 && !(force && atoi(force)))
-    c->exchange = 0;
+  if ((rc = visible_devices(&ndev))) return rc;
+  auto dev_of = [&](int i) { return devices ? devices[i] : i; };
+  if (nslabs == 1 && !exchange_forced())
+    exchange = 0;
   else if (exchange == LBM_EXCHANGE_AUTO) {
     // RCCL wants one rank per device (ncclCommInitAll rejects a repeated device): several slabs
     // on one GPU trade their halos with peer copies instead
     bool repeated = false;
     for (int i = 0; i < nslabs && !repeated; ++i)
       for (int j = 0; j < i; ++j)
-        if ((devices ? devices[i] : i) == (devices ? devices[j] : j)) { repeated = true; break; }
-    c->exchange = repeated ? LBM_EXCHANGE_COPY : LBM_EXCHANGE_RCCL;
-  } else {
-    c->exchange = exchange;
+        if (dev_of(i) == dev_of(j)) { repeated = true; break; }
+    exchange = repeated ? LBM_EXCHANGE_COPY : LBM_EXCHANGE_RCCL;
   }
-  if (c->exchange == LBM_EXCHANGE_P2P && params->ny / nslabs < 2) {
-    delete c;
-    return fail(LBM_EINVAL, "peer-to-peer halos need at least 2 rows per slab");
-  }
+  if (exchange == LBM_EXCHANGE_P2P && (rc = p2p_rows_check(params, nslabs))) return rc;
+  for (int i = 0; i < nslabs; ++i)
+    if (dev_of(i) < 0 || dev_of(i) >= ndev) return fail(LBM_ENODEV, "slab %d wants HIP device %d but only %d visible", i, dev_of(i), ndev);
+
+  lbm_ctx* c = new lbm_ctx();   // (from here on every failure goes through create_fail)
+  c->p = *params;
+  c->nranks = nslabs;
+  c->exchange = exchange;
   c->tot_fluid = count_fluid(obstacles, (long)params->nx * params->ny);
   c->slabs.resize(nslabs);
   std::vector<int> devs(nslabs);
   for (int i = 0; i < nslabs; ++i) {
     Slab& s = c->slabs[i];
-    s.dev = devices ? devices[i] : i;
-    devs[i] = s.dev;
-    if (s.dev < 0 || s.dev >= ndev) {
-      delete c;
-      return fail(LBM_ENODEV, "slab %d wants HIP device %d but only %d visible", i, s.dev, ndev);
-    }
-    s.row0 = (int)((long)i * params->ny / nslabs);
-    s.nyl = (int)((long)(i + 1) * params->ny / nslabs) - s.row0;
+    s.dev = devs[i] = dev_of(i);
+    const RowRange r = slab_rows(params->ny, nslabs, i);
+    s.row0 = r.row0; s.nyl = r.nyl;
   }
   rc = finish_create(c, obstacles, cells);
   if (!rc && c->exchange == LBM_EXCHANGE_RCCL) {
@@ -550,24 +586,19 @@ extern "C" int lbm_create(const lbm_param* params, const int* obstacles, const f
 extern "C" int lbm_create_rank_ex(const lbm_param* params, const int* obstacles, const float* cells,
                                   int rank, int nranks, int device, const void* unique_id, int exchange,
                                   lbm_ctx** out) {
-  if (!out) return fail(LBM_EINVAL, "out is NULL");
-  *out = nullptr;
-  int rc = check_params(params);
+  int rc = create_args(params, obstacles, out);
   if (rc) return rc;
-  if (!obstacles) return fail(LBM_EINVAL, "obstacles is NULL");
   if (nranks < 1 || nranks > params->ny || rank < 0 || rank >= nranks)
     return fail(LBM_EINVAL, "bad rank %d of %d (ny = %d)", rank, nranks, params->ny);
   if (exchange != LBM_EXCHANGE_RCCL && exchange != LBM_EXCHANGE_P2P)
     return fail(LBM_EINVAL, "rank contexts trade halos by RCCL or peer-to-peer (got mode %d)", exchange);
   int ndev = 0;
-  lbm_device_count(&ndev);
-  if (ndev < 1) return fail(LBM_ENODEV, "no HIP device visible; this library has no CPU path");
+  if ((rc = visible_devices(&ndev))) return rc;
   if (device < 0 || device >= ndev) return fail(LBM_ENODEV, "HIP device %d not visible (%d devices)", device, ndev);
-  const char* force = getenv("LBM_FORCE_EXCHANGE");
-  const bool exchanging = nranks > 1 || (force && atoi(force));
+  const bool exchanging = nranks > 1 || exchange_forced();
   const bool want_p2p = exchanging && exchange == LBM_EXCHANGE_P2P;
   if (exchanging && !unique_id && !want_p2p) return fail(LBM_EINVAL, "unique_id is NULL");
-  if (want_p2p && params->ny / nranks < 2) return fail(LBM_EINVAL, "peer-to-peer halos need at least 2 rows per slab");
+  if (want_p2p && (rc = p2p_rows_check(params, nranks))) return rc;
 
   lbm_ctx* c = new lbm_ctx();
   c->p = *params;
@@ -580,8 +611,8 @@ extern "C" int lbm_create_rank_ex(const lbm_param* params, const int* obstacles,
   c->slabs.resize(1);
   Slab& s = c->slabs[0];
   s.dev = device;
-  s.row0 = (int)((long)rank * params->ny / nranks);
-  s.nyl = (int)((long)(rank + 1) * params->ny / nranks) - s.row0;
+  const RowRange rows = slab_rows(params->ny, nranks, rank);
+  s.row0 = rows.row0; s.nyl = rows.nyl;
   int p2p_rc = LBM_OK;   // a failed peer-to-peer set-up is survivable when RCCL is there to fall back on
   if (want_p2p && unique_id) {
     // probe the uncached allocation first, so that a refusal does not abort the slab set-up half way
@@ -710,16 +741,15 @@ static bool wave_probes_admit(lbm_ctx* c, bool with_forces) {
 // *_in_kernel key stays 0), nothing has been stepped and the caller runs the steps in pieces.
 static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (nsteps == 0) { c->gpu_ms = c->wall_ms = 0.0; return LBM_OK; }
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   const int nx = c->p.nx;
-  const float a1 = accel_pair(c).a1, a2 = accel_pair(c).a2;
+  const AccelRun acc{accel_pair(c), k.drive};
+  const float a1 = acc.ctx.a1, a2 = acc.ctx.a2;
   const bool fo = k.nb > 0;   // lbm_run_forces: the register tiles only in their force flavour; lbm_wave in its force flavour where lbm_run would
                               // run it (fwave, below); else the one-step kernel, lbm_body_forces behind each step
   const bool dr = k.drive != nullptr;   // lbm_run_driven: the register tiles in their kRegDrive flavour; lbm_wave in its driven flavour on a
                                         // lattice alone (dwave, below); else the one-step kernel, each step with its own constants
                                         // (with forces or probes beside it, lbm_run_driven_observed: the driven force-and-probe flavours)
-  auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };   // the accelerate constants of step t (0-based) of this run
-  auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };
   if (!k.no_tiles && regtile_is_next(c)) {   // (a forces run that may not use the tiles says no_tiles)
     bool done = false;
     int rr = run_regtile(c, nsteps, av_vels, &done, k);
@@ -747,9 +777,12 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   if (c->engine >= 2 && !fo && !dr) return fail(LBM_EINVAL, "the register tiles cannot run here (%s), or this lattice has no register tiling (engine = %d)",
                                          c->resident_why[0] ? c->resident_why : "no tiling", c->engine);
   if (k.snap) return LBM_OK;
-  if (c->exchange == LBM_EXCHANGE_P2P) { c->engine_last = 1; return run_p2p(c, nsteps, av_vels, k); }
   c->engine_last = 1;
-  const bool ex = c->exchange != 0;
+  // The halo transport: none (a lattice alone); events -- RCCL or peer copies on the exchange stream between an edge launch and
+  // the interior launch, ev_bnd / ev_int / ev_recv joining the streams; or peer-to-peer -- one stream per slab, no events, no
+  // host-side exchange, the hand-off in the kernels (launch group c->seq).  The launch groups below take their branch by it.
+  const bool p2p = c->exchange == LBM_EXCHANGE_P2P, ev = c->exchange != 0 && !p2p;
+  if (p2p && !c->p2p_connected) return fail(LBM_EINVAL, "peer-to-peer halos are not connected (lbm_p2p_connect)");
   int rc;
   // lbm_run_forces where lbm_run would run lbm_wave (a lattice alone): the groups of K steps in lbm_wave's force flavour.
   // Decided before anything is queued; maps, contributions or partials that do not fit: the one-step path, the same bits.
@@ -759,7 +792,8 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   // (behind those groups the left-over steps go as lbm_run's do, in pairs where it takes pairs: av_vels is lbm_run's bits;
   // a driven run takes no pairs -- lbm_sweep2 has one pair of constants for its two steps)
   const bool pairs = (!fo || fwave) && !dr && t2_eligible(c) && nsteps >= 2;
-  // probes and fields on an admitted context (RunKind::wave): is step s (1-based) of this run a sample step of theirs
+  // probes and fields on an admitted context (RunKind::wave; wave_admit: a lattice alone, so under no exchange): is step s
+  // (1-based) of this run a sample step of theirs
   const WaveWants& w = k.wave;
   const bool pw = w.pout != nullptr, fw = w.fout != nullptr;
   // (the field flavour is a flavour of its own: refused before anything is queued, launch_wave would refuse it mid-run)
@@ -785,20 +819,19 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
                          nx, ncell, sl.blocked, c->p.density, w.fslot(s), w.fpart, w.fmass);
       HIPC(hipGetLastError());
     }
-    if (then_accelerate && sl.accel_row >= 0) {
-      hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, sl.sc,
-                         sl.lat[c->cur], sl.plane, sl.pitch, nx, sl.accel_row, sl.blocked, da1(s), da2(s));   // (step s + 1's phase: entry s)
-      HIPC(hipGetLastError());
-    }
-    return LBM_OK;
+    return then_accelerate ? launch_accelerate(c, sl, acc.pair(s).a1, acc.pair(s).a2) : LBM_OK;   // (step s + 1's phase: entry s)
   };
 
   for (auto& s : c->slabs)
     if ((rc = ensure_sums(s, nsteps))) return rc;
 
-  const bool slabs_march = !fo && !dr && ex && march_slabs_on(c) && nsteps >= slab_K(c);
-  const bool bands = !fo && !dr && ex && !slabs_march && march_bands_on(c) && nsteps >= slab_K(c);   // RCCL transport: ghost bands
-  if (!fo && (!dr || dwave) && (slabs_march || nsteps >= c->time_block) && (rc = check_march_partials(c, slabs_march))) return rc;   // (before anything is queued)
+  // groups of K steps across slabs: the neighbours' rows read in place (slabs of one process under copies; peer-to-peer
+  // contexts by their own rule, the same on every rank), or ghost bands under RCCL
+  const bool slabs_march = !fo && !dr && ev && march_slabs_on(c) && nsteps >= slab_K(c);
+  const bool p2p_march = !fo && !dr && p2p && p2p_march_on(c) && nsteps >= slab_K(c);
+  const bool nb_march = slabs_march || p2p_march;
+  const bool bands = !fo && !dr && ev && !slabs_march && march_bands_on(c) && nsteps >= slab_K(c);
+  if (!fo && (!dr || dwave) && (nb_march || nsteps >= c->time_block) && (rc = check_march_partials(c, nb_march))) return rc;   // (before anything is queued)
   if (bands) {
     if ((rc = bands_setup(c, slab_K(c)))) return rc;
     for (auto& s : c->slabs) {
@@ -811,18 +844,20 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   // ---- prologue: accelerate phase of the first step
   for (auto& s : c->slabs) {
     HIPC(hipSetDevice(s.dev));
-    if (s.accel_row >= 0) {
-      hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, s.sc,
-                         s.lat[c->cur], s.plane, s.pitch, nx, s.accel_row, s.blocked, da1(0), da2(0));
-      HIPC(hipGetLastError());
-    }
+    if ((rc = launch_accelerate(c, s, acc.pair(0).a1, acc.pair(0).a2))) return rc;
     if (slabs_march) HIPC(hipEventRecord(s.ev_march[1], s.sc));   // "launch -1": the starting lattice is in place
   }
   // halo buffers of the launches that trade halos (lbm_sweep2 / lbm_sweep on slabs), filled from the current lattice
-  // as "launch par" (the launch before the first one that reads them)
+  // as "launch par" (the launch before the first one that reads them); peer-to-peer: pushed, as a launch group of its own
   auto prime_halos = [&](int par) -> int {
+    const uint32_t seq = p2p ? ++c->seq : 0;
     for (auto& s : c->slabs) {
       HIPC(hipSetDevice(s.dev));
+      if (p2p) {
+        const int rc = p2p_push(c, s, s.lat[c->cur], seq);
+        if (rc) return rc;
+        continue;
+      }
       if (s.nyl >= 2)
         hipLaunchKernelGGL(lbm::lbm_pack_halos9, dim3(cdiv(nx, 256)), dim3(256), 0, s.sc,
                            s.lat[c->cur], s.plane, s.pitch, nx, s.nyl, s.send_s[par], s.send_n[par]);
@@ -833,9 +868,10 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
       HIPC(hipEventRecord(s.ev_bnd[par], s.sc));   // "edge rows of launch -1 are in place"
       if (split_edge_stream(c, s)) HIPC(hipEventRecord(s.ev_int[par], s.sc));   // "interior of launch -1 is done"
     }
+    if (p2p) return LBM_OK;
     return pairs ? exchange_halos(c, par, 0, lbm::kHaloSlots) : exchange_halos(c, par, 3, 3);
   };
-  if (ex && !slabs_march && !bands && (rc = prime_halos(1))) return rc;
+  if (ev && !slabs_march && !bands && (rc = prime_halos(1))) return rc;
   if (bands) {
     // the ghost bands of the starting lattice, as "group -1" (parity 1 of the events)
     for (auto& s : c->slabs) {
@@ -853,43 +889,33 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   }
 
   // ---- the step loop (reference d2q9-bgk.c:180-201); no host sync inside.
-  // Launch index li numbers the launch groups (a pair of steps or a single step); its parity
+  // Launch index li numbers the launch groups (K steps, a pair of steps or a single step); its parity
   // selects the halo / partial-sum buffers.
   int li = 0, tt = 0;
+  // Every launch folds the partials of the one before it; behind the last group of a kind, here: its `steps` steps,
+  // blocks(s) partials each (join: the edge stream first, where the group had an edge launch).
+  auto fold_last = [&](int steps, bool join, auto blocks) -> int {
+    const int ql = (li - 1) & 1;
+    for (auto& s : c->slabs) {
+      HIPC(hipSetDevice(s.dev));
+      if (join && split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[ql], 0));
+      const int rc = launch_fold(s, ql, steps, blocks(s), tt - steps);
+      if (rc) return rc;
+    }
+    return LBM_OK;
+  };
   if (bands) {                                         // groups of K steps, ghost bands by RCCL once per group
     const int K = slab_K(c), ngroups = nsteps / K;
     for (int g = 0; g < ngroups; ++g, ++li, tt += K)
       if ((rc = launch_band_group(c, li, tt, tt + K < nsteps, g > 0))) return rc;
-    const int ql = (li - 1) & 1;
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      if (split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[ql], 0));   // join the edge stream
-      const BandPlan b = band_plan(c, s);
-      const int nb = b.nb_e + b.nb_i;
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[ql], nb, s.sums + (tt - K), nb);
-      HIPC(hipGetLastError());
-    }
-    if (tt < nsteps && (rc = prime_halos((li & 1) ^ 1))) return rc;   // the remaining steps trade halos
+    if ((rc = fold_last(K, true, [&](const Slab& s) { const BandPlan b = band_plan(c, s); return b.nb_e + b.nb_i; }))) return rc;
   } else
-  if (slabs_march) {                                   // groups of K steps, row-marching, every slab of this process
+  if (nb_march) {                                      // groups of K steps, row-marching, every slab of this process
     const int K = slab_K(c), ngroups = nsteps / K;
+    if (p2p_march && (rc = p2p_march_open(c))) return rc;
     for (int g = 0; g < ngroups; ++g, ++li, tt += K)
-      if ((rc = launch_march_slabs(c, li, tt, tt + K < nsteps, g > 0))) return rc;
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      const int nb = march_slab_blocks(c, s);
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
-                         s.sums + (tt - K), nb);
-      HIPC(hipGetLastError());
-    }
-    if (tt < nsteps) {
-      // the remaining steps trade halos: every slab's marching launches must be over before a neighbour packs / copies
-      for (auto& s : c->slabs) {
-        HIPC(hipSetDevice(s.dev));
-        for (auto& o : c->slabs) HIPC(hipStreamWaitEvent(s.sc, o.ev_march[(li - 1) & 1], 0));
-      }
-      if ((rc = prime_halos((li & 1) ^ 1))) return rc;
-    }
+      if ((rc = (p2p_march ? launch_march_p2p : launch_march_slabs)(c, li, tt, tt + K < nsteps, g > 0))) return rc;
+    if ((rc = fold_last(K, false, [&](const Slab& s) { return march_slab_blocks(c, s); }))) return rc;
   } else
   if ((!fo || fwave) && (!dr || dwave) && march_eligible(c) && nsteps >= c->time_block) {   // groups of K steps, row-marching (lone slab)
     const int K = c->time_block, ngroups = nsteps / K;
@@ -902,11 +928,18 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
     if (dwave) c->driven_in_wave = 1;
     if (pw && wave) c->probes_in_wave = 1;
     if (fw && wave) (w.win && w.fstats ? c->window_stats_in_wave : w.win ? c->window_in_wave : w.fstats ? c->stats_in_wave : w.fadd ? c->mean_in_wave : c->samples_in_wave) = 1;
-    Slab& s = c->slabs[0];
     const int nb = wave ? wave_blocks(c) : cdiv(nx, lbm::MarchCfg<kMarchK>::WOUT) * cdiv(c->p.ny, c->march_rows);
-    hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
-                       s.sums + (tt - K), nb);
-    HIPC(hipGetLastError());
+    if ((rc = fold_last(K, false, [&](const Slab&) { return nb; }))) return rc;
+  }
+  if (tt < nsteps && (bands || nb_march || p2p)) {
+    // the remaining steps trade halos (peer-to-peer: all of them do).  Slabs that marched: every slab's marching launches
+    // must be over before a neighbour packs / copies
+    if (slabs_march)
+      for (auto& s : c->slabs) {
+        HIPC(hipSetDevice(s.dev));
+        for (auto& o : c->slabs) HIPC(hipStreamWaitEvent(s.sc, o.ev_march[(li - 1) & 1], 0));
+      }
+    if ((rc = prime_halos((li & 1) ^ 1))) return rc;
   }
   if (pairs && nsteps - tt >= 2) {
     const int npairs = (nsteps - tt) / 2;
@@ -925,21 +958,13 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
       if (fo && (rc = launch_forces(c, tt + 1, li & 1, nsteps, k))) return rc;
       if (p2 && (rc = pgather(tt + 2, tt + 2 < nsteps))) return rc;
     }
-    const int ql = (li - 1) & 1;
-    for (auto& s : c->slabs) {  // fold the last pair's partials
-      HIPC(hipSetDevice(s.dev));
-      if (ex && split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[ql], 0));   // join the edge stream
-      const int nbtot = cdiv(nx, kT2X) * cdiv(s.nyl, kT2Y);
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(2), dim3(lbm::kBlock), 0, s.sc, s.partials[ql], nbtot, s.sums + (tt - 2), nbtot);
-      HIPC(hipGetLastError());
-    }
+    if ((rc = fold_last(2, ev, [&](const Slab& s) { return t2_tiles(c, s.nyl); }))) return rc;
   }
   const int first_single = tt;
   for (; tt < nsteps; ++tt, ++li) {
     const bool ps = psample(tt + 1) || fsample(tt + 1);
-    // (the rows a step writes carry the NEXT step's accelerate phase: its constants)
-    const bool lst = tt == nsteps - 1;
-    if ((rc = launch_single(c, li, tt, lst || ps, tt > first_single, lst ? a1 : da1(tt + 1), lst ? a2 : da2(tt + 1)))) return rc;
+    const AccelPair next = acc.after(tt, nsteps);
+    if ((rc = launch_single(c, li, tt, tt == nsteps - 1 || ps, tt > first_single, next.a1, next.a2))) return rc;
     if (fo && (rc = launch_forces(c, tt, li & 1, nsteps, k))) return rc;
     if (ps && (rc = pgather(tt + 1, tt + 1 < nsteps))) return rc;
   }
@@ -948,14 +973,10 @@ static int run_steps(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
   const int ql = (li - 1) & 1;
   for (auto& s : c->slabs) {
     HIPC(hipSetDevice(s.dev));
-    if (ex && split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[ql], 0));     // join the edge stream
-    if (first_single < nsteps) {
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(1), dim3(lbm::kBlock), 0, s.sc, s.partials[ql],
-                         single_partial_count(c, s), s.sums + (nsteps - 1), 0);
-      HIPC(hipGetLastError());
-    }
+    if (ev && split_edge_stream(c, s)) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[ql], 0));     // join the edge stream
+    if (first_single < nsteps && (rc = launch_fold(s, ql, 1, single_partial_count(c, s), nsteps - 1))) return rc;
     HIPC(hipEventRecord(s.ev_t1, s.sc));
-    if (ex) HIPC(hipStreamWaitEvent(s.sc, s.ev_recv[ql], 0));  // drain the last exchange
+    if (ev) HIPC(hipStreamWaitEvent(s.sc, s.ev_recv[ql], 0));  // drain the last exchange
   }
   return collect_sums(c, nsteps, av_vels, wall0, k);
 }
@@ -980,7 +1001,7 @@ extern "C" int lbm_run_driven(lbm_ctx* c, int nsteps, float* av_vels, const floa
     if (!std::isfinite(accel[t])) return fail(LBM_EINVAL, "accel[%d] is not finite", t);
   c->driven_in_kernel = 0; c->driven_in_wave = 0;
   if (nsteps == 0) return run_steps(c, 0, av_vels);
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   const std::vector<float> pairs = accel_pairs(c, accel, nsteps);
   // ---- the register tiles need the table on the device: decided here, before anything is queued; no room, or a rank that
   // would not use the tiles: every rank takes the one-step path (the same bits), nobody fails
@@ -1141,7 +1162,7 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
   if (!strcmp(key, "march_rows")) {
     if (value < 1 || value > c->p.ny) return fail(LBM_EINVAL, "march_rows must be in [1, ny]");
     { const int was = c->march_rows; c->march_rows = (int)value;
-      if (check_march_partials(c, c->exchange != 0 && c->exchange != LBM_EXCHANGE_P2P && march_slabs_on(c))) { c->march_rows = was; return LBM_EINVAL; } }
+      if (check_march_partials(c, march_slabs_on(c))) { c->march_rows = was; return LBM_EINVAL; } }
     return LBM_OK;
   }
   if (!strcmp(key, "march_kernel")) {
@@ -1152,7 +1173,7 @@ extern "C" int lbm_set_option(lbm_ctx* c, const char* key, long value) {
   if (!strcmp(key, "wave_rows")) {
     if (value < 1 || value > c->p.ny) return fail(LBM_EINVAL, "wave_rows must be in [1, ny]");
     { const int was = c->wave_rows; c->wave_rows = (int)value;
-      if (check_march_partials(c, c->exchange != 0 && (p2p_march_on(c) || (c->exchange != LBM_EXCHANGE_P2P && march_slabs_on(c))))) { c->wave_rows = was; return LBM_EINVAL; } }
+      if (check_march_partials(c, p2p_march_on(c) || march_slabs_on(c))) { c->wave_rows = was; return LBM_EINVAL; } }
     return LBM_OK;
   }
   if (!strcmp(key, "wave_cols")) {
@@ -1240,7 +1261,7 @@ extern "C" int lbm_get_info(const lbm_ctx* c, const char* key, double* value) {
     if (!strcmp(key, e.key)) { *value = c->*e.member; return LBM_OK; }
   if (!strcmp(key, "kernel_variant")) { *value = (double)c->variant; return LBM_OK; }
   if (!strcmp(key, "time_block_active")) {
-    *value = (march_eligible(c) || p2p_march_on(c) || march_bands_on(c) || (c->exchange != 0 && c->exchange != LBM_EXCHANGE_P2P && march_slabs_on(const_cast<lbm_ctx*>(c))))
+    *value = (march_eligible(c) || p2p_march_on(c) || march_bands_on(c) || march_slabs_on(const_cast<lbm_ctx*>(c)))
                  ? c->time_block : t2_eligible(c) ? 2 : 1;
     return LBM_OK;
   }

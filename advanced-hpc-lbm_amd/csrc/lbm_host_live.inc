@@ -18,7 +18,7 @@
 namespace {
 
 int live_guard(const lbm_ctx* c) {
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   return LBM_OK;
 }
 

@@ -1,6 +1,8 @@
-// lbm_host_march.inc -- part of lbm_api.hip (included there): the marching kernels on the host side -- lbm_march and lbm_wave on
-// a lattice alone and across slabs (neighbours' rows read in place; ghost bands under RCCL), the wave-slot model that picks chunk
-// heights and columns per lane.
+// lbm_host_march.inc -- part of lbm_api.hip (included there): the launch groups of the step loop (run_steps), each with a
+// branch per halo transport -- the parts they share (sweep_args, sweep2_args, launch_accelerate, launch_fold), single steps and
+// pairs, and the marching kernels on the host side: lbm_march and lbm_wave on a lattice alone and across slabs (neighbours'
+// rows read in place, under copies and peer-to-peer; ghost bands under RCCL), the wave-slot model that picks chunk heights and
+// columns per lane.
 namespace {
 
 // Edge launches run on their own high-priority stream, concurrent with the interior launch, only
@@ -9,46 +11,97 @@ namespace {
 inline bool split_edge_stream(const lbm_ctx* c, const Slab& s) { return (long)s.nyl * c->p.nx >= (1L << 22); }
 inline hipStream_t edge_stream(const lbm_ctx* c, const Slab& s) { return split_edge_stream(c, s) ? s.se : s.sc; }
 
-// One single-step launch group (all local slabs) for step tt, launch index li.
+// ---- the parts of the step loop (run_steps), one copy each
+// The accelerate phase of the current lattice, by a launch of its own: the first step of a run, and behind a gather.
+int launch_accelerate(const lbm_ctx* c, Slab& s, float a1, float a2) {
+  if (s.accel_row < 0) return LBM_OK;
+  hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(c->p.nx, 256)), dim3(256), 0, s.sc,
+                     s.lat[c->cur], s.plane, s.pitch, c->p.nx, s.accel_row, s.blocked, a1, a2);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// Folds `steps` steps of the launch of parity q, nb blocks' partials each, into sums + t: behind the last launch of its kind,
+// which no next launch folds.
+int launch_fold(Slab& s, int q, int steps, int nb, int t) {
+  hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(steps), dim3(lbm::kBlock), 0, s.sc, s.partials[q], nb, s.sums + t, steps > 1 ? nb : 0);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
+// Partial sums (blocks) of one single-step launch group of a slab: edge rows and interior rows where they are two launches.
+int single_partial_count(const lbm_ctx* c, const Slab& s) {
+  if (c->exchange == 0 || c->exchange == LBM_EXCHANGE_P2P) return sweep_blocks(c, s.nyl);
+  return sweep_blocks(c, s.nyl >= 2 ? 2 : 1) + (s.nyl > 2 ? sweep_blocks(c, s.nyl - 2) : 0);
+}
+
+// The arguments of a one-step launch of slab s, launch parity q, as every launch sets them: lattices, geometry, omega, the
+// accelerate row (last: none) and pair, the partials of parity q and -- fold_prev -- the fold of the group before, step
+// tt - 1.  The caller sets the rows, the ghost rows and the send buffers (value-initialised: none).
+lbm::SweepArgs sweep_args(const lbm_ctx* c, const Slab& s, int q, int tt, bool last, bool fold_prev, float a1, float a2) {
+  lbm::SweepArgs a{};
+  a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
+  a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.nyl = s.nyl;
+  a.blocked = s.blocked; a.omega = c->p.omega;
+  a.accel_row = last ? -1 : s.accel_row;
+  a.a1 = a1; a.a2 = a2;
+  a.partials = s.partials[q];
+  if (fold_prev) { a.prev_partials = s.partials[q ^ 1]; a.prev_count = single_partial_count(c, s); a.prev_sum = s.sums + (tt - 1); }
+  return a;
+}
+// ... and of a two-step launch (steps tt, tt + 1; the fold: of the pair before).  The caller sets the tile rows and, on an
+// edge or peer-to-peer launch, the ghost rows, their obstacle bytes, the send buffers and the hand-off.
+lbm::Sweep2Args sweep2_args(const lbm_ctx* c, const Slab& s, int q, int tt, bool accel_out, bool fold_prev, float a1, float a2) {
+  const int nbtot = t2_tiles(c, s.nyl);
+  lbm::Sweep2Args a{};
+  a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
+  a.plane = s.plane; a.pitch = s.pitch; a.nx = c->p.nx; a.ny = s.nyl;
+  a.blocked = s.blocked; a.omega = c->p.omega;
+  a.accel_row = s.accel_row >= 0 ? s.accel_row : lbm::kNoRow;
+  a.accel_out = accel_out ? 1 : 0;
+  a.a1 = a1; a.a2 = a2;
+  a.partials1 = s.partials[q]; a.partials2 = s.partials[q] + nbtot;
+  if (fold_prev) { a.prev1 = s.partials[q ^ 1]; a.prev2 = s.partials[q ^ 1] + nbtot; a.prev_count = nbtot; a.prev_sum = s.sums + (tt - 2); }
+  return a;
+}
+
+// One single-step launch group (all local slabs) for step tt, launch index li, by the context's transport: a slab alone;
+// slabs that trade halos through events (RCCL, copies): the edge rows, the exchange, the interior rows; peer-to-peer: group
+// ++c->seq -- a wait launch, the rows on the halos of the group before, a push launch.
 int launch_single(lbm_ctx* c, int li, int tt, bool last, bool fold_prev, float a1, float a2) {
   const int nx = c->p.nx;
   const int q = li & 1, qp = q ^ 1;
-  const bool ex = c->exchange != 0;
+  const bool p2p = c->exchange == LBM_EXCHANGE_P2P, ex = c->exchange != 0 && !p2p;
+  const uint32_t seq = p2p ? ++c->seq : 0;
   const long h3 = 3L * nx;  // one-step halos live in slots 3..5 of the nine-slot buffers
   int rc;
   for (auto& s : c->slabs) {
     HIPC(hipSetDevice(s.dev));
-    lbm::SweepArgs a;
-    a.src = s.lat[c->cur];
-    a.dst = s.lat[c->cur ^ 1];
-    a.plane = s.plane; a.pitch = s.pitch; a.nx = nx; a.nyl = s.nyl;
-    a.blocked = s.blocked;
-    a.omega = c->p.omega;
-    a.accel_row = last ? -1 : s.accel_row;
-    a.a1 = a1; a.a2 = a2;
-    a.partials = s.partials[q];
-    a.prev_partials = nullptr; a.prev_count = 0; a.prev_sum = nullptr;
-    if (!ex) {
+    lbm::SweepArgs a = sweep_args(c, s, q, tt, last, fold_prev, a1, a2);
+    a.y_begin = 0; a.y_count = s.nyl; a.y_stride = 1;
+    if (c->exchange == 0) {
       // one slab, periodic self-wrap: the halo rows are the slab's own edge rows
       const long top = (long)(s.nyl - 1) * s.pitch;
       a.south2 = a.src + 2 * s.plane + top; a.south5 = a.src + 5 * s.plane + top; a.south6 = a.src + 6 * s.plane + top;
       a.north4 = a.src + 4 * s.plane; a.north7 = a.src + 7 * s.plane; a.north8 = a.src + 8 * s.plane;
-      a.send_south = a.send_north = nullptr;
-      a.y_begin = 0; a.y_count = s.nyl; a.y_stride = 1;
-      const int nb = sweep_blocks(c, a.y_count);
-      if (fold_prev) { a.prev_partials = s.partials[qp]; a.prev_count = nb; a.prev_sum = s.sums + (tt - 1); }
       launch_sweep(c, a, s.sc);
       HIPC(hipGetLastError());
+      continue;
+    }
+    const int qg = p2p ? (seq - 1) & 1 : qp;
+    const float* gs = s.ghost_s[qg] + h3;
+    const float* gn = s.ghost_n[qg] + h3;
+    a.south2 = gs; a.south5 = gs + nx; a.south6 = gs + 2 * nx;
+    a.north4 = gn; a.north7 = gn + nx; a.north8 = gn + 2 * nx;
+    if (p2p) {
+      if ((rc = p2p_push(c, s, nullptr, seq))) return rc;
+      launch_sweep(c, a, s.sc);
+      HIPC(hipGetLastError());
+      if ((rc = p2p_push(c, s, a.dst, seq))) return rc;   // the new edge rows
     } else {
-      a.south2 = s.ghost_s[qp] + h3; a.south5 = s.ghost_s[qp] + h3 + nx; a.south6 = s.ghost_s[qp] + h3 + 2 * nx;
-      a.north4 = s.ghost_n[qp] + h3; a.north7 = s.ghost_n[qp] + h3 + nx; a.north8 = s.ghost_n[qp] + h3 + 2 * nx;
       a.send_south = s.send_s[q] + h3; a.send_north = s.send_n[q] + h3;
       // boundary rows first: they feed the exchange
-      const int nb_rows = s.nyl >= 2 ? 2 : 1;
-      a.y_begin = 0; a.y_count = nb_rows; a.y_stride = s.nyl >= 2 ? s.nyl - 1 : 1;
-      const int nbb = sweep_blocks(c, nb_rows);
-      const int nbi = s.nyl > 2 ? sweep_blocks(c, s.nyl - 2) : 0;
-      if (fold_prev) { a.prev_partials = s.partials[qp]; a.prev_count = nbb + nbi; a.prev_sum = s.sums + (tt - 1); }
+      a.y_count = s.nyl >= 2 ? 2 : 1; a.y_stride = s.nyl >= 2 ? s.nyl - 1 : 1;
       // edge stream: after the halos of the previous launch arrived and its interior finished
       hipStream_t es = edge_stream(c, s);
       HIPC(hipStreamWaitEvent(es, s.ev_recv[qp], 0));
@@ -66,19 +119,9 @@ int launch_single(lbm_ctx* c, int li, int tt, bool last, bool fold_prev, float a
       const bool split = split_edge_stream(c, s);
       if (split) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[qp], 0));
       if (s.nyl <= 2) { if (split) HIPC(hipEventRecord(s.ev_int[q], s.sc)); continue; }
-      lbm::SweepArgs a;
-      a.src = s.lat[c->cur];
-      a.dst = s.lat[c->cur ^ 1];
-      a.plane = s.plane; a.pitch = s.pitch; a.nx = nx; a.nyl = s.nyl;
-      a.blocked = s.blocked;
-      a.omega = c->p.omega;
-      a.accel_row = last ? -1 : s.accel_row;
-      a.a1 = a1; a.a2 = a2;
-      a.south2 = a.south5 = a.south6 = a.north4 = a.north7 = a.north8 = nullptr;  // interior rows never touch halos
-      a.send_south = a.send_north = nullptr;
+      lbm::SweepArgs a = sweep_args(c, s, q, tt, last, false, a1, a2);   // (interior rows never touch halos)
       a.y_begin = 1; a.y_count = s.nyl - 2; a.y_stride = 1;
-      a.partials = s.partials[q] + sweep_blocks(c, 2);
-      a.prev_partials = nullptr; a.prev_count = 0; a.prev_sum = nullptr;
+      a.partials += sweep_blocks(c, 2);
       launch_sweep(c, a, s.sc);
       HIPC(hipGetLastError());
       if (split) HIPC(hipEventRecord(s.ev_int[q], s.sc));
@@ -88,46 +131,35 @@ int launch_single(lbm_ctx* c, int li, int tt, bool last, bool fold_prev, float a
   return LBM_OK;
 }
 
-int single_partial_count(const lbm_ctx* c, const Slab& s) {
-  if (c->exchange == 0) return sweep_blocks(c, s.nyl);
-  return sweep_blocks(c, s.nyl >= 2 ? 2 : 1) + (s.nyl > 2 ? sweep_blocks(c, s.nyl - 2) : 0);
-}
-
-// One two-step launch group (all local slabs) for steps tt, tt+1, launch index li.
+// One two-step launch group (all local slabs) for steps tt, tt+1, launch index li.  Peer-to-peer: ONE launch per slab, whose
+// edge tiles go first and carry the hand-off themselves (lbm::kSweep2P2P).
 int launch_pair(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, float a1, float a2) {
-  const int nx = c->p.nx;
   const int q = li & 1, qp = q ^ 1;
-  const bool ex = c->exchange != 0;
-  const int ntx = cdiv(nx, kT2X);   // (partial tiles only when the slab is alone)
+  const bool p2p = c->exchange == LBM_EXCHANGE_P2P, ex = c->exchange != 0 && !p2p;
+  const uint32_t seq = p2p ? ++c->seq : 0;
+  const int ntx = cdiv(c->p.nx, kT2X);   // (partial tiles only when the slab is alone)
   int rc;
-  auto fill = [&](Slab& s, lbm::Sweep2Args& a) {
-    const int nbtot = ntx * cdiv(s.nyl, kT2Y);
-    a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
-    a.plane = s.plane; a.pitch = s.pitch; a.nx = nx; a.ny = s.nyl;
-    a.blocked = s.blocked; a.omega = c->p.omega;
-    a.accel_row = s.accel_row >= 0 ? s.accel_row : lbm::kNoRow;
-    a.accel_out = accel_out ? 1 : 0;
-    a.a1 = a1; a.a2 = a2;
-    a.partials1 = s.partials[q]; a.partials2 = s.partials[q] + nbtot;
-    a.prev1 = a.prev2 = nullptr; a.prev_count = 0; a.prev_sum = nullptr;
-    a.ghost_s = a.ghost_n = nullptr; a.blocked_gs = a.blocked_gn = nullptr; a.send_s = a.send_n = nullptr;
-    return nbtot;
-  };
   for (auto& s : c->slabs) {
     HIPC(hipSetDevice(s.dev));
-    lbm::Sweep2Args a;
-    const int nbtot = fill(s, a);
+    lbm::Sweep2Args a = sweep2_args(c, s, q, tt, accel_out, fold_prev, a1, a2);
     const int nty = cdiv(s.nyl, kT2Y);
-    if (fold_prev) { a.prev1 = s.partials[qp]; a.prev2 = s.partials[qp] + nbtot; a.prev_count = nbtot; a.prev_sum = s.sums + (tt - 2); }
-    if (!ex) {
-      a.by_begin = 0; a.by_count = nty; a.by_stride = 1;
-      launch_sweep2(c, a, nbtot, s.sc, false);
+    a.by_begin = 0; a.by_count = nty; a.by_stride = 1;
+    if (c->exchange == 0) {
+      launch_sweep2(c, a, ntx * nty, s.sc, false);
+      HIPC(hipGetLastError());
+      continue;
+    }
+    const int qg = p2p ? (seq - 1) & 1 : qp;
+    a.ghost_s = s.ghost_s[qg]; a.ghost_n = s.ghost_n[qg];
+    a.blocked_gs = s.blocked_gs; a.blocked_gn = s.blocked_gn;
+    if (p2p) {
+      a.send_s = p2p_remote_s(s, seq); a.send_n = p2p_remote_n(s, seq);
+      a.sync = p2p_sync(s, seq, ntx, ntx);
+      launch_sweep2_p2p(c, a, ntx * nty, s.sc);
       HIPC(hipGetLastError());
     } else {
       // edge tile rows first: they consume the halos of the previous pair and pack the next ones
-      a.by_begin = 0; a.by_count = nty >= 2 ? 2 : 1; a.by_stride = nty >= 2 ? nty - 1 : 1;
-      a.ghost_s = s.ghost_s[qp]; a.ghost_n = s.ghost_n[qp];
-      a.blocked_gs = s.blocked_gs; a.blocked_gn = s.blocked_gn;
+      a.by_count = nty >= 2 ? 2 : 1; a.by_stride = nty >= 2 ? nty - 1 : 1;
       a.send_s = s.send_s[q]; a.send_n = s.send_n[q];
       hipStream_t es = edge_stream(c, s);
       HIPC(hipStreamWaitEvent(es, s.ev_recv[qp], 0));
@@ -145,8 +177,7 @@ int launch_pair(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev, floa
       const bool split = split_edge_stream(c, s);
       if (split) HIPC(hipStreamWaitEvent(s.sc, s.ev_bnd[qp], 0));
       if (nty <= 2) { if (split) HIPC(hipEventRecord(s.ev_int[q], s.sc)); continue; }
-      lbm::Sweep2Args a;
-      fill(s, a);
+      lbm::Sweep2Args a = sweep2_args(c, s, q, tt, accel_out, false, a1, a2);
       a.by_begin = 1; a.by_count = nty - 2; a.by_stride = 1;
       a.partials1 += 2 * ntx; a.partials2 += 2 * ntx;   // after the two edge tile rows
       launch_sweep2(c, a, ntx * (nty - 2), s.sc, false);
@@ -196,7 +227,7 @@ int launch_march(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev) {
 bool march_slabs_setup(lbm_ctx* c) {
   if (c->march_slabs >= 0) return c->march_slabs == 1;
   c->march_slabs = 0;
-  if (c->rank_mode || c->exchange == 0 || c->exchange == LBM_EXCHANGE_RCCL) return false;
+  if (c->rank_mode || c->exchange != LBM_EXCHANGE_COPY) return false;   // (peer-to-peer contexts march by p2p_march_on's rule)
   const int K = (c->time_block == 8) ? 8 : kMarchK;
   if (K != kMarchK ? c->p.nx < 64 : (c->p.nx % 4 != 0 || c->p.nx < lbm::MarchCfg<kMarchK>::W)) return false;
   const int ns = (int)c->slabs.size();
@@ -345,6 +376,61 @@ int launch_march_slabs(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_pre
     const int rc = launch_slab_pass(c, s, nbr, K, q, tt, accel_out, fold_prev);
     if (rc) return rc;
     HIPC(hipEventRecord(s.ev_march[q], s.sc));
+  }
+  c->cur ^= 1;
+  return LBM_OK;
+}
+
+// ---- ... and across slabs with peer-to-peer halos, one process or one per GPU: the K ghost rows either side are read
+// straight out of the neighbours' lattices (Slab::nb_lat, over xGMI), where every slab fills the chip.  The decision uses
+// the lattice, the number of slabs and the options only -- every rank must come to the same answer, the two protocols
+// do not mix.
+bool p2p_march_on(const lbm_ctx* c) {
+  const int K = slab_K(c);
+  if (K == 0 || c->exchange != LBM_EXCHANGE_P2P) return false;
+  const int rows = c->p.ny / c->nranks;                     // the smallest slab
+  if (rows < 4 * K || (double)(rows + 1) * c->slabs[0].pitch * 4.0 >= 4.0e9) return false;
+  for (auto& s : c->slabs) if (!s.nb_lat[0][0] || !s.nb_lat[1][0]) return false;   // (connect failed: an error everywhere)
+  return true;
+}
+bool p2p_march_pays(const lbm_ctx* c) {                      // same estimate as for a lone lattice, on the smallest slab
+  const int rows = c->p.ny / c->nranks, h = march_rows_for(c, rows), ns = cdiv(c->p.nx, lbm::MarchCfg<kMarchK>::WOUT), ncu = std::max(c->ncu, 1);
+  const long blocks = (long)ns * cdiv(rows, h), rounds = (blocks + ncu - 1) / ncu;
+  return (double)rows * ns / ((double)rounds * ncu * (h + 3 * (kMarchK - 1))) >= 0.65;
+}
+// lbm_wave<8> instead of lbm_march on slabs of `rows` rows?  When its waves fill at least most of one round of the
+// chip's wave slots.  Measured on one GPU (tools/strong_scaling_proxy.py, us per step, lbm_wave<8> against lbm_march):
+// 8192 x 4096 126 / 135, 8192 x 2048 69.3 / 70.3, 8192 x 1024 38.7 / 39.4 -- a little ahead everywhere, with half as
+// many launches (and flag hand-offs over xGMI) per step; 1024-wide slabs (22 wave columns) are far too narrow: 12.4 / 5.4.
+bool slab_wave_pays(const lbm_ctx* c, int rows, int K) {
+  if (c->p.nx < 64 || rows < 32 || c->march_kernel == 0) return false;
+  const int h = slab_wave_rows(c, rows, K);
+  return (double)cdiv(c->p.nx, wave_out_cols(c, K)) * cdiv(rows, h) >= 0.85 * wave_slots(c, K);
+}
+// Launch group seq of a slab starts once both neighbours have raised seq - 1 ("my group seq - 1 is over": their rows are
+// final, and they no longer read the lattice this launch overwrites) and raises seq when it is over.  In front of a run's
+// first group, "the starting lattice is in place": a group of its own that launches nothing.
+int p2p_march_open(lbm_ctx* c) {
+  const uint32_t seq = ++c->seq;
+  int rc;
+  for (auto& s : c->slabs) {
+    HIPC(hipSetDevice(s.dev));
+    if ((rc = p2p_push(c, s, nullptr, seq))) return rc;   // (the neighbours are through with the previous run)
+    if ((rc = p2p_raise(s, seq))) return rc;
+  }
+  return LBM_OK;
+}
+// One marching launch group over all local slabs: steps tt .. tt+K-1, launch index li.
+int launch_march_p2p(lbm_ctx* c, int li, int tt, bool accel_out, bool fold_prev) {
+  const uint32_t seq = ++c->seq;
+  int rc;
+  for (auto& s : c->slabs) {
+    HIPC(hipSetDevice(s.dev));
+    if ((rc = p2p_push(c, s, nullptr, seq))) return rc;   // wait for both neighbours' seq-1
+    const SlabNb nbr{s.nb_lat[0][c->cur], s.nb_lat[1][c->cur], s.nb_plane[0], s.nb_plane[1], s.nb_nyl[0], s.nb_nyl[1],
+                     s.nb_blocked[0], s.nb_blocked[1]};
+    if ((rc = launch_slab_pass(c, s, nbr, slab_K(c), li & 1, tt, accel_out, fold_prev))) return rc;
+    if ((rc = p2p_raise(s, seq))) return rc;
   }
   c->cur ^= 1;
   return LBM_OK;

@@ -435,7 +435,7 @@ extern "C" int lbm_run_sampled(lbm_ctx* c, int nsteps, float* av_vels, int every
   if (m > 0 && !fields_out) return fail(LBM_EINVAL, "fields_out is NULL but %d snapshot(s) are due", m);
   c->samples_in_kernel = 0; c->samples_in_wave = 0;
   if (m == 0) return run_steps(c, nsteps, av_vels);
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   const int nx = c->p.nx;
   const int base_row = c->rank_mode ? c->slabs[0].row0 : 0;
@@ -561,7 +561,7 @@ extern "C" int lbm_run_forces(lbm_ctx* c, int nsteps, float* av_vels, float* for
   if (nsteps > 0 && !forces) return fail(LBM_EINVAL, "forces is NULL");
   c->forces_in_kernel = 0; c->forces_in_wave = 0;
   if (nsteps == 0) return run_steps(c, 0, av_vels);
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   const int nb = c->nbodies;
   const long nval = 2L * nb * nsteps;
   if (nval + nsteps + 1 > (1L << 30)) return fail(LBM_EINVAL, "a forces run of %d steps is too long (split it)", nsteps);
@@ -590,7 +590,7 @@ extern "C" int lbm_run_mean(lbm_ctx* c, int nsteps, float* av_vels, int every, f
   if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
   if (!mean_out) return fail(LBM_EINVAL, "mean_out is NULL");
   c->mean_in_kernel = 0; c->mean_in_wave = 0;
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   CellSums mo(c, 4);
   int rc;
@@ -634,7 +634,7 @@ extern "C" int lbm_run_stats(lbm_ctx* c, int nsteps, float* av_vels, int every, 
   if (m == 0) return fail(LBM_EINVAL, "nothing to average: no sample step in %d step(s) at every = %d", nsteps, every);
   if (!stats_out) return fail(LBM_EINVAL, "stats_out is NULL");
   c->stats_in_wave = 0;
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   CellSums mo(c, 8);
   int rc;
@@ -724,7 +724,7 @@ extern "C" int lbm_run_probes(lbm_ctx* c, int nsteps, float* av_vels, int every,
   if (m == 0) return fail(LBM_EINVAL, "nothing to record: no sample step in nsteps = %d step(s) at every = %d", nsteps, every);
   if (!probes_out) return fail(LBM_EINVAL, "probes_out is NULL");
   c->probes_in_kernel = 0; c->probes_in_wave = 0;
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   // ---- everything that can fail for want of room or a wrong pointer is decided here, before anything is queued
   ProbeOut po(c);
   int rc;
@@ -914,7 +914,7 @@ extern "C" int lbm_run_window(lbm_ctx* c, int nsteps, float* av_vels, int every,
   if (m > 0 && (rc = wo.locate(window_out, "window_out"))) return rc;
   c->window_in_kernel = 0; c->window_in_wave = 0;
   if (m == 0) return run_steps(c, nsteps, av_vels);
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   // ---- everything that can fail for want of room is decided here, before anything is queued.  The staging of m windows, or
   // the register tiles' tables, that do not fit: the split path with the staging of one window, the same bits.
   bool in_kernel = regtile_is_next(c);
@@ -970,7 +970,7 @@ extern "C" int lbm_run_window_stats(lbm_ctx* c, int nsteps, float* av_vels, int 
   CellSums ws(c, 8, &plan.w);
   if ((rc = ws.locate(stats_out, "stats_out"))) return rc;
   c->window_stats_in_wave = 0; c->window_stats_in_kernel = 0; c->window_stats_pieces = 0;
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   // ---- everything that can fail for want of room is decided here, before anything is queued.  The sums must fit; the
   // register tiles' tables or staging that do not: the split path, the same bits, nobody fails.
   rc = ws.prepare();
@@ -1042,7 +1042,7 @@ static int run_observed(lbm_ctx* c, int nsteps, float* av_vels, const lbm_observ
   if (ws && se < 0) return fail(LBM_EINVAL, "fields_every < 0");
   const int mp = wp ? nsteps / pe : 0, mm = wm ? nsteps / me : 0, msn = (ws && se > 0) ? nsteps / se : 0;
   if (msn == 0) ws = false;                               // (no snapshot is due: legal, nothing written, as lbm_run_sampled)
-  if (c->p2p_failed) return fail(LBM_EHIP, "a peer-to-peer halo wait timed out earlier: this lattice is no longer defined");
+  if (int refused = refuse_failed(c)) return refused;
   ProbeOut po(c);
   CellSums mo(c, 4);
   bool s_dev = false;

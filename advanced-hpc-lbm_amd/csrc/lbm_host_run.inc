@@ -1,7 +1,8 @@
 // lbm_host_run.inc -- part of lbm_api.hip (included there): the kind of a run (RunKind: one flavour field for the register
 // tiles), the end of a run (sums, agreement), the tiles' tables (ONE upload, tile_table_set, of the layout lbm_tile_table.h
 // builds: forces, probes, windows, the empty table), the register-tile engine (one driver for a lattice alone and for
-// slabs; run_regtile turns the flavour into kernel, LDS and tables in one switch), the step loop with peer-to-peer halos.
+// slabs; run_regtile turns the flavour into kernel, LDS and tables in one switch).  (The step loop of every halo transport
+// is run_steps, lbm_api.hip; its launch groups are in lbm_host_march.inc.)
 namespace {
 
 // Where a register-tile run puts its snapshots (lbm_run_sampled): per local slab, the slab's region of snapshot 0 on its
@@ -644,221 +645,8 @@ int run_regtile(lbm_ctx* c, int nsteps, float* av_vels, bool* done, RunKind k) {
   return LBM_OK;
 }
 
-// Peer-to-peer pointers of a slab for launch group `seq` (see lbm::P2PSync); bumps the completion
-// targets by the number of blocks that will count themselves done on each side.
-lbm::P2PSync p2p_sync(Slab& s, uint32_t seq, int blocks_s, int blocks_n) {
-  lbm::P2PSync y;
-  const size_t f = 4 * s.halo_bytes;
-  y.flag_s = (const uint32_t*)(s.comm_block + f);
-  y.flag_n = (const uint32_t*)(s.comm_block + f + 256);
-  y.rem_flag_s = (uint32_t*)(s.peer_s + f + 256);   // I am the south neighbour's NORTH side
-  y.rem_flag_n = (uint32_t*)(s.peer_n + f);
-  y.cnt_s = s.counters; y.cnt_n = s.counters + 16; y.err = s.counters + 32;
-  s.cnt_s_total += (uint32_t)blocks_s; s.cnt_n_total += (uint32_t)blocks_n;
-  y.cnt_target_s = s.cnt_s_total; y.cnt_target_n = s.cnt_n_total;
-  y.seq = seq;
-  return y;
-}
-inline float* p2p_remote_s(const Slab& s, uint32_t seq) { return (float*)(s.peer_s + (size_t)(2 + (seq & 1)) * s.halo_bytes); }  // its ghost_n
-inline float* p2p_remote_n(const Slab& s, uint32_t seq) { return (float*)(s.peer_n + (size_t)(seq & 1) * s.halo_bytes); }        // its ghost_s
-
-// Peer-to-peer contexts march too (lbm_march, neighbours' rows read in place over xGMI) where every slab fills the
-// chip.  The decision uses the lattice, the number of slabs and the options only -- every rank must come to the same
-// answer, the two protocols do not mix.
-bool p2p_march_on(const lbm_ctx* c) {
-  const int K = slab_K(c);
-  if (K == 0 || c->exchange != LBM_EXCHANGE_P2P) return false;
-  const int rows = c->p.ny / c->nranks;                     // the smallest slab
-  if (rows < 4 * K || (double)(rows + 1) * c->slabs[0].pitch * 4.0 >= 4.0e9) return false;
-  for (auto& s : c->slabs) if (!s.nb_lat[0][0] || !s.nb_lat[1][0]) return false;   // (connect failed: an error everywhere)
-  return true;
-}
-bool p2p_march_pays(const lbm_ctx* c) {                      // same estimate as for a lone lattice, on the smallest slab
-  const int rows = c->p.ny / c->nranks, h = march_rows_for(c, rows), ns = cdiv(c->p.nx, lbm::MarchCfg<kMarchK>::WOUT), ncu = std::max(c->ncu, 1);
-  const long blocks = (long)ns * cdiv(rows, h), rounds = (blocks + ncu - 1) / ncu;
-  return (double)rows * ns / ((double)rounds * ncu * (h + 3 * (kMarchK - 1))) >= 0.65;
-}
-// lbm_wave<8> instead of lbm_march on slabs of `rows` rows?  When its waves fill at least most of one round of the
-// chip's wave slots.  Measured on one GPU (tools/strong_scaling_proxy.py, us per step, lbm_wave<8> against lbm_march):
-// 8192 x 4096 126 / 135, 8192 x 2048 69.3 / 70.3, 8192 x 1024 38.7 / 39.4 -- a little ahead everywhere, with half as
-// many launches (and flag hand-offs over xGMI) per step; 1024-wide slabs (22 wave columns) are far too narrow: 12.4 / 5.4.
-bool slab_wave_pays(const lbm_ctx* c, int rows, int K) {
-  if (c->p.nx < 64 || rows < 32 || c->march_kernel == 0) return false;
-  const int h = slab_wave_rows(c, rows, K);
-  return (double)cdiv(c->p.nx, wave_out_cols(c, K)) * cdiv(rows, h) >= 0.85 * wave_slots(c, K);
-}
-
-// The step loop with peer-to-peer halos: one stream per slab, no events, no host-side exchange.
-// Two-step launches carry the hand-off themselves (edge tiles first); single steps are bracketed
-// by a wait launch and a push launch.
-int run_p2p(lbm_ctx* c, int nsteps, float* av_vels, RunKind k) {
-  if (!c->p2p_connected) return fail(LBM_EINVAL, "peer-to-peer halos are not connected (lbm_p2p_connect)");
-  const int nx = c->p.nx;
-  const float a1 = accel_pair(c).a1, a2 = accel_pair(c).a2;
-  const bool dr = k.drive != nullptr;                              // lbm_run_driven: one step per launch, each with its own constants
-  auto da1 = [&](int t) { return dr ? k.drive[2 * t] : a1; };      // the accelerate constants of step t (0-based) of this run
-  auto da2 = [&](int t) { return dr ? k.drive[2 * t + 1] : a2; };
-  const bool pairs = k.nb == 0 && !dr && t2_eligible(c) && nsteps >= 2;   // (lbm_run_forces: one step per launch, forces behind each)
-  const int ntx = nx / kT2X;
-  const int push_grid = cdiv(nx, lbm::kBlock);
-  int rc;
-  for (auto& s : c->slabs)
-    if ((rc = ensure_sums(s, nsteps))) return rc;
-  const bool march = k.nb == 0 && !dr && p2p_march_on(c) && nsteps >= slab_K(c);
-  if (march && (rc = check_march_partials(c, true))) return rc;   // (before anything is queued)
-
-  auto push = [&](Slab& s, const float* lat, uint32_t seq, bool do_push) -> int {
-    const int grid = do_push ? push_grid : 1;
-    lbm::P2PSync y = p2p_sync(s, seq, do_push ? grid : 0, do_push ? grid : 0);
-    hipLaunchKernelGGL(lbm::lbm_p2p_push, dim3(grid), dim3(lbm::kBlock), 0, s.sc, lat, s.plane, s.pitch, nx, s.nyl,
-                       p2p_remote_s(s, seq), p2p_remote_n(s, seq), y, do_push ? 1 : 0);
-    HIPC(hipGetLastError());
-    return LBM_OK;
-  };
-
-  // ---- prologue: accelerate phase of the first step
-  uint32_t seq = 0;
-  for (auto& s : c->slabs) {
-    HIPC(hipSetDevice(s.dev));
-    if (s.accel_row >= 0) {
-      hipLaunchKernelGGL(lbm::lbm_accelerate_row, dim3(cdiv(nx, 256)), dim3(256), 0, s.sc,
-                         s.lat[c->cur], s.plane, s.pitch, nx, s.accel_row, s.blocked, da1(0), da2(0));
-      HIPC(hipGetLastError());
-    }
-  }
-  const auto wall0 = std::chrono::steady_clock::now();
-  for (auto& s : c->slabs) {
-    HIPC(hipSetDevice(s.dev));
-    HIPC(hipEventRecord(s.ev_t0, s.sc));
-  }
-
-  int li = 0, tt = 0;
-  // ---- groups of K steps with lbm_march: the K ghost rows either side are read straight out of the neighbours'
-  // lattices.  Launch group seq of a slab starts once both neighbours have raised seq-1 ("my launch seq-1 is over":
-  // their rows are final, and they no longer read the lattice this launch overwrites) and raises seq when it is over.
-  if (march) {
-    const int K = slab_K(c);
-    auto raise = [&](Slab& s, uint32_t q) -> int {
-      const size_t f = 4 * s.halo_bytes;
-      hipLaunchKernelGGL(lbm::lbm_p2p_raise, dim3(1), dim3(64), 0, s.sc, (uint32_t*)(s.peer_s + f + 256), (uint32_t*)(s.peer_n + f), q);
-      HIPC(hipGetLastError());
-      return LBM_OK;
-    };
-    seq = ++c->seq;                                     // "the starting lattice is in place"
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      if ((rc = push(s, nullptr, seq, false))) return rc;   // (the neighbours are through with the previous run)
-      if ((rc = raise(s, seq))) return rc;
-    }
-    const int ngroups = nsteps / K;
-    for (int g = 0; g < ngroups; ++g, ++li, tt += K) {
-      seq = ++c->seq;
-      const int q = li & 1;
-      for (auto& s : c->slabs) {
-        HIPC(hipSetDevice(s.dev));
-        if ((rc = push(s, nullptr, seq, false))) return rc;   // wait for both neighbours' seq-1
-        const SlabNb nbr{s.nb_lat[0][c->cur], s.nb_lat[1][c->cur], s.nb_plane[0], s.nb_plane[1], s.nb_nyl[0], s.nb_nyl[1],
-                         s.nb_blocked[0], s.nb_blocked[1]};
-        if ((rc = launch_slab_pass(c, s, nbr, K, q, tt, tt + K < nsteps, g > 0))) return rc;
-        if ((rc = raise(s, seq))) return rc;
-      }
-      c->cur ^= 1;
-    }
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      const int nb = march_slab_blocks(c, s);
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(K), dim3(lbm::kBlock), 0, s.sc, s.partials[(li - 1) & 1], nb,
-                         s.sums + (tt - K), nb);
-      HIPC(hipGetLastError());
-    }
-  }
-  // ---- the remaining steps trade halos: push those of the lattice as it stands
-  if (tt < nsteps) {
-    seq = ++c->seq;
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      if ((rc = push(s, s.lat[c->cur], seq, true))) return rc;
-    }
-  }
-  if (pairs && nsteps - tt >= 2) {
-    const int npairs = (nsteps - tt) / 2;
-    for (int j = 0; j < npairs; ++j, ++li, tt += 2) {
-      seq = ++c->seq;
-      const int q = li & 1, qp = q ^ 1;
-      for (auto& s : c->slabs) {
-        HIPC(hipSetDevice(s.dev));
-        const int nty = s.nyl / kT2Y, nbtot = ntx * nty;
-        lbm::Sweep2Args a;
-        a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
-        a.plane = s.plane; a.pitch = s.pitch; a.nx = nx; a.ny = s.nyl;
-        a.blocked = s.blocked; a.omega = c->p.omega;
-        a.accel_row = s.accel_row >= 0 ? s.accel_row : lbm::kNoRow;
-        a.accel_out = (tt + 2 < nsteps) ? 1 : 0;
-        a.a1 = a1; a.a2 = a2;
-        a.partials1 = s.partials[q]; a.partials2 = s.partials[q] + nbtot;
-        a.prev1 = a.prev2 = nullptr; a.prev_count = 0; a.prev_sum = nullptr;
-        if (j > 0) { a.prev1 = s.partials[qp]; a.prev2 = s.partials[qp] + nbtot; a.prev_count = nbtot; a.prev_sum = s.sums + (tt - 2); }
-        a.by_begin = 0; a.by_count = nty; a.by_stride = 1;
-        a.ghost_s = s.ghost_s[(seq - 1) & 1]; a.ghost_n = s.ghost_n[(seq - 1) & 1];
-        a.blocked_gs = s.blocked_gs; a.blocked_gn = s.blocked_gn;
-        a.send_s = p2p_remote_s(s, seq); a.send_n = p2p_remote_n(s, seq);
-        a.sync = p2p_sync(s, seq, ntx, ntx);
-        launch_sweep2_k<lbm::kSweep2P2P>(c, a, nbtot, s.sc);
-        HIPC(hipGetLastError());
-      }
-      c->cur ^= 1;
-    }
-    const int ql = (li - 1) & 1;
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      const int nbtot = ntx * (s.nyl / kT2Y);
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(2), dim3(lbm::kBlock), 0, s.sc, s.partials[ql], nbtot, s.sums + (tt - 2), nbtot);
-      HIPC(hipGetLastError());
-    }
-  }
-  const int first_single = tt;
-  for (; tt < nsteps; ++tt, ++li) {
-    seq = ++c->seq;
-    const int q = li & 1, qp = q ^ 1;
-    const bool last = (tt == nsteps - 1);
-    const long h3 = 3L * nx;
-    for (auto& s : c->slabs) {
-      HIPC(hipSetDevice(s.dev));
-      if ((rc = push(s, nullptr, seq, false))) return rc;   // wait for the halos of launch seq-1
-      lbm::SweepArgs a;
-      a.src = s.lat[c->cur]; a.dst = s.lat[c->cur ^ 1];
-      a.plane = s.plane; a.pitch = s.pitch; a.nx = nx; a.nyl = s.nyl;
-      a.blocked = s.blocked; a.omega = c->p.omega;
-      a.accel_row = last ? -1 : s.accel_row;
-      a.a1 = last ? a1 : da1(tt + 1); a.a2 = last ? a2 : da2(tt + 1);   // (the rows it writes carry the NEXT step's accelerate phase)
-      a.partials = s.partials[q];
-      const float* gs = s.ghost_s[(seq - 1) & 1] + h3;
-      const float* gn = s.ghost_n[(seq - 1) & 1] + h3;
-      a.south2 = gs; a.south5 = gs + nx; a.south6 = gs + 2 * nx;
-      a.north4 = gn; a.north7 = gn + nx; a.north8 = gn + 2 * nx;
-      a.send_south = a.send_north = nullptr;
-      a.y_begin = 0; a.y_count = s.nyl; a.y_stride = 1;
-      const int nb = sweep_blocks(c, s.nyl);
-      a.prev_partials = nullptr; a.prev_count = 0; a.prev_sum = nullptr;
-      if (tt > first_single) { a.prev_partials = s.partials[qp]; a.prev_count = nb; a.prev_sum = s.sums + (tt - 1); }
-      launch_sweep(c, a, s.sc);
-      HIPC(hipGetLastError());
-      if ((rc = push(s, s.lat[c->cur ^ 1], seq, true))) return rc;   // the new edge rows, packed and pushed
-    }
-    c->cur ^= 1;
-    if (k.nb > 0 && (rc = launch_forces(c, tt, q, nsteps, k))) return rc;
-  }
-  const int ql = (li - 1) & 1;
-  for (auto& s : c->slabs) {
-    HIPC(hipSetDevice(s.dev));
-    if (first_single < nsteps) {
-      hipLaunchKernelGGL(lbm::lbm_fold_partials, dim3(1), dim3(lbm::kBlock), 0, s.sc, s.partials[ql],
-                         sweep_blocks(c, s.nyl), s.sums + (nsteps - 1), 0);
-      HIPC(hipGetLastError());
-    }
-    HIPC(hipEventRecord(s.ev_t1, s.sc));
-  }
-  return collect_sums(c, nsteps, av_vels, wall0, k);
-}
+// The two-step kernel's peer-to-peer kind (declared in lbm_host_slabs.inc, launched by launch_pair): its instantiations are
+// asked for HERE, behind everything above, which is where the code object has them.
+void launch_sweep2_p2p(const lbm_ctx* c, const lbm::Sweep2Args& a, int grid, hipStream_t st) { launch_sweep2_k<lbm::kSweep2P2P>(c, a, grid, st); }
 
 }  // namespace

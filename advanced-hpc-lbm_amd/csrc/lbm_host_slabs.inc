@@ -1,5 +1,6 @@
-// lbm_host_slabs.inc -- part of lbm_api.hip (included there, not a translation unit of its own): slab allocation and upload,
-// halo buffers and the peer-to-peer halo block, the launch helpers of the one- and two-step kernels, the halo exchange, the
+// lbm_host_slabs.inc -- part of lbm_api.hip (included there, not a translation unit of its own): the layout rules (row
+// partition, plane padding, the peer-to-peer halo block: slab_rows, slab_plane, CommLayout), slab allocation and upload, halo
+// buffers, the launch helpers of the one- and two-step kernels, the halo exchange and the peer-to-peer hand-off launches, the
 // per-step sums, the kernel defaults of a new context (finish_create).
 namespace {
 
@@ -12,6 +13,33 @@ int pick_vector_width(int nx) {
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- the layout rules, each in ONE place: every slab, and every rank about its neighbours, must come to the same numbers
+// The row partition: slab (or rank) i of n holds the global rows [row0, row0 + nyl).
+struct RowRange { int row0, nyl; };
+inline RowRange slab_rows(int ny, int n, int i) {
+  auto first = [=](long j) { return (int)(j * ny / n); };
+  return {first(i), first(i + 1) - first(i)};
+}
+// Floats per plane of a slab of nyl rows: the rows + 20.25 KiB (why: slab_alloc).
+inline long slab_plane(int nyl, int pitch) { return (long)nyl * pitch + 5184; }
+// The peer-to-peer halo block of a slab (Slab::comm_block), as byte offsets: the four nine-slot halo buffers (halo_bytes
+// each, a multiple of 256), the flag line the southern neighbour raises and the one the northern raises, the hipIpc handles
+// of lattice 0, lattice 1 and the obstacle map (a neighbouring PROCESS reads the slab's rows in place) and of the mail area
+// of the register tiles (zero: none).
+struct CommLayout {
+  size_t halo_bytes;
+  static constexpr size_t kFlagLine = 256, kHandle = sizeof(hipIpcMemHandle_t);
+  size_t ghost_s(int par) const { return (size_t)par * halo_bytes; }
+  size_t ghost_n(int par) const { return (size_t)(2 + par) * halo_bytes; }
+  size_t flag_s() const { return 4 * halo_bytes; }
+  size_t flag_n() const { return flag_s() + kFlagLine; }
+  size_t lattice_handles() const { return flag_n() + kFlagLine; }
+  size_t mail_handle() const { return lattice_handles() + 3 * kHandle; }
+  size_t total() const { return mail_handle() + kHandle; }
+};
+inline CommLayout comm_layout(int nx) { return {(sizeof(float) * lbm::kHaloSlots * (size_t)nx + 255) / 256 * 256}; }
+inline CommLayout comm_layout(const Slab& s) { return {s.halo_bytes}; }
 
 // Halo buffers of a slab for the context's exchange mode (callable again after a fallback from
 // peer-to-peer to RCCL: slab_free_halos first).
@@ -59,8 +87,9 @@ int slab_alloc_halos(lbm_ctx* c, Slab& s) {
   if (c->exchange == LBM_EXCHANGE_P2P) {
     HIPC(hipMalloc((void**)&s.blocked_gs, (size_t)nx));
     HIPC(hipMalloc((void**)&s.blocked_gn, (size_t)nx));
-    s.halo_bytes = (sizeof(float) * lbm::kHaloSlots * (size_t)nx + 255) / 256 * 256;
-    const size_t total = 4 * s.halo_bytes + 512 + 256;   // halos, two flag lines, the hipIpc handles of both lattices and the obstacle map
+    const CommLayout lay = comm_layout(nx);
+    const size_t total = lay.total();
+    s.halo_bytes = lay.halo_bytes;
     // uncached: the neighbours write it over xGMI behind this GPU's L2.  Fine-grained memory is NOT
     // accepted as a substitute (the local L2 may keep ghost rows a neighbour has since rewritten):
     // without uncached memory peer-to-peer halos count as unavailable and the caller uses RCCL.
@@ -71,8 +100,8 @@ int slab_alloc_halos(lbm_ctx* c, Slab& s) {
     HIPC(hipMemset(s.counters, 0, 64 * sizeof(uint32_t)));
     HIPC(hipDeviceSynchronize());
     for (int i = 0; i < 2; ++i) {
-      s.ghost_s[i] = (float*)(s.comm_block + (size_t)i * s.halo_bytes);
-      s.ghost_n[i] = (float*)(s.comm_block + (size_t)(2 + i) * s.halo_bytes);
+      s.ghost_s[i] = (float*)(s.comm_block + lay.ghost_s(i));
+      s.ghost_n[i] = (float*)(s.comm_block + lay.ghost_n(i));
     }
     if (c->rank_mode && c->nranks > 1) {
       // a neighbouring PROCESS reads this slab's rows in place (marching launches): it finds the handles here
@@ -81,7 +110,7 @@ int slab_alloc_halos(lbm_ctx* c, Slab& s) {
       HIPC(hipIpcGetMemHandle(&h[1], s.lat[1]));
       HIPC(hipIpcGetMemHandle(&h[2], s.blocked));
       static_assert(sizeof(hipIpcMemHandle_t) == 64, "three handles in 192 bytes");
-      HIPC(hipMemcpy(s.comm_block + 4 * s.halo_bytes + 512, h, sizeof(h), hipMemcpyHostToDevice));
+      HIPC(hipMemcpy(s.comm_block + lay.lattice_handles(), h, sizeof(h), hipMemcpyHostToDevice));
     }
   } else {
     const size_t hb = sizeof(float) * lbm::kHaloSlots * (size_t)nx;
@@ -108,7 +137,7 @@ int slab_alloc(lbm_ctx* c, Slab& s, bool exchanging) {
   // concurrent streams (kbench: plain 9-plane copy 4.9 -> 5.4 TB/s, sweep 5.35 -> 5.6 TB/s with
   // 4 KiB; a sweep over pads on two boxes put 5 x 4 KiB + 256 B at or next to the best for the
   // copy, the one-step and the two-step kernels, 2-8 % ahead of 4 KiB).
-  s.plane = (long)s.nyl * s.pitch + 5184;
+  s.plane = slab_plane(s.nyl, s.pitch);
   const size_t lat_bytes = sizeof(float) * 9 * (size_t)s.plane;
   for (int i = 0; i < 2; ++i) HIPC(hipMalloc((void**)&s.lat[i], lat_bytes));
   HIPC(hipMalloc((void**)&s.blocked, (size_t)s.plane));
@@ -362,6 +391,9 @@ void launch_sweep2(const lbm_ctx* c, const lbm::Sweep2Args& a, int grid, hipStre
   if (edge) launch_sweep2_k<lbm::kSweep2Edge>(c, a, grid, st);
   else launch_sweep2_k<lbm::kSweep2Plain>(c, a, grid, st);
 }
+// ... and of its peer-to-peer kind (defined at the end of lbm_host_run.inc: the code object keeps its kernels in the order
+// in which the source first asks for them, and these come last)
+void launch_sweep2_p2p(const lbm_ctx* c, const lbm::Sweep2Args& a, int grid, hipStream_t st);
 
 void slab_free(Slab& s) {
   slab_free_halos(s);
@@ -490,6 +522,43 @@ int exchange_halos(lbm_ctx* c, int q, int slot0, int nslots) {
   return LBM_OK;
 }
 
+// ---- peer-to-peer halos (LBM_EXCHANGE_P2P): no events, no host-side exchange -- launch group `seq` of a slab hands off
+// through the flags in the halo blocks (lbm::P2PSync).
+// The pointers of a slab for launch group `seq`; bumps the completion targets by the number of blocks that will count
+// themselves done on each side.
+lbm::P2PSync p2p_sync(Slab& s, uint32_t seq, int blocks_s, int blocks_n) {
+  lbm::P2PSync y;
+  const CommLayout lay = comm_layout(s);
+  y.flag_s = (const uint32_t*)(s.comm_block + lay.flag_s());
+  y.flag_n = (const uint32_t*)(s.comm_block + lay.flag_n());
+  y.rem_flag_s = (uint32_t*)(s.peer_s + lay.flag_n());   // I am the south neighbour's NORTH side
+  y.rem_flag_n = (uint32_t*)(s.peer_n + lay.flag_s());
+  y.cnt_s = s.counters; y.cnt_n = s.counters + 16; y.err = s.counters + 32;
+  s.cnt_s_total += (uint32_t)blocks_s; s.cnt_n_total += (uint32_t)blocks_n;
+  y.cnt_target_s = s.cnt_s_total; y.cnt_target_n = s.cnt_n_total;
+  y.seq = seq;
+  return y;
+}
+inline float* p2p_remote_s(const Slab& s, uint32_t seq) { return (float*)(s.peer_s + comm_layout(s).ghost_n(seq & 1)); }  // its ghost_n
+inline float* p2p_remote_n(const Slab& s, uint32_t seq) { return (float*)(s.peer_n + comm_layout(s).ghost_s(seq & 1)); }  // its ghost_s
+// One launch of lbm_p2p_push for group seq: waits for both neighbours' seq - 1; then, given a lattice, packs its edge rows
+// and pushes them into the neighbours' blocks as seq (lat == nullptr: the wait alone, one block).
+int p2p_push(const lbm_ctx* c, Slab& s, const float* lat, uint32_t seq) {
+  const int push = lat ? 1 : 0, grid = push ? cdiv(c->p.nx, lbm::kBlock) : 1;
+  const lbm::P2PSync y = p2p_sync(s, seq, push * grid, push * grid);
+  hipLaunchKernelGGL(lbm::lbm_p2p_push, dim3(grid), dim3(lbm::kBlock), 0, s.sc, lat, s.plane, s.pitch, c->p.nx, s.nyl,
+                     p2p_remote_s(s, seq), p2p_remote_n(s, seq), y, push);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+// ... and of lbm_p2p_raise: "my launch group seq is over", into both neighbours' flags (the marching launches, which push nothing)
+int p2p_raise(Slab& s, uint32_t seq) {
+  const CommLayout lay = comm_layout(s);
+  hipLaunchKernelGGL(lbm::lbm_p2p_raise, dim3(1), dim3(64), 0, s.sc, (uint32_t*)(s.peer_s + lay.flag_n()), (uint32_t*)(s.peer_n + lay.flag_s()), seq);
+  HIPC(hipGetLastError());
+  return LBM_OK;
+}
+
 // Per-step sums of a run.  Sized once at lbm_create for the deck's own maxIters and grown
 // geometrically, so that a run never allocates unless it is longer than anything before it (an
 // allocation inside lbm_run costs more than a 20-step run of 1024^2).  Where no collective reduces
@@ -602,7 +671,7 @@ int finish_create(lbm_ctx* c, const int* obstacles, const float* cells) {
       else {
         hipIpcMemHandle_t h;
         if (hipIpcGetMemHandle(&h, s0.tmail) != hipSuccess) { (void)hipGetLastError(); c->tplan.ty = 0; }
-        else HIPC(hipMemcpy(s0.comm_block + 4 * s0.halo_bytes + 512 + 192, &h, sizeof(h), hipMemcpyHostToDevice));
+        else HIPC(hipMemcpy(s0.comm_block + comm_layout(s0).mail_handle(), &h, sizeof(h), hipMemcpyHostToDevice));
       }
     }
     // Four steps per pass (lbm_march) where its strips and chunks fill the chip: measured 1.5-1.6x
